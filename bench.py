@@ -25,12 +25,22 @@ Other workloads (`--workload`), each with its own roofline line:
   pipeline  the metric's second half: `kmx pipeline` end to end (FASTA files in, matrix files out) on configs[2]'s cohort at the
          size the GPU box's disk takes (1000 samples x 1 Mbp, 256 partitions), wall clock and k-mers merged/s end to end, with
          the oracle's split + count + merge on the host cores over a bounded sample of the same files beside it
-  all    (default on one GPU) the headline count workload first -- its fields are the line's own --, then count_stage, bf, bft, pa63,
-         count_200 and pipeline: their lines go into "workloads" / "pipeline" of the ONE JSON line
+  all    (default on one GPU with --full) the headline count workload first -- its fields are the line's own --, then count_stage, bf,
+         bft, pa63, count_200 and pipeline: their lines go into "workloads" / "pipeline" of the ONE JSON line
+
+A plain run (`--gpus 1 --steps N --warmup W`) is the headline count workload alone: set-up, W warm-up steps, N timed steps, the line.
+Everything else it used to carry moves behind --full: the other workloads and the end-to-end runs, the CPU baselines, the whole-job
+and rows-left-in-arena passes (runs of their own behind the timed steps), the k = 96 end-to-end run, and with several ranks the
+`kmx pipeline --gpus N` point and the per-rank probe.
+
+--dump-outputs DIR: after the timed steps, what the last one computed (rank 0's kmx_merge_dev result) as DIR/<name>.npy (float64):
+rows per task, the merge statistics, byte sums of every column of each matrix body over all its rows, and a fixed seeded sample of
+whole rows with their indices -- the same arguments give the same inputs, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
-import argparse, json, os, sys, time
+import argparse, collections, json, os, sys, time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -104,37 +114,51 @@ def gen_counted(ctx, lib, N, k, genome, d, total_parts, my_parts, seed, log, all
     import numpy as np
     m = 10
     table = (xxh64_u32(np.arange(4 ** m, dtype=np.uint32)) % np.uint64(total_parts)).astype(np.uint16)
-    anc = np.random.Generator(np.random.PCG64(seed)).integers(0, 4, genome, dtype=np.uint8)
-    letters = np.frombuffer(b"ACGT", np.uint8)
     store = lib.Store(ctx.device, limit_bytes=200 << 30)
     lists = [[] for _ in my_parts]
+    anc = np.random.Generator(np.random.PCG64(seed)).integers(0, 4, genome, dtype=np.uint8)
     L = 2000
-    starts = np.arange(0, genome - k + 1, L)
-    win = starts[:, None] + np.arange(L + k - 1)[None, :]                # (the last window runs into a tail of N's: no k-mers there)
-    offs = (np.arange(2 * len(starts) + 1, dtype=np.uint64) * np.uint64(L + k - 1))
+    bases = np.concatenate([np.frombuffer(b"ACGT", np.uint8)[anc], np.full(L, ord("N"), np.uint8)])
+    offs = (np.arange(2 * len(range(0, genome - k + 1, L)) + 1, dtype=np.uint64) * np.uint64(L + k - 1))
+    # the samples' bases are made on host threads (the random draws release the GIL) while this thread counts them in sample order
+    # (at most 16 threads: a large host's affinity set is far more than the set-up needs)
+    nthr = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
     t0 = time.perf_counter()
-    for i in range(N):
-        rng = np.random.Generator(np.random.PCG64(seed + 1 + i))
-        gsm = anc.copy()
-        pos = np.nonzero(rng.random(genome) < d)[0]
-        gsm[pos] = (gsm[pos] + rng.integers(1, 4, len(pos), dtype=np.uint8)) & 3
-        # the genome as overlapping 2 kb windows (every k-mer exactly once; a wave per read in the split), twice
-        seq = np.concatenate([letters[gsm], np.full(L, ord("N"), np.uint8)])[win].tobytes()
-        ls, _, _ = ctx.count_reads_dev((seq + seq, offs), k, m, table, total_parts, 2, [store])
-        for j, p in enumerate(my_parts):
-            lists[j].append(ls[p])
-        if all_lists is not None:      # (every partition of the job: the whole-job figure of a one-GPU run)
-            for p in range(total_parts):
-                all_lists[p].append(ls[p])
-        if log and (i + 1) % 100 == 0:
-            print(f"[bench] counted lists: {i + 1}/{N} samples, {time.perf_counter() - t0:.1f} s, {store.used() / 1e9:.1f} GB resident", file=sys.stderr, flush=True)
+    with ThreadPoolExecutor(nthr) as ex:
+        ahead = collections.deque(ex.submit(counted_sample_bases, anc, bases, k, d, seed, i, L) for i in range(min(N, 2 * nthr)))
+        for i in range(N):
+            seq = ahead.popleft().result()
+            if i + len(ahead) + 1 < N:
+                ahead.append(ex.submit(counted_sample_bases, anc, bases, k, d, seed, i + len(ahead) + 1, L))
+            ls, _, _ = ctx.count_reads_dev((seq, offs), k, m, table, total_parts, 2, [store])
+            for j, p in enumerate(my_parts):
+                lists[j].append(ls[p])
+            if all_lists is not None:      # (every partition of the job: the whole-job figure of a one-GPU run)
+                for p in range(total_parts):
+                    all_lists[p].append(ls[p])
+            if log and (i + 1) % 100 == 0:
+                print(f"[bench] counted lists: {i + 1}/{N} samples, {time.perf_counter() - t0:.1f} s, {store.used() / 1e9:.1f} GB resident", file=sys.stderr, flush=True)
     return store, lists
 
 
+def counted_sample_bases(anc, bases, k, d, seed, i, L=2000):
+    """gen_counted's sample i: the ancestor genome anc (2-bit codes; bases: its letters followed by L N's) with i.i.d. substitutions
+    at rate d (PCG64(seed + 1 + i)), as overlapping windows of L + k - 1 bases starting every L (every k-mer exactly once; a wave per
+    read in the split; the last window runs into the tail of N's: no k-mers there), the whole set given twice -> bytes"""
+    import numpy as np
+    genome = len(anc)
+    rng = np.random.Generator(np.random.PCG64(seed + 1 + i))
+    pos = np.nonzero(rng.random(genome) < d)[0]
+    g = bases.copy()
+    g[pos] = np.frombuffer(b"ACGT", np.uint8)[(anc[pos] + rng.integers(1, 4, len(pos), dtype=np.uint8)) & 3]
+    w = np.lib.stride_tricks.sliding_window_view(g, L + k - 1)[np.arange(0, genome - k + 1, L)]
+    return np.concatenate([w, w]).tobytes()
+
+
 # ---------------------------------------------------------------------------------------------- merge workloads
-def merge_workload(env, a, wl, lists_kind, want_cpu):
+def merge_workload(env, a, wl, lists_kind, want_cpu, dump_dir=None):
     """One `--workload` of the merge stage: builds its lists on this rank's GPU, times a.steps batches, returns the JSON fields
-    (on rank 0; None elsewhere)."""
+    (on rank 0; None elsewhere).  dump_dir: where rank 0 writes the last timed step's result (dump_outputs)."""
     torch, dist, lib, shard = env["torch"], env["dist"], env["lib"], env["shard"]
     rank, world, local, dev = env["rank"], env["world"], env["local"], env["dev"]
     import numpy as np
@@ -169,7 +193,7 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
     if wl in ("count", "pa63"):
         mode = lib.MODE_COUNT if wl == "count" else lib.MODE_PA
         if lists_kind == "counted":
-            job_lists = [[] for _ in range(total_parts)] if (wl == "count" and not small and not wide and world == 1 and a.whole_job) else None
+            job_lists = [[] for _ in range(total_parts)] if (wl == "count" and not small and not wide and world == 1 and a.full and a.whole_job) else None
             store, lists = gen_counted(ctx, lib, N, k, genome, a.subst_rate, total_parts, my_parts, 20240601, rank == 0, job_lists)
             keep.append(store)
             def host_lists(j):
@@ -228,14 +252,17 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
         n8 = (N + 7) // 8 * 8
         xbuf = [torch.empty((n8, W // 8), dtype=torch.uint8, device=dev) for _ in range(P)]
 
-    def run(n, record, batches=None):
+    held = []
+
+    def run(n, record, batches=None, hold_last=False):
         """n steps = n kmx_merge_dev batches; batch i+1 is submitted before batch i is waited for (the host
         prepares the next batch while the GPU merges the current one, as the pipeline driver does with
         consecutive partition batches); every batch is waited for before the clock stops.
-        batches: a list of prepared task batches run once each instead (the whole job of a one-GPU run)."""
+        batches: a list of prepared task batches run once each instead (the whole job of a one-GPU run).
+        hold_last: the last batch's result is kept in `held` instead of freed (--dump-outputs)."""
         nonlocal algo_bytes, rows_out
 
-        def finish(res):
+        def finish(res, last=False):
             nonlocal algo_bytes, rows_out, kernel_name
             res.wait()
             if xbuf is not None:      # per-sample Bloom rows to their owners: the one collective of the path (RCCL all-to-all)
@@ -249,7 +276,10 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
                 algo_bytes = sum(res.algo_bytes(t) for t in range(P))
                 rows_out = sum(res.rows(t) for t in range(P))
                 kernel_name = res.kernel()
-            res.free()
+            if last and hold_last:
+                held.append(res)
+            else:
+                res.free()
 
         prev = None                      # two batches in flight (double buffering: no new device blocks)
         for it in range(n if batches is None else len(batches)):
@@ -258,7 +288,7 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
                 finish(prev)
             prev = cur
         if prev is not None:
-            finish(prev)
+            finish(prev, last=True)
 
     # setup, not warm-up: libkmx sizes its row arenas from the batches it has completed (the first ones of a cohort run twice, and
     # the first arenas of the final size are fresh hipMallocs): three batches, one at a time, before the W warm-up steps
@@ -267,10 +297,15 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
     run(a.warmup, False)
     barrier()
     t0 = time.perf_counter()
-    run(a.steps, True)
+    run(a.steps, True, hold_last=dump_dir is not None)
     barrier()
     dt = time.perf_counter() - t0
     dt, job_recs = shard.reduce_job(dist if world > 1 else None, dev, dt, float(total_recs))
+    for res in held:
+        if rank == 0:
+            dump_outputs(dump_dir, res, len(tasks_d), torch, dev)
+        res.free()
+    held.clear()
     # ---- on one GPU, the WHOLE job: all partitions of configs[2] (8 batches of 32 on one MI355X), rows in file order ----
     whole_job = None
     if job_lists is not None and rank == 0:
@@ -293,7 +328,7 @@ def merge_workload(env, a, wl, lists_kind, want_cpu):
     #      k_cols_sparse, each list ascending -- NOT the matrix body; the headline of rounds 1-4, kept for continuity) ----
     arena = None
     gather_ms = order_ms = None
-    if wl in ("count", "pa63") and hasattr(ctx, "set_file_order"):
+    if a.full and wl in ("count", "pa63") and hasattr(ctx, "set_file_order"):
         ctx.set_file_order(False)
         head_ms, head_name, head_algo, head_rows = list(kernel_ms), kernel_name, algo_bytes, rows_out
         kernel_ms.clear()
@@ -526,7 +561,7 @@ def pipeline_workload(a, n_gpus=1, genome=None, tmp_root=None, cpu=True):
             out["warmup"] = f"one untimed run of the same command over {'the cohort' if warm_n == S else 'the first ' + str(warm_n) + ' samples'} in front of the timed one"
         elif genome is not None:
             out["warmup"] = "none: the timed run is the first job of its size on this box"
-        if genome is None:
+        if genome is None and a.full:
             # the same files at k = 96 (Kmer<128>, keys of three words: the reference's default KMER_LIST reaches 128) -- the
             # split by k_superk_wide, the decode by k_superk_decode_wide, the word-by-word sort, k_merge_rows<3>
             try:
@@ -546,7 +581,7 @@ def pipeline_workload(a, n_gpus=1, genome=None, tmp_root=None, cpu=True):
                 shutil.rmtree(run, ignore_errors=True)
             except Exception as e:
                 out["wide_k"] = {"error": repr(e)}
-        if not a.no_cpu_baseline and cpu:
+        if a.full and not a.no_cpu_baseline and cpu:
             # the host's share: the oracle over a bounded sample of the same files, in a process of its own (a plain Python process
             # forks its workers cheaply; this one may hold a HIP runtime and tens of GB of mappings)
             try:
@@ -627,6 +662,9 @@ def parse_args(argv=None):
     ap.add_argument("--tmp-ram", default="/dev/shm", help="RAM file system for the end-to-end workload at full size (5 Mbp genomes: 130 GB of files)")
     ap.add_argument("--no-full-size", dest="full_size", action="store_false", help="skip the end-to-end run at G = 5 Mbp")
     ap.add_argument("--no-multi-gpu-pipeline", dest="multi_gpu_pipeline", action="store_false", help="several ranks: skip the `kmx pipeline --gpus N` point behind the merge steps")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: every workload (one GPU, default workload), "
+                    "CPU baselines, the whole-job and rows-left-in-arena passes, the k = 96 and full-size end-to-end runs, the multi-rank pipeline point and probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -636,8 +674,10 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     wl = a.workload
-    if wl == "auto":      # one GPU: every workload in one invocation; several ranks (the scaling runs): the headline workload
-        wl = "all" if world == 1 else "count"
+    if wl == "auto":      # the headline workload; with --full on one GPU every workload in one invocation
+        wl = "all" if (a.full and world == 1) else "count"
+    if a.dump_outputs is not None and wl in ("pipeline", "count_stage"):
+        sys.exit(f"--dump-outputs: the merge workloads only (not {wl})")
     if wl == "pipeline":
         if rank == 0:
             print(json.dumps(pipeline_workload(a, a.gpus if world == 1 else 1)))
@@ -674,13 +714,13 @@ def run_workloads(a, wl, env):
     (None on one rank), lib (the ctypes binding of libkmx), shard, rank, world, local, dev (+ sync / empty_cache overrides: the CPU
     test of this plumbing runs it under a two-rank gloo group with a stand-in for lib)"""
     rank, world = env["rank"], env["world"]
-    want_cpu = not a.no_cpu_baseline and world == 1      # (the host baseline is a 1-GPU line: with more ranks the others would wait at the barrier for it)
+    want_cpu = a.full and not a.no_cpu_baseline and world == 1      # (the host baseline is a 1-GPU line: with more ranks the others would wait at the barrier for it)
     extras, pipe, head = {}, None, None
     if wl == "all":
         t_all = time.perf_counter()
         # the headline workload first (round 6): on device memory nothing has been carved up yet -- behind the other workloads and the
         # end-to-end runs the same 20 steps read 3 % slower (4.95 against 4.79 ms on one box, the same build minutes apart)
-        head = merge_workload(env, a, "count", a.lists, want_cpu)
+        head = merge_workload(env, a, "count", a.lists, want_cpu, a.dump_outputs)
         if rank == 0:
             print(f"[bench] workload count (the line's own) done, {time.perf_counter() - t_all:.0f} s", file=sys.stderr, flush=True)
         for w in ("count_stage", "bf", "bft", "pa63", "count_200"):
@@ -698,7 +738,7 @@ def run_workloads(a, wl, env):
             print(f"[bench] workload pipeline done, {time.perf_counter() - t_all:.0f} s", file=sys.stderr, flush=True)
             # ... and at SURVEY 8d's stated size (G = 5 Mbp: 30 GB of FASTA in, ~100 GB of count matrices out -- more than the box's
             # disk): in a RAM file system when the box has one with room for it
-            if a.full_size and isinstance(pipe, dict) and "error" not in pipe:
+            if a.full and a.full_size and isinstance(pipe, dict) and "error" not in pipe:
                 try:
                     import shutil as _sh
                     big = a.tmp_ram if os.path.isdir(a.tmp_ram) else None
@@ -714,8 +754,8 @@ def run_workloads(a, wl, env):
         wl = "count"
     if wl == "count_stage":
         return count_stage_workload(env, a) if rank == 0 else None
-    out = head if head is not None else merge_workload(env, a, wl, a.lists, want_cpu)
-    if world > 1 and a.multi_gpu_pipeline and wl == "count" and env.get("run_pipeline", True):
+    out = head if head is not None else merge_workload(env, a, wl, a.lists, want_cpu, a.dump_outputs)
+    if world > 1 and a.full and a.multi_gpu_pipeline and wl == "count" and env.get("run_pipeline", True):
         # several ranks (the scaling runs): the PRODUCT's own multi-GPU path gets a point too -- `kmx pipeline --gpus <world>`, one
         # process driving every GPU of the node (partitions p -> GPU p mod G, count lists to the merging GPU's store over xGMI),
         # started by rank 0 once every rank has let go of its device memory; the other ranks wait at the barrier
@@ -727,7 +767,7 @@ def run_workloads(a, wl, env):
                 pipe = {"error": repr(e)}
         env["dist"].barrier()
     per_rank = None
-    if world > 1:
+    if world > 1 and a.full:
         per_rank = rank_probe(env)      # (every rank takes part: a collective)
     if rank == 0:
         # what the scaling runs need to be read without a second look: the world the ranks saw, and the one-GPU line of the last round
@@ -783,6 +823,44 @@ def rank_probe(env):
     else:
         out = [rec]
     return out
+
+
+def dump_outputs(out_dir, res, n_tasks, torch, dev, budget=48 << 20):
+    """--dump-outputs: what a caller of kmx_merge_dev receives from the last timed step -- per task the matrix body (rows of
+    row_bytes in file order), its row count and the merge statistics -- as float64 arrays in out_dir/<name>.npy:
+      rows[t]                  kept rows of task t
+      stats[t, 6, lists]       kmx_result_copy_stats
+      column_sums[t, b]        byte b of every row summed over all rows of task t's body (the whole body, exactly)
+      sample_index[t, s]       a fixed seeded sample of row indices (seed 20240601 + t; -1 past the task's rows)
+      sample_rows[t, s, w]     those rows whole, as u32 words (u8 when row_bytes is not a multiple of 4; NaN past the rows)
+    The sample takes what the budget (bytes in all) leaves; the body goes through device memory (kmx_result_copy_body_dev), never
+    whole to the host."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = [int(res.rows(t)) for t in range(n_tasks)]
+    rb = [int(res.row_bytes(t)) for t in range(n_tasks)]
+    wide = all(b % 4 == 0 for b in rb)
+    width = max(b // 4 if wide else b for b in rb)
+    stats = np.stack([res.stats(t) for t in range(n_tasks)]).astype(np.float64)
+    S = max(1, (budget - 8 * n_tasks * (max(rb) + 1) - stats.nbytes) // (8 * n_tasks * (max(1, width) + 1)))
+    sums = np.zeros((n_tasks, max(rb)), np.float64)
+    index = np.full((n_tasks, S), -1.0)
+    sample = np.full((n_tasks, S, width), np.nan)
+    buf = torch.empty(max(1, max(r * b for r, b in zip(rows, rb))), dtype=torch.uint8, device=dev)
+    for t in range(n_tasks):
+        if rows[t] == 0:
+            continue
+        res.body_to_device(t, buf.data_ptr(), rows[t] * rb[t])
+        body = buf[:rows[t] * rb[t]].view(rows[t], rb[t])
+        sums[t, :rb[t]] = body.sum(0, dtype=torch.int64).cpu().numpy()
+        idx = np.sort(np.random.default_rng(20240601 + t).choice(rows[t], min(S, rows[t]), replace=False))
+        got = body[torch.from_numpy(idx).to(dev)].cpu().numpy()
+        index[t, :len(idx)] = idx
+        sample[t, :len(idx), :got.shape[1] // (4 if wide else 1)] = got.view(np.uint32) if wide else got
+    arrays = dict(rows=np.array(rows, np.float64), stats=stats,
+                  column_sums=sums, sample_index=index, sample_rows=sample)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
 
 
 def pmc_traffic(wl, lists, N, P, kernel):

@@ -1,10 +1,10 @@
-# one workload's kernel time under several tuning builds of libkmx (scripts/dev/build_variant.sh): bench_variants.sh <dir> <workload> <name>...
+# one workload's kernel time under several tuning builds of libkmx (scripts/dev/build_variant.sh): bench_variants.sh <output directory> <workload> <name>...
 d=$1; wl=$2; shift; shift
-mkdir -p gpurun_out/$d
+mkdir -p $d
 for v in "$@"; do
   lib=""; [ "$v" != "product" ] && lib=$GRAFT_REPO_ROOT/kmtricks_amd/libkmx_$v.so
-  KMX_LIB=$lib python bench.py --workload $wl --no-cpu-baseline --steps 10 $EXTRA > gpurun_out/$d/${wl}_$v.json 2> gpurun_out/$d/${wl}_$v.err
-  python - gpurun_out/$d/${wl}_$v.json $v <<PY
+  KMX_LIB=$lib python bench.py --workload $wl --full --no-cpu-baseline --steps 10 $EXTRA > $d/${wl}_$v.json 2> $d/${wl}_$v.err
+  python - $d/${wl}_$v.json $v <<PY
 import json, sys
 try:
     d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -1,6 +1,6 @@
 for v in 1 0; do for N in 500 200 1000 300; do
   echo -n "narrow=$v N=$N: "
-  KMX_DENSE_NARROW=$v KMX_MERGE_KERNEL=cols timeout 300 python bench.py --workload count --lists random --samples $N --subst-rate 0.001 --steps 4 --warmup 2 --no-cpu-baseline --no-whole-job 2>&1 | python -c "
+  KMX_DENSE_NARROW=$v KMX_MERGE_KERNEL=cols timeout 300 python bench.py --workload count --lists random --samples $N --subst-rate 0.001 --steps 4 --warmup 2 --full --no-cpu-baseline --no-whole-job 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 for cfg in ${CFGS:-"128 32" "128 128" "128 256" "200 128"}; do set -- $cfg; for K in ${KS:-rows cols auto}; do
   echo -n "N=$1 partitions=$2 $K: "
   if [ $K = auto ]; then unset KMX_MERGE_KERNEL; else export KMX_MERGE_KERNEL=$K; fi
-  timeout 300 python bench.py --workload count --lists random --samples $1 --partitions-per-gpu $2 --subst-rate 0.001 --steps 4 --warmup 2 --no-cpu-baseline --no-whole-job 2>&1 | python -c "
+  timeout 300 python bench.py --workload count --lists random --samples $1 --partitions-per-gpu $2 --subst-rate 0.001 --steps 4 --warmup 2 --full --no-cpu-baseline --no-whole-job 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

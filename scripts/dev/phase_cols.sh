@@ -2,7 +2,7 @@
 # bench.py runs the steps with the rows where the kernels leave them first, then in file order -- two dumps per workload
 for wl in ${WLS:-count pa63}; do
   echo "== $wl $EXTRA"
-  KMX_LIB=$GRAFT_REPO_ROOT/kmtricks_amd/libkmx_prof.so python bench.py --workload $wl --steps 1 --warmup 1 --no-cpu-baseline --no-whole-job $EXTRA 2>&1 | grep -E "^\[cols\]|^\[sparse\]" > /tmp/ph.txt
+  KMX_LIB=$PWD/kmtricks_amd/libkmx_prof.so python bench.py --workload $wl --steps 1 --warmup 1 --full --no-cpu-baseline --no-whole-job $EXTRA 2>&1 | grep -E "^\[cols\]|^\[sparse\]" > /tmp/ph.txt
   python - <<'PY'
 import re, collections
 # every result free dumps both tables: sum the dumps of the arena steps (first half) and of the file-order steps (second half)

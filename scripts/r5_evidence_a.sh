@@ -3,7 +3,7 @@
 # -> gpurun_out/r5e/ (copied to profiles/ by hand)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5e; mkdir -p $O; cd $R
 line() { grep '^{"metric' | tail -1; }
-( time python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/err_all.log | line > $O/bench_all.json ) 2> $O/time_all.txt
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>$O/err_all.log | line > $O/bench_all.json ) 2> $O/time_all.txt
 python scripts/r5_grid.py --wl count --steps 10 --settings "x=1" > $O/pair_parts.jsonl 2>$O/err_parts.log
 python scripts/r5_grid.py --wl pa63 --steps 10 --settings "x=1" >> $O/pair_parts.jsonl 2>>$O/err_parts.log
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -5 > $O/gpu_tests.txt

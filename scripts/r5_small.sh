@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5s; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for N in ${NS:-128 200}; do for K in rows cols; do
   rm -rf $O/p; mkdir -p $O/p
-  KMX_MERGE_KERNEL=$K timeout 600 rocprofv3 --kernel-trace --stats -d $O/p --output-format csv -- python $R/bench.py --workload count --samples $N --steps 10 --warmup 2 --no-cpu-baseline --no-whole-job > $O/log_${N}_$K.txt 2>&1
+  KMX_MERGE_KERNEL=$K timeout 600 rocprofv3 --kernel-trace --stats -d $O/p --output-format csv -- python $R/bench.py --workload count --samples $N --steps 10 --warmup 2 --full --no-cpu-baseline --no-whole-job > $O/log_${N}_$K.txt 2>&1
   echo "== N=$N $K" >> $O/small.txt
   grep '^{' $O/log_${N}_$K.txt | tail -1 | python -c "
 import sys,json

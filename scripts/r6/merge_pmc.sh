@@ -2,7 +2,7 @@
 # round 6: SQ counters of a merge workload's kernels (WL = count_200 | count | pa63 | bft | bf): how busy the vector units are
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6mpmc; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for P in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE"; do
-  timeout 900 rocprofv3 --pmc $P -d $O/p --output-format csv -- python $R/bench.py --workload ${WL:-count_200} --steps 3 --warmup 1 --no-cpu-baseline --no-whole-job > $O/log.txt 2>&1
+  timeout 900 rocprofv3 --pmc $P -d $O/p --output-format csv -- python $R/bench.py --workload ${WL:-count_200} --steps 3 --warmup 1 --full --no-cpu-baseline --no-whole-job > $O/log.txt 2>&1
   python - <<PY
 import glob, csv, collections
 acc = collections.defaultdict(lambda: [0.0, 0])

@@ -1,9 +1,10 @@
 #!/bin/bash
 # round 6: kernel trace of the whole job of configs[2] on one GPU (8 batches of 32 partitions, two in flight): where 56 ms go when a batch's pair takes 4.8
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r6wj${TAG:-}
 rm -rf $O; mkdir -p $O
-timeout 900 rocprofv3 --kernel-trace --memory-copy-trace -d $O/trace --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --workload count --steps 3 --warmup 1 --no-cpu-baseline ${ARGS:-} > $O/bench.json 2> $O/trace.log
+timeout 900 rocprofv3 --kernel-trace --memory-copy-trace -d $O/trace --output-format csv -- python $R/bench.py --workload count --steps 3 --warmup 1 --full --no-cpu-baseline ${ARGS:-} > $O/bench.json 2> $O/trace.log
 python - <<PY > $O/timeline.txt
 import csv, glob
 ev = []

@@ -9,10 +9,10 @@ cd /tmp && export TMPDIR=/tmp
 prof() { L=$1; shift; rm -rf $O/prof_$L; mkdir -p $O/prof_$L
   timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof_$L --output-format csv -- "$@" > $O/prof_$L.log 2>&1
   find $O/prof_$L -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_$L.csv \; ; grep '^{' $O/prof_$L.log | tail -1 > $O/line_under_rocprof_$L.json; rm -rf $O/prof_$L; }
-prof count python $R/bench.py --workload count --no-cpu-baseline --no-whole-job
+prof count python $R/bench.py --workload count --full --no-cpu-baseline --no-whole-job
 prof bf python $R/bench.py --workload bf --no-cpu-baseline
 prof bft python $R/bench.py --workload bft --no-cpu-baseline
-prof pa63 python $R/bench.py --workload pa63 --no-cpu-baseline
+prof pa63 python $R/bench.py --workload pa63 --full --no-cpu-baseline
 cd $R
 bash scripts/r5_pmc_traffic.sh > /dev/null 2>&1; cp gpurun_out/r5pmc/traffic.txt $O/pmc_traffic_count.txt
 WL=pa63 bash scripts/r5_pmc_traffic.sh > /dev/null 2>&1; cp gpurun_out/r5pmc/traffic.txt $O/pmc_traffic_pa63.txt

@@ -24,6 +24,10 @@ class _StubResult:
     def body_to_device(self, t, ptr, n):
         ctypes.memset(ptr, (self.o.rank * 16 + t) & 0xFF, n)
         self.o.log.append(f"body{t}")
+    def row_bytes(self, t): return 12
+    def stats(self, t):
+        import numpy as np
+        return np.arange(6 * 6, dtype=np.uint64).reshape(6, 6) + t
 
 
 class _StubContext:
@@ -61,7 +65,7 @@ def _worker(rank, world, port, q, argv, wl):
 def test_bench_rank_plumbing_two_ranks(wl, extra):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--samples", "6", "--partitions-per-gpu", "2", "--total-partitions", "4",
-            "--genome", "4000", "--bloom", "4096", "--no-cpu-baseline"] + extra
+            "--genome", "4000", "--bloom", "4096", "--no-cpu-baseline", "--full"] + extra
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q, argv, wl)) for r in range(2)]
@@ -90,3 +94,53 @@ def test_bench_rank_plumbing_two_ranks(wl, extra):
     pr = out0["ranks"]["per_rank"]
     assert out0["ranks"]["world_size"] == 2 and [x["rank"] for x in pr] == [0, 1] and all(x["world_size_seen"] == 2 for x in pr)
     assert all("error" not in x and x["bloom_exchange"]["ok"] and x["bloom_exchange"]["bytes_sent"] > 0 for x in pr)
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """One rank, no --full: the set-up batches, W warm-up and N timed steps and nothing behind them (no CPU baseline, whole-job or
+    rows-left-in-arena pass); --dump-outputs writes the last timed step's result as float .npy files, the same on a second run."""
+    import numpy as np
+    import bench
+    from kmtricks_amd import shard
+
+    def plain(out):
+        a = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2", "--samples", "6", "--partitions-per-gpu", "2",
+                              "--total-partitions", "4", "--genome", "4000", "--lists", "random", "--dump-outputs", str(out)])
+        env = dict(torch=torch, dist=None, lib=_StubLib, shard=shard, rank=0, world=1, local=0, dev=torch.device("cpu"),
+                   sync=lambda: None, empty_cache=lambda: None)
+        return bench.run_workloads(a, "count", env), list(_StubLib.last_log)
+
+    out, log = plain(tmp_path / "a")
+    json.dumps(out)
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert "cpu_baseline" not in out and "workloads" not in out and "pipeline" not in out
+    assert out["roofline"]["whole_job"] is None and out["roofline"]["rows_left_in_arena"] is None
+    assert log.count("submit") == 3 + 2 + 4 and log.count("free") == log.count("submit")
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"rows.npy", "stats.npy", "column_sums.npy", "sample_index.npy", "sample_rows.npy"}
+    assert all(x.dtype in (np.float32, np.float64) for x in got.values()) and sum(x.nbytes for x in got.values()) <= 64 << 20
+    assert list(got["rows.npy"]) == [8, 8] and got["stats.npy"].shape == (2, 6, 6)
+    assert list(got["column_sums.npy"][1]) == [8 * 1] * 12                     # task 1's body: every byte 1 (the stub's fill)
+    assert np.array_equal(got["sample_rows.npy"][1, :8], np.full((8, 3), 0x01010101))
+    out2, _ = plain(tmp_path / "b")
+    for f, x in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f), x, equal_nan=True), f
+
+
+def test_counted_sample_bases_are_the_windows_of_the_mutated_genome():
+    """bench.gen_counted's inputs: sample i = the ancestor with the substitutions PCG64(seed + 1 + i) draws, cut into windows of
+    L + k - 1 bases every L bases (N's past the genome's end), the set twice -- built here the straightforward way"""
+    import numpy as np
+    import bench
+    G, k, d, seed, L = 50_000, 31, 0.01, 20240601, 2000
+    anc = np.random.Generator(np.random.PCG64(seed)).integers(0, 4, G, dtype=np.uint8)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    bases = np.concatenate([letters[anc], np.full(L, ord("N"), np.uint8)])
+    for i in (0, 1, 7):
+        rng = np.random.Generator(np.random.PCG64(seed + 1 + i))
+        g = anc.copy()
+        pos = np.nonzero(rng.random(G) < d)[0]
+        g[pos] = (g[pos] + rng.integers(1, 4, len(pos), dtype=np.uint8)) & 3
+        ext = np.concatenate([letters[g], np.full(L, ord("N"), np.uint8)])
+        seq = b"".join(ext[s:s + L + k - 1].tobytes() for s in range(0, G - k + 1, L))
+        assert len(pos) > 0 and bench.counted_sample_bases(anc, bases, k, d, seed, i, L) == seq + seq

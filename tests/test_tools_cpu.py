@@ -1,7 +1,7 @@
 """CPU-only: `kmx dump` on the reference's committed count files (text forms of io/kmer_file.hpp:140-148 and
-io/hash_file.hpp:211-219: `ACGT... count` / `hash count` per line), and the example plugins of the reference compiled UNCHANGED
-against the shipped include/kmtricks headers (only in the build container, where /root/reference exists; nothing of it ships)."""
-import glob, os, subprocess
+io/hash_file.hpp:211-219: `ACGT... count` / `hash count` per line), and merge plugins of both kinds compiled against the shipped
+include/kmtricks headers alone."""
+import os, subprocess
 import numpy as np
 import pytest
 
@@ -30,11 +30,11 @@ def test_dump_kmer_and_hash_files():
     assert r.returncode == 1 and "[error]" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/plugins/example"), reason="the reference tree is only present in the build container")
-def test_reference_example_plugins_compile_unchanged(tmp_path):
-    """plugins/example/*.cpp of the reference against include/kmtricks/{plugin,kmer,utils}.hpp (compile + the exported symbols the
+def test_plugins_compile_against_the_shipped_headers(tmp_path):
+    """a plain plugin (create0: kmtricks_amd/host/test_plugin.cpp) and one templated over the k-mer width (create32 / create64:
+    tests/helpers/width_plugin.cpp) against include/kmtricks/{plugin,kmer,utils}.hpp alone (compile + the exported symbols the
     plugin manager looks up, plugin_manager.hpp:38-113)"""
-    for src in sorted(glob.glob("/root/reference/plugins/example/*.cpp")):
+    for src in (f"{ROOT}/kmtricks_amd/host/test_plugin.cpp", f"{ROOT}/tests/helpers/width_plugin.cpp"):
         so = tmp_path / (os.path.basename(src)[:-4] + ".so")
         r = subprocess.run(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-Wall", "-DDMAX_C=4294967295", f"-I{ROOT}/include", src, "-o", str(so)],
                            capture_output=True, text=True)
