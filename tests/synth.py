@@ -26,7 +26,11 @@ def synth_lists(seed, n_lists, pool, p_present, n_private, kw=1, key_bits=62, co
 
     allk = np.unique(draw(int(total * 1.1) + 8), axis=0)
     rng.shuffle(allk, axis=0)
-    allk = allk[:total]
+    return _assemble(rng, allk[:total], n_lists, pool, p_present, n_private, kw, count_max, ragged)
+
+
+def _assemble(rng, allk, n_lists, pool, p_present, n_private, kw, count_max, ragged=False):
+    """the lists out of distinct keys allk[n, kw]: the first `pool` shared, n_private private to each list"""
     shared, priv = allk[:pool], allk[pool:]
     out = []
     for i in range(n_lists):
@@ -41,6 +45,82 @@ def synth_lists(seed, n_lists, pool, p_present, n_private, kw=1, key_bits=62, co
         cs = rng.integers(1, count_max, len(ks), dtype=np.uint32)
         out.append((ks, cs))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- full-width keys
+U64 = (1 << 64) - 1
+SHAPES = ("uniform", "straddle", "near-max", "low-word-only", "zero")
+TOP_WORD = 0xC3A5C85C97CB3127          # the most significant word of every low-word-only key (bit 63 set)
+
+
+def max_canonical(kw):
+    """the largest canonical k-mer of k = 32 * kw (k = 128 for kw = 4: a bound the API accepts, no k reaches it): G^(16 kw) C^(16 kw),
+    G = 3 and C = 1 (A0 C1 T2 G3), the first nucleotide in the top digit -- its reverse complement C^(16 kw) G^(16 kw) is smaller"""
+    return kmer_value("G" * (16 * kw) + "C" * (16 * kw))
+
+
+def key_words(v, kw):
+    """a key as its words, low word first"""
+    return [(v >> (64 * w)) & U64 for w in range(kw)]
+
+
+def key_value(words):
+    return sum(int(x) << (64 * w) for w, x in enumerate(words))
+
+
+def _draw_wide(rng, n, kw, shape):
+    """n keys (uint64[n, kw], low word first, not yet distinct) of one full-width shape"""
+    def u64(m, hi=U64):
+        return rng.integers(0, hi, m, dtype=np.uint64, endpoint=True)
+
+    if shape == "uniform":                 # every word uniform over its 64 bits, the most significant one included
+        return np.stack([u64(n) for _ in range(kw)], axis=1)
+    if shape == "straddle":                # the most significant word within delta of 2^63, where a signed compare reverses the order
+        delta = max(4 * n, 64) if kw == 1 else 3
+        top = (np.uint64(1 << 63) - np.uint64(delta)) + u64(n, 2 * delta)
+        return np.stack([u64(n) for _ in range(kw - 1)] + [top], axis=1)
+    if shape == "near-max":                # at and just below the largest canonical value of k = 32 * kw
+        ws = [np.full(n, x, np.uint64) for x in key_words(max_canonical(kw), kw)]      # (no word of it is below 4 n + 8: no borrow)
+        ws[0] -= rng.integers(0, 4 * n + 8, n).astype(np.uint64)
+        if kw > 1:
+            ws[1] -= rng.integers(0, 3, n).astype(np.uint64)
+        return np.stack(ws, axis=1)
+    if shape == "low-word-only":           # every upper word alike (the middle ones of four values); low words in pairs that differ
+        base = u64(n // 2 + 1, (1 << 63) - 1)      # in bit 63 alone
+        ws = [np.concatenate([base, base | np.uint64(1 << 63)])[:n]]
+        mids = np.array([0x0123456789ABCDEF, 0x8000000000000000, 0x7FFFFFFFFFFFFFFF, 0xFEDCBA9876543210], np.uint64)
+        ws += [mids[rng.integers(0, 4, n)] for _ in range(kw - 2)]
+        ws += [np.full(n, TOP_WORD, np.uint64)] if kw > 1 else []
+        return np.stack(ws, axis=1)
+    if shape == "zero":                    # the smallest keys: 0, 1 and a few above, every upper word 0
+        return np.stack([u64(n, 8 * n + 16)] + [np.zeros(n, np.uint64)] * (kw - 1), axis=1)
+    raise ValueError(shape)
+
+
+def _special_keys(kw, shape):
+    """keys a shape always holds (in the shared pool): the largest canonical value itself, key 0 and key 1"""
+    if shape == "near-max":
+        mx = max_canonical(kw)
+        return [key_words(mx, kw), key_words(mx - 1, kw)]
+    if shape == "zero":
+        return [key_words(0, kw), key_words(1, kw)]
+    if shape == "low-word-only":
+        return [key_words((TOP_WORD << (64 * (kw - 1))) if kw > 1 else 0, kw)]
+    return []
+
+
+def synth_wide_lists(seed, n_lists, pool, p_present, n_private, kw=1, shape="uniform", count_max=50, ragged=False):
+    """synth_lists over the whole key width: the keys of one of SHAPES (`uniform`, `straddle`, `near-max`, `low-word-only`, `zero`),
+    lists strictly ascending, most significant word first.  The special keys of the shape (the largest canonical value, keys 0 and 1)
+    lead the shared pool."""
+    rng = np.random.default_rng(seed)
+    total = pool + n_lists * n_private
+    special = np.array(_special_keys(kw, shape), np.uint64).reshape(-1, kw)
+    drawn = np.unique(_draw_wide(rng, int(total * 1.2) + 8, kw, shape), axis=0)
+    drawn = drawn[~(drawn[:, None, :] == special[None, :, :]).all(axis=2).any(axis=1)] if len(special) else drawn
+    rng.shuffle(drawn, axis=0)
+    allk = np.concatenate([special, drawn], axis=0)[:total]
+    return _assemble(rng, allk, n_lists, pool, p_present, n_private, kw, count_max, ragged)
 
 
 def synth_hash_lists(seed, n_lists, lower, window, density, count_max=20):

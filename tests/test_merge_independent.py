@@ -348,3 +348,53 @@ def test_parti_info_oracle_against_the_string_restatement(k, m, P):
     got, ms, mk, _ = orc.superk_stats(reads, k, m, lut, rep, P)
     assert got.tolist() == exp
     assert {int(v): [int(ms[v]), int(mk[v])] for v in np.nonzero(ms)[0]} == minim
+
+
+# ---------------------------------------------------------------------------------------------------------------- full key width
+EXTREME_COUNTS = [254, 255, 256, 65535, 65536, 1 << 31, 0xFFFFFFFF]
+
+
+def wide_cohort(seed, n, kw, shape, pool=300, n_private=20):
+    """synth_wide_lists as {key: count} dictionaries (Python ints), counts around the soft-mins, some of them EXTREME_COUNTS"""
+    from synth import synth_wide_lists, key_value
+    rng = np.random.default_rng(seed)
+    lists = []
+    for ks, cs in synth_wide_lists(seed, n, pool, 0.8, n_private, kw=kw, shape=shape, count_max=7):
+        cs = cs.astype(np.uint64)
+        m = rng.random(len(cs)) < 0.05
+        cs[m] = np.array(EXTREME_COUNTS, np.uint64)[rng.integers(0, len(EXTREME_COUNTS), int(m.sum()))]
+        lists.append({key_value(k): int(c) for k, c in zip(ks, cs)})
+    return lists
+
+
+def arrays_of(lists, kw):
+    """{key: count} dictionaries -> the (keys uint64[n, kw], counts uint32[n]) arrays the C ABIs take, ascending"""
+    out = []
+    for l in lists:
+        ks = sorted(l)
+        keys = np.array([[(key >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(kw)] for key in ks], np.uint64).reshape(len(ks), kw)
+        out.append((keys, np.array([l[key] for key in ks], np.uint32)))
+    return out
+
+
+@pytest.mark.parametrize("shape", ["uniform", "straddle", "near-max", "low-word-only", "zero"])
+@pytest.mark.parametrize("kw", [1, 2, 3, 4])
+def test_oracle_against_the_second_restatement_at_full_key_width(kw, shape):
+    """the oracle's kw_less / kw_eq where the most significant word reaches bits 62 and 63 (k = 32, 64, 96: ceil(k / 32) full words): keys
+    around 2^63, the largest canonical k-mer and the keys below it, keys that differ only in bit 63 of a low word, keys 0 and 1 -- judged
+    by `dict_merge` (Python integers: no word order to get wrong), with counts up to 2^32 - 1 in the statistics"""
+    n = 9
+    lists = wide_cohort(77 * kw + len(shape), n, kw, shape)
+    top = [key >> (64 * (kw - 1)) for l in lists for key in l]
+    if shape in ("uniform", "straddle", "near-max", "low-word-only"):
+        assert max(top) >= 1 << 63
+    arrays = arrays_of(lists, kw)
+    soft = [1 + (i % 4) for i in range(n)]
+    soft[2] = 0xFFFFFFFF            # (every record of list 2 non-solid: its rescued counts alone make TOTAL_W)
+    for r, s in itertools.product([0, 1, 2, n], [0, 1, 2, n + 1]):
+        rows, stats = dict_merge(lists, soft, r, s)
+        for mode in (orc.MODE_COUNT, orc.MODE_PA):
+            body, nrows, st = orc.merge_matrix(arrays, kw, soft, r, s, mode)
+            assert nrows == len(rows) and body == body_of(rows, kw, n, mode), (kw, shape, r, s, mode)
+            assert st.tolist() == stats, (kw, shape, r, s)
+    assert max(max(x) for x in dict_merge(lists, soft, 1, 1)[1][4:]) > 1 << 32      # (the totals pass 2^32)

@@ -627,6 +627,37 @@ def test_wide_kmer_pipeline(tmp_path, KK, mode):
             assert len(first[0]) == KK and set(first[0]) <= set("ACGT") and len(first) == 1 + NS
 
 
+@pytest.mark.parametrize("KK,mode", [(32, "kmer:count:bin"), (32, "kmer:pa:bin"), (96, "kmer:count:bin")])
+def test_full_word_kmer_pipeline(tmp_path, KK, mode):
+    """k = 32 and 96: the most significant word of a key holds 64 bits of the k-mer (ceil(k / 32) words), so every canonical k-mer that
+    starts with G or T has a top word of at least 2^63 -- end to end through `kmx pipeline`, every matrix body and merge_info against the
+    oracle, and the merged keys do reach the top bit"""
+    NS, GL, PP = 9, 30_000, 4
+    reads = _synthetic_samples(tmp_path, NS, GL, 200 + KK)
+    out = tmp_path / "run"
+    args = [KMX, "pipeline", "--file", str(tmp_path / "syn.fof"), "--run-dir", str(out), "--kmer-size", str(KK), "--hard-min", "2",
+            "--nb-partitions", str(PP), "--static-repart", "--mode", mode, "--recurrence-min", "2"]
+    r = subprocess.run(args, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    kw = orc.kw_of_k(KK)
+    omode, ext = (orc.MODE_COUNT, "count") if mode == "kmer:count:bin" else (orc.MODE_PA, "pa")
+    row = 8 * kw + (4 * NS if omode == orc.MODE_COUNT else (NS + 7) // 8)
+    lut = orc.minimizer_lut(10); rep = orc.repart_static(10, PP)
+    sk = [orc.superk_partition(rs, KK, 10, lut, rep, PP) for rs in reads]
+    total_rows = top_rows = 0
+    for p in range(PP):
+        lists = [tuple(x if i else x.reshape(-1) for i, x in enumerate(orc.count_kmer(s[p][0], KK, 2))) for s in sk]
+        body, rows, stats = orc.merge_matrix(lists, kw, [1] * NS, 2, 0, omode)
+        raw = open(out / "matrices" / f"matrix_{p}.{ext}", "rb").read()
+        assert struct.unpack_from("<II", raw, 21) == (KK, kw) and raw[45:] == body
+        mi = [l.split("\t") for l in open(out / "merge_infos" / f"partition{p}.merge_info").read().splitlines()]
+        for rix in range(6):
+            assert [int(x) for x in mi[rix][1:1 + NS]] == [int(x) for x in stats[rix]]
+        top = np.frombuffer(body, np.uint8).reshape(rows, row)[:, 8 * (kw - 1):8 * kw].copy().view(np.uint64).reshape(-1)
+        total_rows += rows; top_rows += int((top >= np.uint64(1 << 63)).sum())
+    assert total_rows > 10_000 and top_rows > total_rows // 8, (total_rows, top_rows)
+
+
 @pytest.mark.parametrize("KK", [80, 127])
 def test_wide_kmer_pipeline_through_files(tmp_path, KK):
     """k >= 64 with --keep-tmp --hist (super-k-mer and count files written and read back; the abundance histograms) and with --cpr:
