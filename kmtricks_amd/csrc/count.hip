@@ -1022,7 +1022,7 @@ static int decode_and_count(kmx_ctx* ctx, StageClock& clk, const u8* d_recs, con
   if (rc == 1) {
     if (!co.dev()) for (u32 p = 0; p < n_parts; p++) { free(co.keys[p]); free(co.counts[p]); co.keys[p] = nullptr; co.counts[p] = nullptr; co.n_out[p] = 0; }
     unsigned key_bits = 2 * k;
-    if (hash_mode) { u64 top = pid.empty() ? (u64)n_parts - 1 : 0; for (u32 p = 0; p < n_parts && !pid.empty(); p++) top = std::max(top, pid[p]); key_bits = 64; const unsigned __int128 span = (unsigned __int128)window * (top + 1);
+    if (hash_mode) { u64 top = pid.empty() ? (u64)n_parts - 1 : 0; for (u32 p = 0; p < n_parts && !pid.empty(); p++) top = std::max(top, pid[p]); key_bits = 64; const unsigned __int128 span = (unsigned __int128)window * ((unsigned __int128)top + 1);      // (top + 1 in 128 bits: a partition id of 2^64 - 1)
       if (span < ((unsigned __int128)1 << 63)) { key_bits = 1; while ((((u64)1) << key_bits) < (u64)span) key_bits++; } }
     // the partition of every k-mer: the library sort's second key
     u16* d_kpart = (u16*)ctx->dalloc(total * 2); u32* d_kmo = (u32*)ctx->dalloc(((size_t)n_parts + 1) * 4);

@@ -565,7 +565,7 @@ void k_cs_count_hash(const u64* __restrict__ bkeys, const u32* __restrict__ boff
   __shared__ u32 lb[CAP];          // hash set counts [0, CS_HT)                                                 |  the sort path's run starts
   __shared__ u32 wsum[CS_TPB / 64];
   __shared__ u32 hh[258];
-  __shared__ u32 ndist;
+  __shared__ u32 ndist, ntop;
   __shared__ volatile u32 full;
   static_assert(2 * CS_HT <= CAP, "the dense copy lies behind the hash set");
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -577,17 +577,21 @@ void k_cs_count_hash(const u64* __restrict__ bkeys, const u32* __restrict__ boff
   const u32 o = boff[b], n = boff[b + 1] - o;
   if (lo && n <= lo) continue;
   if (n == 0) { if (tid == 0) nkept[b] = 0; continue; }
-  const u64 EMPTY = ~0ULL;           // (no canonical k-mer and no window hash is all ones)
+  // the set's "empty": no canonical k-mer is all ones, but a window hash can be (XXH64 % window + window * partition wraps mod 2^64).
+  // That key is counted beside the set, as k_cs_wave_count does, and written behind the others (it is the largest)
+  const u64 EMPTY = ~0ULL;
   for (u32 i = tid; i < (u32)CS_HT; i += CS_TPB) { la[i] = EMPTY; lb[i] = 0; }
-  if (tid == 0) { ndist = 0; full = 0; }
+  if (tid == 0) { ndist = 0; ntop = 0; full = 0; }
   if (hist) for (u32 i = tid; i < 258; i += CS_TPB) hh[i] = 0;
   __syncthreads();
+  u32 my_top = 0;
   for (u32 i0 = 0; i0 < n; i0 += CS_TPB) {
     const u32 i = i0 + tid;
     if (i < n) {
       const u64 k = bkeys[o + i];
       u32 h = cs_hash(k);
-      for (u32 probe = 0; probe < (u32)CS_HT; probe++) {
+      if (k == EMPTY) my_top++;
+      else for (u32 probe = 0; probe < (u32)CS_HT; probe++) {
         u64 cur = ((volatile u64*)la)[h];
         if (cur == EMPTY) {
           cur = (u64)atomicCAS((unsigned long long*)&la[h], (unsigned long long)EMPTY, (unsigned long long)k);
@@ -600,6 +604,7 @@ void k_cs_count_hash(const u64* __restrict__ bkeys, const u32* __restrict__ boff
     }
     if (full) break;                 // (uniform enough: every thread leaves at its next look)
   }
+  if (my_top) atomicAdd(&ntop, my_top);
   __syncthreads();
   if (full) {                        // too many distinct keys for the hash set
     if (n > (u32)CAP) { if (tid == 0) { nkept[b] = 0; atomicOr(overflow, 1u); } continue; }
@@ -655,7 +660,13 @@ void k_cs_count_hash(const u64* __restrict__ bkeys, const u32* __restrict__ boff
       if (len >= hard_min) { tk[o + w0] = k; tc[o + w0] = len; w0++; }
     }
   }
-  if (tid == 0) nkept[b] = tot;
+  const u32 top = ntop;
+  if (tid == 0) {
+    if (top && top >= hard_min) { tk[o + tot] = EMPTY; tc[o + tot] = top; }
+    nkept[b] = tot + (top && top >= hard_min ? 1u : 0u);
+    if (hist && top) { if (top <= 255u) atomicAdd(&hh[top], 1u); else { atomicAdd(&hh[256], 1u); atomicAdd(&hh[257], top); } }
+  }
+  if (hist) __syncthreads();      // (thread 0's entry above before the histogram leaves)
   if (hist) {
     for (u32 i = tid; i < 258; i += CS_TPB) if (hh[i]) atomicAdd(&hist[i], (unsigned long long)hh[i]);
   }

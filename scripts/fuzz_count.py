@@ -14,10 +14,15 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--cases", type=int, default=60); ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--scale", type=int, default=1, help="times as many reads per case (partitions of many buckets)")
 ap.add_argument("--kmers", choices=["narrow", "wide", "all"], default="narrow", help="k <= 63, k = 64 ... 127 (keys of two to four words), or both")
+ap.add_argument("--wide", action="store_true", help="about half the cases take a window of tests/synth.py's shapes (hash keys up to 2^64 - 1)")
 a = ap.parse_args()
+if a.wide:      # (imported only here: plain runs draw and need what they did before)
+    from synth import WINDOW_SHAPES, hash_window
+    wide_rng = np.random.default_rng(a.seed + 7919)
+    FUSED = [s for s in WINDOW_SHAPES if s not in ("sparse-ids", "all-ones-top")]      # (the fused calls' window id is the partition)
 rng = np.random.default_rng(a.seed)
 ctx = lib.Context(0)
-done = 0
+done = wide_cases = 0
 for case in range(a.cases):
     ks = ([12, 15, 20, 21, 27, 31, 32, 33, 40, 47, 55, 63] if a.kmers != "wide" else []) + ([64, 65, 80, 95, 96, 97, 111, 127] if a.kmers != "narrow" else [])
     k = int(rng.choice(ks))
@@ -43,6 +48,16 @@ for case in range(a.cases):
     lut = orc.minimizer_lut(m)
     rep = orc.repart_static(m, P)
     exp = orc.superk_partition(reads, k, m, lut, rep, P)
+    shape = None
+    if a.wide and hashed and wide_rng.random() < 0.5:
+        # (all-ones-one: the first k-mer of partition 1 -- or of any partition -- gets the all-ones key when its hash is below 2^63)
+        first = next((orc.superk_decode(e[0], k)[0] for e in (exp[1:2] if P > 1 else []) + exp if e[1]), None)
+        x = orc.xxh64(np.ascontiguousarray(first, np.uint64).tobytes()) if first is not None else 0
+        shape = str(wide_rng.choice(FUSED))
+        if shape == "all-ones-one" and x >= 1 << 63:
+            shape = "above-2^64"
+        W = hash_window(shape, max(P, 2), x, at=1)[0]
+        wide_cases += 1
     got_s, nk_s, streams, info = ctx.count_reads(reads, k, m, rep, P, hard_min, window=W if hashed else 0, streams=True)
     got_d, nk_d, none, _ = ctx.count_reads(reads, k, m, rep, P, hard_min, window=W if hashed else 0)
     store = lib.Store(0)
@@ -55,7 +70,7 @@ for case in range(a.cases):
         rk, rc = ctx.read_list(lists[p][0], lists[p][1], kw)
         ok = ok and np.array_equal(rk.reshape(ek.shape), ek) and np.array_equal(rc, ec)
         if not ok:
-            print(json.dumps({"failed_case": case, "seed": a.seed, "k": k, "m": m, "P": P, "hard_min": hard_min, "hashed": hashed, "style": style, "reads": len(reads), "partition": p}))
+            print(json.dumps({"failed_case": case, "seed": a.seed, "k": k, "m": m, "P": P, "hard_min": hard_min, "hashed": hashed, "window": W, "shape": shape, "style": style, "reads": len(reads), "partition": p}))
             sys.exit(1)
     epin, ems, emk, _ = orc.superk_stats(reads, k, m, lut, rep, P)
     pr, ms, mk, nsk = raw
@@ -65,4 +80,4 @@ for case in range(a.cases):
         sys.exit(1)
     store.close()
     done += 1
-print(json.dumps({"cases": done, "seed": a.seed, "all_equal_to_oracle": True}))
+print(json.dumps({"cases": done, "seed": a.seed, "all_equal_to_oracle": True, **({"wide_cases": wide_cases} if a.wide else {})}))

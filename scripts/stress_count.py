@@ -9,6 +9,10 @@ import orc
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+wide = "wide" in sys.argv[3:]      # about half the cases take a window of tests/synth.py's shapes and its partition ids
+if wide:      # (imported only here: plain runs draw and need what they did before)
+    from synth import WINDOW_SHAPES, hash_window
+    wide_rng = random.Random((int(sys.argv[2]) if len(sys.argv) > 2 else 1) + 7919)
 ctx = lib.Context(0)
 for case in range(n_cases):
     k = rng.choice([12, 20, 21, 25, 31, 32, 33, 47, 63]); m = rng.choice([x for x in (5, 7, 8, 10, 11, 12) if x < k - 1])
@@ -32,13 +36,24 @@ for case in range(n_cases):
             print("MISMATCH superk partition", p); sys.exit(1)
     streams = [exp[p][0] for p in range(P)]
     hm = rng.choice([1, 2, 3]); W = rng.choice([64, 6400, 1000003])
-    gb = ctx.count_batch(streams, k, hm); gh = ctx.count_batch(streams, k, hm, window=W, partitions=list(range(P)))
+    ids = list(range(P))
+    if wide and wide_rng.random() < 0.5:
+        # (the all-ones shapes: the first k-mer of the first non-empty stream, in its partition)
+        at = next((p for p in range(P) if streams[p]), 0)
+        x = orc.xxh64(orc.superk_decode(streams[at], k)[0].tobytes()) if streams[at] else 0
+        shape = wide_rng.choice(WINDOW_SHAPES)
+        if shape == "all-ones-one" and x >= 1 << 63:
+            shape = "all-ones-top"
+        W, ids = hash_window(shape, max(P, 2), x, at=at)
+        ids = ids[:P]
+        print(f"  window={shape} W={W} ids={ids[:4]}", flush=True)
+    gb = ctx.count_batch(streams, k, hm); gh = ctx.count_batch(streams, k, hm, window=W, partitions=ids)
     for p in range(P):
-        ek, ec = orc.count_kmer(streams[p], k, hm); eh, ehc = orc.count_hash(streams[p], k, W, p, hm)
+        ek, ec = orc.count_kmer(streams[p], k, hm); eh, ehc = orc.count_hash(streams[p], k, W, ids[p], hm)
         if not (np.array_equal(ek, gb[p][0]) and np.array_equal(ec, gb[p][1]) and np.array_equal(eh, gh[p][0]) and np.array_equal(ehc, gh[p][1])):
             print("MISMATCH count partition", p); sys.exit(1)
         if p == 0:
-            a, b = ctx.count_kmer(streams[p], k, hm); c, d = ctx.count_hash(streams[p], k, W, p, hm)
+            a, b = ctx.count_kmer(streams[p], k, hm); c, d = ctx.count_hash(streams[p], k, W, ids[p], hm)
             if not (np.array_equal(ek, a) and np.array_equal(ec, b) and np.array_equal(eh, c) and np.array_equal(ehc, d)):
                 print("MISMATCH single-stream count"); sys.exit(1)
 print("all", n_cases, "cases equal the oracle")

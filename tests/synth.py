@@ -178,3 +178,60 @@ def synth_superk_stream(seed, k, n_records, max_kmers, genome=4000):
             v = canonical_value(seq[j:j + k])
             counts[v] = counts.get(v, 0) + 1
     return b"".join(out), counts
+
+
+# ---------------------------------------------------------------------------------------------------------------- hash windows
+# A window hash is XXH64(canonical k-mer words) % window + window * partition, mod 2^64 (kmx.h; hash.hpp's HashWindow): both the
+# window and the partition id are u64, so keys reach every value of 64 bits, the all-ones key included.
+WINDOW_SHAPES = ("small", "2^32-1", "2^32", "2^32+64", "2^40", "below-2^63", "above-2^63", "below-2^64", "above-2^64", "sparse-ids",
+                 "all-ones-top", "all-ones-one")
+SPARSE_IDS = (0, 65535, 1 << 32, U64)
+
+
+def value_xxh64(v, k):
+    """XXH64 (seed 0) over the 8 * ceil(k / 32) little-endian bytes of a canonical k-mer value's words"""
+    import orc      # (the oracle's XXH64, pinned to the specification's vectors; imported here: plain draws need no oracle)
+    return orc.xxh64(b"".join(w.to_bytes(8, "little") for w in key_words(v, (k + 31) // 32)))
+
+
+def hash_key(s, window, partition):
+    """the window hash of k-mer string `s`, restated with Python integers"""
+    return (value_xxh64(canonical_value(s), len(s)) % window + window * partition) & U64
+
+
+def hash_counts(counts, k, window, partition, hard_min=1, xxh=None):
+    """{canonical value: count} (synth_superk_stream) -> sorted [(window hash, count)] with count >= hard_min; k-mers whose hashes
+    meet are one key.  xxh: {value: value_xxh64(value, k)} computed once by the caller"""
+    out = {}
+    for v, c in counts.items():
+        h = ((xxh[v] if xxh is not None else value_xxh64(v, k)) % window + window * partition) & U64
+        out[h] = out.get(h, 0) + c
+    return sorted((h, c) for h, c in out.items() if c >= hard_min)
+
+
+def hash_window(shape, P, x=None, at=0):
+    """-> (window, partition ids[P]) of one of WINDOW_SHAPES.  `all-ones-*` build the all-ones key for a k-mer whose XXH64 is x, kept
+    in partition `at`: window x + 1 at partition id 2^64 - 1 (x < 2^64 - 1), or window 2^64 - 1 - x at partition id 1 (x < 2^63)"""
+    assert P >= 2
+    ids = list(range(P))
+    if shape == "small":
+        return 100003, [(3 * p + 7) % 11 for p in range(P)]
+    if shape in ("2^32-1", "2^32", "2^32+64", "2^40"):
+        return {"2^32-1": (1 << 32) - 1, "2^32": 1 << 32, "2^32+64": (1 << 32) + 64, "2^40": 1 << 40}[shape], ids
+    if shape == "below-2^63":              # window * P just below 2^63 / 2^64, and just above (the keys of the last partitions wrap)
+        return ((1 << 63) - 1) // P, ids
+    if shape == "above-2^63":
+        return (1 << 63) // P + 1, ids
+    if shape == "below-2^64":
+        return U64 // P, ids
+    if shape == "above-2^64":
+        return (1 << 64) // P + 1, ids
+    if shape == "sparse-ids":
+        return (1 << 20) + 7, [SPARSE_IDS[p % 4] for p in range(P)]
+    if shape == "all-ones-top":
+        assert x is not None and x < U64
+        return x + 1, [U64 if p == at else p for p in range(P)]
+    if shape == "all-ones-one":           # (partition `at` takes id 1, partition 1 id `at`)
+        assert x is not None and x < 1 << 63
+        return U64 - x, [1 if p == at else at if p == 1 else p for p in range(P)]
+    raise ValueError(shape)

@@ -255,3 +255,29 @@ def test_count_oracle_against_an_independent_restatement(k):
         vals = [sum(int(keys[i, w]) << (64 * w) for w in range(kw)) for i in range(len(c))]
         exp = sorted((v, n) for v, n in cnt.items() if n >= hm)
         assert vals == [v for v, _ in exp] and list(map(int, c)) == [n for _, n in exp]
+
+
+@pytest.mark.parametrize("k", [21, 31, 32, 47, 63, 64, 96, 127])
+def test_hash_count_oracle_against_an_independent_restatement(k):
+    """hash mode of the same check: the oracle's window hashes against XXH64 of the strings' canonical words % window + window * partition,
+    mod 2^64 (tests/synth.py), for every window shape of tests/synth.py -- windows of 2^32 and beyond, window * P on both sides of 2^63 and
+    2^64, partition ids up to 2^64 - 1, and the two windows that give one k-mer of the stream the all-ones key"""
+    from synth import synth_superk_stream, hash_counts, hash_window, value_xxh64, WINDOW_SHAPES, U64
+    mx = 28 if k < 32 else 60 if k < 64 else 92 if k < 96 else 124
+    recs, cnt = synth_superk_stream(k + 1000, k, 300, mx)
+    xxh = {v: value_xxh64(v, k) for v in cnt}
+    # the chosen k-mer of the all-ones shapes: the most frequent one whose hash is below 2^63 (both constructions apply to it)
+    v0 = max((v for v in cnt if xxh[v] < 1 << 63), key=lambda v: (cnt[v], v))
+    P = 4
+    for shape in WINDOW_SHAPES:
+        W, ids = hash_window(shape, P, xxh[v0], at=2)
+        for p in range(P):
+            exp_all = hash_counts(cnt, k, W, ids[p], 1, xxh)
+            for hm in (1, 2):
+                keys, c = orc.count_hash(recs, k, W, ids[p], hm)
+                exp = [e for e in exp_all if e[1] >= hm]
+                assert [int(x) for x in keys] == [h for h, _ in exp] and [int(x) for x in c] == [n for _, n in exp], (shape, p, hm)
+            if shape.startswith("all-ones") and p == 2:
+                assert exp_all[-1] == (U64, cnt[v0]) and int(keys[-1]) == U64 and int(c[-1]) == cnt[v0]
+            if shape in ("2^40", "above-2^64", "sparse-ids") and ids[p] >= 2:
+                assert max(h for h, _ in exp_all) >= 1 << 33      # (keys far above 2^32 P)

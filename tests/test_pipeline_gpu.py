@@ -171,6 +171,24 @@ def test_hash_pipeline(inputs, tmp_path, mode, omode, ext, hdrlen):
             assert np.allclose(fpr, exp, atol=1e-6)
 
 
+@pytest.mark.parametrize("mode,omode,ext,hdrlen", [("hash:count:bin", orc.MODE_COUNT, "count_hash", 37), ("hash:pa:bin", orc.MODE_PA, "pa_hash", 37)])
+def test_hash_pipeline_with_a_window_of_2_to_the_38(inputs, tmp_path, mode, omode, ext, hdrlen):
+    """--bloom-size 2^40: window 2^38 at four partitions, so partition p's keys lie in [2^38 p, 2^38 (p + 1)), far above 2^32.  The count and
+    PA matrices hold only the hashes that occur: nothing of the run may grow with the window"""
+    out = run(inputs, tmp_path / "run", "--mode", mode, "--bloom-size", str(1 << 40))
+    hi = struct.unpack("<QQQQI", open(out / "hash.info", "rb").read())
+    assert hi[:3] == (1 << 40, 4, 1 << 38)
+    W = hi[2]
+    lists = oracle_lists(True, W)
+    for p in range(P):
+        raw = open(out / "matrices" / f"matrix_{p}.{ext}", "rb").read()
+        body, rows, _ = orc.merge_matrix([(h, c) for h, c in lists[p]], 1, [1, 1], 1, 0, omode)
+        assert rows > 0 and raw[hdrlen:] == body
+        keys = np.frombuffer(body, np.uint8).reshape(rows, -1)[:, :8].copy().view(np.uint64).ravel()
+        assert keys.min() >= W * p and keys.max() < W * (p + 1) and (p == 0 or keys.min() > 1 << 32)
+    assert sum(os.path.getsize(f) for f in (out / "matrices").iterdir()) < 1 << 24
+
+
 def test_plugin_pipeline(inputs, tmp_path):
     plug = os.path.join(ROOT, "kmtricks_amd", "libkmx_test_plugin.so")
     out = run(inputs, tmp_path / "run", "--mode", "kmer:count:bin", "--plugin", plug, "--plugin-config", "0")

@@ -61,3 +61,29 @@ def test_full_width_shapes(kw, shape):
         assert sum(1 for x in s if x >> 63 and (x ^ (1 << 63)) in s) > 10      # low words that differ in bit 63 alone
     else:
         assert min(vals) == 0 and 1 in vals and max(top) == (max(vals) if kw == 1 else 0)
+
+
+@pytest.mark.parametrize("args,digest", [((21, 21, 300, 28), "30ed913cd81c4971"), ((127, 127, 300, 124), "5c0d5aa55f083807")])
+def test_existing_superk_streams_are_unchanged(args, digest):
+    """the record streams the count restatements draw (synth_superk_stream) are pinned as well"""
+    from synth import synth_superk_stream
+    recs, cnt = synth_superk_stream(*args)
+    h = hashlib.sha256(recs); h.update(repr(sorted(cnt.items())).encode())
+    assert h.hexdigest()[:16] == digest
+
+
+def test_window_shapes():
+    """the hash windows are what their names promise: window * P on the named side of 2^63 / 2^64, the sparse ids, and the all-ones key
+    for the chosen hash in the chosen partition (both constructions)"""
+    from synth import WINDOW_SHAPES, hash_window, U64
+    x = 0x1234_5678_9ABC_DEF0
+    for P in (2, 3, 4, 8, 37):
+        got = {s: hash_window(s, P, x, at=P - 1) for s in WINDOW_SHAPES}
+        assert all(len(ids) == P and all(0 <= i <= U64 for i in ids) and 0 < W <= U64 for W, ids in got.values())
+        assert got["2^32-1"][0] == (1 << 32) - 1 and got["2^32"][0] == 1 << 32 and got["2^32+64"][0] == (1 << 32) + 64 and got["2^40"][0] == 1 << 40
+        assert got["below-2^63"][0] * P < 1 << 63 < got["above-2^63"][0] * P and got["above-2^63"][0] * P - (1 << 63) <= P
+        assert got["below-2^64"][0] * P < 1 << 64 < got["above-2^64"][0] * P and got["above-2^64"][0] * P - (1 << 64) <= P
+        assert {0, 65535, 1 << 32, U64} <= set(got["sparse-ids"][1]) or P < 4
+        for s in ("all-ones-top", "all-ones-one"):
+            W, ids = got[s]
+            assert (x % W + W * ids[P - 1]) & U64 == U64
