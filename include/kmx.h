@@ -19,6 +19,9 @@
  *   kmx_transpose_bits          replaces km::BitMatrix::transpose / __sse_trans
  *                               (include/kmtricks/bitmatrix.hpp:209-214, 238-289); HashMerger::write_as_bft (merge.hpp:631-644)
  *                               as a whole is kmx_merge* with KMX_MODE_BFT (merge + transpose without leaving HBM)
+ *   kmx_filter_dev / _host      replace km::FilterTask::{exec,f_count_matrix,f_pa_matrix} on top of km::MatrixFilter
+ *                               (include/kmtricks/matrix.hpp:23-393), run by main_filter (include/kmtricks/cmd.hpp:609-724):
+ *                               one partition's matrix rows joined with the new sample's count list
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -207,6 +210,70 @@ void  kmx_free_pinned(void* p);
  * kmx_free.  stats may be NULL. */
 int kmx_merge(kmx_ctx* ctx, const kmx_merge_task* task, void** body, uint64_t* body_bytes,
               uint64_t* rows, uint64_t* stats);
+
+/* ----------------------------------------------------------------- filter */
+
+/* `kmtricks filter`: which rows of an existing k-mer matrix does a new sample share (km::FilterTask, matrix.hpp:23-393).
+ * rows: n_rows rows of one partition's .count / .pa matrix body in file order -- keys strictly ascending (most significant
+ * word first), each row key_words * 8 key bytes (low word first) + 4 * n_cols bytes of u32 counts (KMX_MODE_COUNT) or
+ * ceil(n_cols / 8) bytes (KMX_MODE_PA).  key: the new sample's count list of the same partition (a kmx_list: what
+ * kmx_count_reads_dev leaves in a kmx_store).  The outputs, by definition:
+ *   KMX_FILTER_M  the rows whose k-mer is in `key`, in file order; count rows get one more u32 column at their end, the k-mer's
+ *                 count in `key` (row bytes + 4); PA rows are unchanged (f_pa_matrix, matrix.hpp:202-335, writes the bits it read)
+ *   KMX_FILTER_V  one u32 per input row: the count in `key` (count rows) or 1 (PA rows) when the row's k-mer is in `key`, else 0
+ *   KMX_FILTER_K  the records of `key` whose k-mer is in no row, ascending
+ * A run of rows of a partition may be filtered on its own against the whole key list: `marks` (key.n bytes, zeroed by the caller
+ * before the first run) carries which records have met a row from call to call; every call adds its own, and a call that asks for
+ * KMX_FILTER_K gets the records without a mark as the marks stand after it -- ask in the last run.  M and V of the runs concatenate
+ * to M and V of the whole.  marks == NULL: the call holds the whole partition (libkmx keeps the marks itself).
+ * LIMITS: a row (with its new column) below 4 GiB; at most 2^32 - 256 rows a call and as many records in the key list; the key
+ * list 4-byte aligned; n_cols is otherwise free (no row is ever held in LDS).  Hash matrices and the Bloom modes: KMX_E_UNSUPPORTED. */
+#define KMX_FILTER_M 1u
+#define KMX_FILTER_V 2u
+#define KMX_FILTER_K 4u
+typedef struct {
+  uint32_t    key_words;      /* ceil(k / 32): 1 ... 4 */
+  uint32_t    mode;           /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t    n_cols;         /* N: samples of the matrix */
+  uint32_t    want;           /* KMX_FILTER_M | KMX_FILTER_V | KMX_FILTER_K, at least one */
+  const void* rows;
+  uint64_t    n_rows;
+  kmx_list    key;
+  uint8_t*    marks;          /* NULL, or key.n bytes: where `key` lies (device memory for kmx_filter_dev) */
+  uint32_t    key_on_device;  /* kmx_filter_host only: non-zero = key.recs (and marks) are DEVICE pointers already (a list of a kmx_store) */
+} kmx_filter_task;
+
+typedef struct kmx_filter_result kmx_filter_result;
+
+/* key.n zeroed mark bytes in device memory for a partition that is filtered in runs of rows (any n; kmx_filter_marks_free gives them back) */
+uint8_t* kmx_filter_marks_alloc(kmx_ctx* ctx, uint64_t n);
+void     kmx_filter_marks_free(kmx_ctx* ctx, uint8_t* marks);
+
+/* every pointer of the task a DEVICE pointer; the kernels are queued on the context's stream (kmx_stream) and the call returns;
+ * the result stays in HBM until it is freed */
+int kmx_filter_dev(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out);
+/* HOST pointers (see key_on_device): the rows (and the key) are uploaded on a stream of their own, so a run travels while the run
+ * before it is filtered; host marks are brought back too.  The host buffers may be reused once kmx_filter_result_wait has returned. */
+int kmx_filter_host(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out);
+int      kmx_filter_result_wait(kmx_filter_result* r);
+/* (the accessors below wait for the call themselves; what was not asked for is empty: 0 rows / entries / records) */
+uint64_t kmx_filter_result_rows(kmx_filter_result* r);             /* kept rows */
+uint64_t kmx_filter_result_row_bytes(const kmx_filter_result* r);  /* bytes of a row of M */
+uint64_t kmx_filter_result_body_bytes(kmx_filter_result* r);       /* rows * row_bytes when M was asked for */
+const void* kmx_filter_result_body_dev(kmx_filter_result* r);
+int      kmx_filter_result_copy_body(kmx_filter_result* r, void* host_dst, uint64_t dst_bytes);
+uint64_t kmx_filter_result_vector_len(const kmx_filter_result* r); /* n_rows when V was asked for */
+const void* kmx_filter_result_vector_dev(kmx_filter_result* r);
+int      kmx_filter_result_copy_vector(kmx_filter_result* r, uint32_t* host_dst, uint64_t dst_entries);
+uint64_t kmx_filter_result_absent(kmx_filter_result* r);           /* records of K */
+const void* kmx_filter_result_absent_dev(kmx_filter_result* r);
+int      kmx_filter_result_copy_absent(kmx_filter_result* r, void* host_dst, uint64_t dst_bytes);
+/* duration in ms of the call's kernels (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_filter_result_kernel_ms(kmx_filter_result* r);
+/* algorithmic bytes: the rows' keys and the key list read, the kept rows in and out (M), the vector (V), the absent records (K) --
+ * not the rows that are dropped: the match touches their key only */
+uint64_t kmx_filter_result_algo_bytes(kmx_filter_result* r);
+void     kmx_filter_result_free(kmx_filter_result* r);
 
 /* ------------------------------------------------------------------ count */
 

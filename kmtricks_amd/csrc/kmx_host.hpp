@@ -65,6 +65,15 @@ u32 bft_round_records(bool wide);
 u32 bft_fit_rows(u32 max_n, bool bits);
 hipError_t launch_merge_bft(const TaskDev* tasks, const uint2* items, u32 n_items, u32* ticket, u32 grid_x, u32 max_n, u32 rt_max, bool rec_bits, bool wide, u64* rem, u32 rem_cap, hipStream_t st);
 hipError_t launch_bit_transpose(const u8* in, u8* out, u64 nrows, u64 ncols, hipStream_t st);
+// filter.hip: the rows of a matrix joined with one sample's count list (kmx_filter_dev)
+u32 filter_tiles(u32 n);      // tiles of n rows / key records: the tile counters hold one entry more
+hipError_t launch_filter_match(int kw, const u8* rows, u32 n_rows, u64 irb, const u8* key, u32 n_key, int pa,
+                               u32* hit, u32* vec, u8* marks, u32* tile_cnt, hipStream_t st);
+hipError_t launch_filter_scan(u32* a, u32 n, hipStream_t st);      // exclusive prefix sums in place, the total in a[n]
+hipError_t launch_filter_move(const u8* rows, u32 n_rows, u64 irb, u64 orb, const u32* hit, const u32* vec, const u32* tile_base,
+                              u8* out, hipStream_t st);
+hipError_t launch_filter_absent_count(const u8* marks, u32 n_key, u32* tile_cnt, hipStream_t st);
+hipError_t launch_filter_absent_scatter(int kw, const u8* key, const u8* marks, u32 n_key, const u32* tile_base, u8* out, hipStream_t st);
 
 }  // namespace kmx
 

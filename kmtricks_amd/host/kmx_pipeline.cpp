@@ -44,11 +44,10 @@
 #include "kmx_pool.hpp"
 #include "kmx_repart.hpp"
 
+#include "kmx_run.hpp"
 namespace fs = std::filesystem;
 using namespace kmxio;
 using clk = std::chrono::steady_clock;
-
-struct Sample { std::string id; std::vector<std::string> files; uint32_t hard_min; };
 
 struct Opt {
   bool merge_only = false;      // `kmx merge --run-dir <dir>`: the merge module by itself over the count files of an existing run directory (src/cli.cpp:526-646)
@@ -62,40 +61,11 @@ struct Opt {
   bool static_repart = false, keep_tmp = false, cpr = false, skip_pinfo = false, hist = false, no_resident = false;
 };
 
-// (a worker thread cannot unwind the others: print and leave without running destructors under them)
-[[noreturn]] static void die(const std::string& msg) { std::cerr << "[error] " << msg << std::endl; std::cerr.flush(); _exit(EXIT_FAILURE); }
 static double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
-
-static std::vector<Sample> parse_fof(const std::string& path, uint32_t default_hard_min)
-{ // grammar `ID : path[ ; path...][ ! hardmin]` (io/fof.hpp:39-43, 126-134)
-  std::ifstream in(path); if (!in) die("Unable to read at " + path);
-  static const std::regex pat(R"((^[A-Za-z0-9_-]+)[\s]*:[\s]*([.A-Za-z0-9\/_\-; ]+)([\s]*![\s]*)?([0-9]+$)?)");
-  std::vector<Sample> out; std::map<std::string, int> seen; std::string line;
-  const fs::path base = fs::absolute(fs::path(path)).parent_path();
-  while (std::getline(in, line)) {
-    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
-    if (line.empty()) continue;
-    std::smatch m;
-    if (!std::regex_match(line, m, pat)) die("fof: invalid line: " + line);
-    Sample s; s.id = m[1]; s.hard_min = m[4].matched ? (uint32_t)std::stoul(m[4]) : default_hard_min;
-    if (seen[s.id]++) die("fof: duplicate id " + s.id);
-    std::stringstream ss(m[2]); std::string f;
-    while (std::getline(ss, f, ';')) {
-      f.erase(0, f.find_first_not_of(" \t")); f.erase(f.find_last_not_of(" \t") + 1);
-      if (f.empty()) continue;
-      fs::path p(f); if (p.is_relative() && !fs::exists(p)) p = base / p;   // fixtures use paths relative to the fof
-      s.files.push_back(p.string());
-    }
-    if (s.files.empty()) die("fof: no file for " + s.id);
-    out.push_back(s);
-  }
-  if (out.empty()) die("fof: empty");
-  return out;
-}
 
 static Opt parse_cli(int argc, char** argv)
 {
-  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
+  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx filter --in-matrix <dir> --key <fof> --output <dir> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
   Opt o;
   // `kmtricks merge` (src/cli.cpp:526-646): --run-dir, --partition-id, --soft-min, --recurrence-min, --share-min, --mode, --clear, --cpr,
   // -t; what the run was made with (k, partitions, Bloom size, minimizer size) is read back from its options.txt below
@@ -261,9 +231,7 @@ int run(int argc, char** argv)
 
   // ---- run directory (kmdir.hpp:195-241) ----
   const std::string root = fs::absolute(o.dir).string();
-  for (const char* d : {"", "/superkmers", "/counts", "/matrices", "/filters", "/histograms", "/merge_infos", "/howde_index",
-                        "/partition_infos", "/fpr", "/plugin_output", "/repartition_gatb", "/config_gatb"})
-    fs::create_directories(root + d);
+  make_run_layout(root);
   if (!o.merge_only) {
   fs::copy_file(o.fof, root + "/kmtricks.fof");
   { std::ofstream b(root + "/build_infos.txt"); b << "kmx (MI355X-native kmtricks pipeline), libkmx ABI " << kmx_version() << "\n"; }
@@ -1360,9 +1328,11 @@ int run(int argc, char** argv)
 }
 
 int kmx_tools_main(int argc, char** argv);      // kmx_tools.cpp: dump, aggregate
+int kmx_filter_main(int argc, char** argv);     // kmx_filter.cpp: filter
 
 int main(int argc, char** argv)
 {
+  if (argc >= 2 && std::string(argv[1]) == "filter") { try { return kmx_filter_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

@@ -25,6 +25,15 @@ class KmxMergeTask(C.Structure):
                 ("rows_hint", C.c_uint64), ("list_on_device", C.c_void_p)]
 
 
+class KmxFilterTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("want", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("key", KmxList), ("marks", C.c_void_p),
+                ("key_on_device", C.c_uint32)]
+
+
+FILTER_M, FILTER_V, FILTER_K = 1, 2, 4
+
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -128,6 +137,33 @@ EXPORTS = ["kmx_copy_to_host_async", "kmx_copy_wait", "kmx_reads_upload", "kmx_r
            "kmx_result_algo_bytes", "kmx_result_copy_body", "kmx_result_copy_stats", "kmx_result_free",
            "kmx_merge", "kmx_count_kmer", "kmx_count_hash", "kmx_count_batch", "kmx_transpose_bits", "kmx_superk_partition",
            "kmx_free"]
+
+_lib.kmx_filter_dev.argtypes = [_vp, C.POINTER(KmxFilterTask), C.POINTER(_vp)]
+_lib.kmx_filter_host.argtypes = [_vp, C.POINTER(KmxFilterTask), C.POINTER(_vp)]
+_lib.kmx_filter_result_wait.argtypes = [_vp]
+for _f in ("kmx_filter_result_rows", "kmx_filter_result_row_bytes", "kmx_filter_result_body_bytes", "kmx_filter_result_vector_len",
+           "kmx_filter_result_absent", "kmx_filter_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_filter_result_body_dev", "kmx_filter_result_vector_dev", "kmx_filter_result_absent_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_filter_result_copy_body", "kmx_filter_result_copy_vector", "kmx_filter_result_copy_absent"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_filter_result_kernel_ms.restype = C.c_double
+_lib.kmx_filter_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_filter_result_free.argtypes = [_vp]
+_lib.kmx_filter_marks_alloc.restype = _vp
+_lib.kmx_filter_marks_alloc.argtypes = [_vp, C.c_uint64]
+_lib.kmx_filter_marks_free.argtypes = [_vp, _vp]
+
+
+def filter_want(want):
+    """'m,v' / 'kmv' / a KMX_FILTER_* mask -> the mask"""
+    if isinstance(want, int):
+        return want
+    bits = {"m": FILTER_M, "v": FILTER_V, "k": FILTER_K}
+    return sum({bits[c] for c in want.replace(",", "")})
 
 
 def key_words_of(k):
@@ -495,6 +531,99 @@ class Context:
         res = _vp()
         self._check(_lib.kmx_merge_dev(self._h, prep[0], prep[1], C.byref(res)), "kmx_merge_dev")
         return MergeResult(self, res, prep[2])
+
+    def filter(self, rows_body, n_cols, key_words, mode, key_list, want="mv", marks=None):
+        """kmx_filter_host: whole rows of a .count / .pa matrix body (bytes or uint8 array) against one sample's count list
+        (keys uint64[n, key_words], counts uint32[n]).  marks: None (the rows are the whole partition) or a uint8 array of len(keys),
+        zero before the first run of rows, updated in place.  -> FilterOutput"""
+        rows = np.frombuffer(rows_body, dtype=np.uint8) if isinstance(rows_body, (bytes, bytearray, memoryview)) else np.ascontiguousarray(rows_body, dtype=np.uint8).reshape(-1)
+        rec = pack_records(key_list[0], key_list[1], key_words)
+        irb = key_words * 8 + (4 * n_cols if mode == MODE_COUNT else (n_cols + 7) // 8)
+        if len(rows) % irb:
+            raise ValueError(f"{len(rows)} bytes are not whole rows of {irb} bytes")
+        if marks is not None and (marks.dtype != np.uint8 or len(marks) != len(rec) or not marks.flags.c_contiguous):
+            raise ValueError("marks: a contiguous uint8 array with one entry per key record")
+        t = KmxFilterTask(key_words, mode, n_cols, filter_want(want), rows.ctypes.data if len(rows) else None, len(rows) // irb,
+                          KmxList(rec.ctypes.data if len(rec) else None, len(rec)), marks.ctypes.data if marks is not None and len(marks) else None, 0)
+        if marks is not None and not len(marks):      # (an empty key list has no marks to carry)
+            t.marks = None
+        res = _vp()
+        self._check(_lib.kmx_filter_host(self._h, C.byref(t), C.byref(res)), "kmx_filter_host")
+        r = FilterResult(self, res, key_words)
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def filter_dev(self, rows_dev, n_rows, n_cols, key_words, mode, key_dev, want="mv", marks_dev=None, keep=False):
+        """kmx_filter_dev: rows_dev a device pointer to n_rows whole rows (MergeResult.body_dev), key_dev = (device pointer, records)
+        (a list of count_reads_dev), marks_dev None or a device pointer to one byte per key record.
+        -> FilterOutput (numpy copies), or with keep the FilterResult itself (results left in HBM; .free() it)"""
+        t = KmxFilterTask(key_words, mode, n_cols, filter_want(want), rows_dev, n_rows, KmxList(key_dev[0], key_dev[1]), marks_dev, 0)
+        res = _vp()
+        self._check(_lib.kmx_filter_dev(self._h, C.byref(t), C.byref(res)), "kmx_filter_dev")
+        r = FilterResult(self, res, key_words)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+
+class FilterOutput:
+    """body: bytes of M (rows kept rows of row_bytes); vector: uint32 per input row (V); absent_keys uint64[n, key_words] and
+    absent_counts uint32[n] (K); what was not asked for is empty"""
+
+    def __init__(self, body, rows, row_bytes, vector, absent_keys, absent_counts):
+        self.body, self.rows, self.row_bytes, self.vector = body, rows, row_bytes, vector
+        self.absent_keys, self.absent_counts = absent_keys, absent_counts
+
+
+class FilterResult:
+    def __init__(self, ctx, h, key_words):
+        self._ctx, self._h, self._kw = ctx, h, key_words
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_filter_result_wait(self._h), "kmx_filter_result_wait")
+
+    def rows(self):
+        return _lib.kmx_filter_result_rows(self._h)
+
+    def row_bytes(self):
+        return _lib.kmx_filter_result_row_bytes(self._h)
+
+    def body_dev(self):
+        return _lib.kmx_filter_result_body_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_filter_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_filter_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        body = np.zeros(_lib.kmx_filter_result_body_bytes(self._h), np.uint8)
+        self._ctx._check(_lib.kmx_filter_result_copy_body(self._h, body.ctypes.data, len(body)), "kmx_filter_result_copy_body")
+        vec = np.zeros(_lib.kmx_filter_result_vector_len(self._h), np.uint32)
+        self._ctx._check(_lib.kmx_filter_result_copy_vector(self._h, vec.ctypes.data, len(vec)), "kmx_filter_result_copy_vector")
+        n, w = _lib.kmx_filter_result_absent(self._h), self._kw * 2 + 1
+        rec = np.zeros((n, w), np.uint32)
+        self._ctx._check(_lib.kmx_filter_result_copy_absent(self._h, rec.ctypes.data, rec.nbytes), "kmx_filter_result_copy_absent")
+        keys = np.ascontiguousarray(rec[:, :self._kw * 2]).view(np.uint64).reshape(n, self._kw)
+        return FilterOutput(body.tobytes(), self.rows(), self.row_bytes(), vec, keys, rec[:, self._kw * 2].copy())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_filter_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class MergeResult:
