@@ -275,6 +275,70 @@ double   kmx_filter_result_kernel_ms(kmx_filter_result* r);
 uint64_t kmx_filter_result_algo_bytes(kmx_filter_result* r);
 void     kmx_filter_result_free(kmx_filter_result* r);
 
+/* ---------------------------------------------------------------- combine */
+
+/* `kmtricks combine`: the matrices of several runs that share a repartition, joined by key (km::MatrixMerger / PartitionMerger,
+ * matrix.hpp:396-886).  A task is ONE partition (or one key range of it): n_blocks blocks in column order.  Block i: n_rows rows,
+ * keys strictly ascending (most significant word first), each row key_words * 8 key bytes (low word first) and
+ *   KMX_MODE_COUNT  n_cols counts of count_bytes (1, 2 or 4) bytes, little endian -- a matrix body has 4-byte counts, the body of a
+ *                   .kmer count file is a one-column block of 1-, 2- or 4-byte counts
+ *   KMX_MODE_PA     ceil(n_cols / 8) bytes, column j = bit j & 7 of byte j >> 3; the padding bits of the last byte are ignored
+ *                   (count_bytes is not read)
+ * The output: one row per distinct key of the union of the blocks, ascending; with N = the sum of the blocks' columns and pos_i =
+ * the columns of the blocks in front of block i,
+ *   KMX_MODE_COUNT  key + N u32: column pos_i + c = block i's count c widened to 32 bits, 0 where block i lacks the key
+ *   KMX_MODE_PA     key + ceil(N / 8) bytes: bit pos_i + c = block i's bit c (pos_i need not be a multiple of 8), 0 where block i
+ *                   lacks the key; the padding bits of the last byte are 0
+ * KMX_COMBINE_DROP_LAST (what PartitionMerger::next does, matrix.hpp:534-583): the greatest key of the union is not written when
+ * exactly one block holds it; it is written when two or more do.  Decided on the device.
+ * Example (COUNT, one-word keys): block 0, 2 columns, rows 3:(1,2) 9:(5,6); block 1, 1 column of 1-byte counts, rows 3:(7) 4:(8)
+ * -> 3:(1,2,7) 4:(0,0,8) 9:(5,6,0); with KMX_COMBINE_DROP_LAST the row of key 9 is missing.
+ * Hash matrices are blocks of key_words = 1.  `rows` pointers need no alignment (a 1-byte-count .kmer body has 9-byte rows).
+ * Empty blocks and a task of empty blocks are legal (0 rows); a task of one block copies and widens it, clears the PA padding and
+ * honours KMX_COMBINE_DROP_LAST.
+ * LIMITS, each refused before any GPU work: 1 <= n_blocks <= KMX_COMBINE_MAX_BLOCKS (KMX_E_INVAL / KMX_E_UNSUPPORTED); key_words
+ * 1 ... 4, mode COUNT or PA, count_bytes 1, 2 or 4 for COUNT, at least one column a block (KMX_E_INVAL; Bloom modes
+ * KMX_E_UNSUPPORTED); at most 2^32 - 256 rows a block and as many in the output -- the output's rows are known on the device
+ * only, so the test is on their bound, the blocks' rows together; an input or output row below 4 GiB (KMX_E_UNSUPPORTED).
+ * Scratch, from the context's pool: 8 * key_words + 4 * n_blocks bytes per input row, and the output is sized for the bound of its
+ * rows, the blocks' rows together (the call does not wait for the true count).  A call on large bodies already in HBM can therefore
+ * return KMX_E_NOMEM although its true output would fit: combine such a partition in key ranges, as `kmx combine --gpus` does. */
+#define KMX_COMBINE_DROP_LAST 1u
+#define KMX_COMBINE_MAX_BLOCKS 64u
+typedef struct {
+  const void* rows;
+  uint64_t    n_rows;
+  uint32_t    n_cols;
+  uint32_t    count_bytes;     /* KMX_MODE_COUNT: 1, 2 or 4 */
+} kmx_block;
+typedef struct {
+  uint32_t key_words, mode, n_blocks, flags;
+  const kmx_block* blocks;          /* [n_blocks], column order */
+  const uint8_t*   block_on_device; /* kmx_combine_host only: NULL, or [n_blocks], non-zero = rows is a DEVICE pointer */
+} kmx_combine_task;
+
+typedef struct kmx_combine_result kmx_combine_result;
+
+/* every rows pointer a DEVICE pointer -- kmx_result_body_dev of a COUNT / PA merge result, kmx_filter_result_body_dev, another
+ * combine's body, the caller's own memory.  The kernels are queued on the context's stream (kmx_stream), behind whatever produced
+ * those bodies there, and the call returns without waiting; the result stays in HBM until it is freed. */
+int kmx_combine_dev(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out);
+/* HOST pointers (see block_on_device): the blocks are uploaded on a stream of their own, so a task travels while the task before
+ * it is combined.  The host buffers may be reused once kmx_combine_result_wait has returned. */
+int kmx_combine_host(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out);
+int      kmx_combine_result_wait(kmx_combine_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t kmx_combine_result_rows(kmx_combine_result* r);
+uint64_t kmx_combine_result_row_bytes(const kmx_combine_result* r);
+uint64_t kmx_combine_result_body_bytes(kmx_combine_result* r);      /* rows * row_bytes */
+const void* kmx_combine_result_body_dev(kmx_combine_result* r);
+int      kmx_combine_result_copy_body(kmx_combine_result* r, void* host_dst, uint64_t dst_bytes);
+/* duration in ms of the call's kernels, the clearing of their tables included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_combine_result_kernel_ms(kmx_combine_result* r);
+/* algorithmic bytes: every input row read once plus every output row written once */
+uint64_t kmx_combine_result_algo_bytes(kmx_combine_result* r);
+void     kmx_combine_result_free(kmx_combine_result* r);
+
 /* ------------------------------------------------------------------ count */
 
 /* superk: concatenated super-k-mer records [u8 n][2-bit nts] of one

@@ -34,6 +34,18 @@ class KmxFilterTask(C.Structure):
 FILTER_M, FILTER_V, FILTER_K = 1, 2, 4
 
 
+class KmxBlock(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_uint64), ("n_cols", C.c_uint32), ("count_bytes", C.c_uint32)]
+
+
+class KmxCombineTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_blocks", C.c_uint32), ("flags", C.c_uint32),
+                ("blocks", C.POINTER(KmxBlock)), ("block_on_device", C.c_void_p)]
+
+
+COMBINE_DROP_LAST, COMBINE_MAX_BLOCKS = 1, 64
+
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -156,6 +168,20 @@ _lib.kmx_filter_result_free.argtypes = [_vp]
 _lib.kmx_filter_marks_alloc.restype = _vp
 _lib.kmx_filter_marks_alloc.argtypes = [_vp, C.c_uint64]
 _lib.kmx_filter_marks_free.argtypes = [_vp, _vp]
+
+
+_lib.kmx_combine_dev.argtypes = [_vp, C.POINTER(KmxCombineTask), C.POINTER(_vp)]
+_lib.kmx_combine_host.argtypes = [_vp, C.POINTER(KmxCombineTask), C.POINTER(_vp)]
+_lib.kmx_combine_result_wait.argtypes = [_vp]
+for _f in ("kmx_combine_result_rows", "kmx_combine_result_row_bytes", "kmx_combine_result_body_bytes", "kmx_combine_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_combine_result_body_dev.restype = _vp
+_lib.kmx_combine_result_body_dev.argtypes = [_vp]
+_lib.kmx_combine_result_copy_body.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_combine_result_kernel_ms.restype = C.c_double
+_lib.kmx_combine_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_combine_result_free.argtypes = [_vp]
 
 
 def filter_want(want):
@@ -569,6 +595,102 @@ class Context:
             return r.output()
         finally:
             r.free()
+
+
+    @staticmethod
+    def _block_row_bytes(key_words, mode, n_cols, count_bytes):
+        return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
+
+    def combine(self, blocks, key_words, mode, drop_last=False):
+        """kmx_combine_host: blocks = [(body, n_cols[, count_bytes])] in column order, body the bytes (or a uint8 array) of whole rows:
+        key words, then n_cols counts of count_bytes (1, 2 or 4; 4 when left out) bytes or ceil(n_cols / 8) presence/absence bytes.
+        -> CombineOutput (rows, row_bytes, body, kernel_ms, algo_bytes)"""
+        keep, arr = [], (KmxBlock * max(len(blocks), 1))()
+        for i, b in enumerate(blocks):
+            body, n_cols, cb = b[0], b[1], (b[2] if len(b) > 2 else 4)
+            a = np.frombuffer(body, dtype=np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+            irb = self._block_row_bytes(key_words, mode, n_cols, cb)
+            if len(a) % irb:
+                raise ValueError(f"block {i}: {len(a)} bytes are not whole rows of {irb} bytes")
+            keep.append(a)
+            arr[i] = KmxBlock(a.ctypes.data if len(a) else None, len(a) // irb, n_cols, cb)
+        t = KmxCombineTask(key_words, mode, len(blocks), COMBINE_DROP_LAST if drop_last else 0, arr, None)
+        res = _vp()
+        self._check(_lib.kmx_combine_host(self._h, C.byref(t), C.byref(res)), "kmx_combine_host")
+        r = CombineResult(self, res)
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def combine_dev(self, blocks, key_words, mode, drop_last=False, keep=False):
+        """kmx_combine_dev: blocks = [(device pointer, n_rows, n_cols[, count_bytes])] in column order -- a torch tensor's data_ptr(),
+        MergeResult.body_dev(), FilterResult.body_dev(), CombineResult.body_dev().
+        -> CombineOutput (numpy copy of the body), or with keep the CombineResult itself (the body left in HBM; .free() it)"""
+        arr = (KmxBlock * max(len(blocks), 1))()
+        for i, b in enumerate(blocks):
+            arr[i] = KmxBlock(b[0], b[1], b[2], b[3] if len(b) > 3 else 4)
+        t = KmxCombineTask(key_words, mode, len(blocks), COMBINE_DROP_LAST if drop_last else 0, arr, None)
+        res = _vp()
+        self._check(_lib.kmx_combine_dev(self._h, C.byref(t), C.byref(res)), "kmx_combine_dev")
+        r = CombineResult(self, res)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+
+class CombineOutput:
+    """body: the bytes of `rows` rows of `row_bytes`; kernel_ms < 0 without set_profiling; algo_bytes: every input row read once plus
+    every output row written once"""
+
+    def __init__(self, body, rows, row_bytes, kernel_ms, algo_bytes):
+        self.body, self.rows, self.row_bytes, self.kernel_ms, self.algo_bytes = body, rows, row_bytes, kernel_ms, algo_bytes
+
+
+class CombineResult:
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_combine_result_wait(self._h), "kmx_combine_result_wait")
+
+    def rows(self):
+        return _lib.kmx_combine_result_rows(self._h)
+
+    def row_bytes(self):
+        return _lib.kmx_combine_result_row_bytes(self._h)
+
+    def body_dev(self):
+        return _lib.kmx_combine_result_body_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_combine_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_combine_result_algo_bytes(self._h)
+
+    def body(self):
+        self.wait()
+        buf = np.zeros(_lib.kmx_combine_result_body_bytes(self._h), np.uint8)
+        self._ctx._check(_lib.kmx_combine_result_copy_body(self._h, buf.ctypes.data, len(buf)), "kmx_combine_result_copy_body")
+        return buf.tobytes()
+
+    def output(self):
+        return CombineOutput(self.body(), self.rows(), self.row_bytes(), self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_combine_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class FilterOutput:
