@@ -22,6 +22,8 @@
  *   kmx_filter_dev / _host      replace km::FilterTask::{exec,f_count_matrix,f_pa_matrix} on top of km::MatrixFilter
  *                               (include/kmtricks/matrix.hpp:23-393), run by main_filter (include/kmtricks/cmd.hpp:609-724):
  *                               one partition's matrix rows joined with the new sample's count list
+ *   kmx_query_dev / _host       no counterpart in the 1.6.0 tree (kmtricks 1.0's `kmtricks query`): query sequences against the .cmbf
+ *                               matrices of a hash:bf:bin run, addressed as kmer_hash.hpp:244-328 and repartition.hpp:94-103 publish
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -338,6 +340,59 @@ double   kmx_combine_result_kernel_ms(kmx_combine_result* r);
 /* algorithmic bytes: every input row read once plus every output row written once */
 uint64_t kmx_combine_result_algo_bytes(kmx_combine_result* r);
 void     kmx_combine_result_free(kmx_combine_result* r);
+
+/* ------------------------------------------------------------------ query */
+
+/* Which samples of a Bloom matrix hold the k-mers of a query sequence (what kmtricks 1.0 shipped as `kmtricks query` and kmindex
+ * does today; the addressing is the published one: repartition.hpp:94-103 get_partition, kmer_hash.hpp:244-328 WinHasher).
+ * The index: the .cmbf bodies of a `--mode hash:bf:bin` run -- per partition `window` rows of ceil(n_cols / 8) bytes, sample i = bit
+ * i & 7 of byte i >> 3.  For every query q (read q = bases[offsets[q] .. offsets[q + 1]), as in kmx_count_reads) and every position
+ * whose k bases are all ACGT (either case): c = the canonical k-mer (A0 C1 T2 G3, min(forward, reverse complement)), p =
+ * repart[minimizer(c)] (the split's minimizer), h = XXH64(c's ceil(k / 32) words, seed 0) % window (kmx_count_hash without the
+ * partition offset), row = rows[p] + h * ceil(n_cols / 8).  Results: n_kmers[q] = such positions; hits[q * n_cols + i] = those whose
+ * row has bit i set.  Every occurrence counts; a row's padding bits are never read into a result; a query without a valid k-mer has
+ * zeros and is still reported.
+ * rows: a HOST array of nb_parts pointers to matrix bodies; NULL = the partition is not part of this call (its k-mers count in
+ * n_kmers and add no hits).  hits: NULL (the result owns a zeroed table), or a DEVICE table of n_seqs * n_cols u32 that the call ADDS
+ * to: the partition groups of one set of queries accumulate on the device (u32 adds commute: the table does not depend on order).
+ * LIMITS, each refused before any GPU work: 8 <= kmer_size <= 127, 4 <= minim_size <= 15 and < kmer_size, 1 <= nb_parts <= 65535
+ * (KMX_E_INVAL); window 1 ... 2^32 - 1, fewer than 2^31 queries and fewer than 2^32 bases a call -- so no query has 2^32 positions
+ * or more, the counters are u32 -- (KMX_E_UNSUPPORTED: send the queries in batches).
+ * Scratch from the context's pool: 16 bytes a base. */
+typedef struct {
+  const char*     bases;
+  const uint64_t* offsets;      /* [n_seqs + 1], offsets[0] = 0 */
+  uint64_t        n_seqs;
+  uint32_t        kmer_size, minim_size;
+  const uint16_t* repart;       /* u16[4^minim_size]: minimizer -> partition */
+  uint32_t        nb_parts;
+  uint32_t        n_cols;       /* N: samples (bits of a row) */
+  uint64_t        window;       /* W: rows of a partition's matrix */
+  const uint8_t* const* rows;   /* [nb_parts] */
+  uint32_t*       hits;         /* NULL, or a device table to accumulate into */
+} kmx_query_task;
+
+typedef struct kmx_query_result kmx_query_result;
+
+/* bases, offsets, repart and every rows[p] DEVICE pointers (the rows array itself lies in host memory).  The kernels are queued on the
+ * context's stream (kmx_stream) and the call returns; it reads offsets[n_seqs] back first (8 bytes: the grid's size).  The result
+ * stays in HBM until it is freed. */
+int kmx_query_dev(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out);
+/* HOST pointers (hits, when given, is still a device table): everything is uploaded on a stream of its own, so a call's inputs travel
+ * while the call before it runs.  The host buffers may be reused once kmx_query_result_wait has returned. */
+int kmx_query_host(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out);
+int      kmx_query_result_wait(kmx_query_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t kmx_query_result_n_seqs(const kmx_query_result* r);
+int      kmx_query_result_copy_kmers(kmx_query_result* r, uint32_t* host_dst, uint64_t dst_entries);   /* n_seqs entries */
+int      kmx_query_result_copy_hits(kmx_query_result* r, uint32_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols: the table as it stands, the task's when one was given */
+uint32_t* kmx_query_result_hits_dev(kmx_query_result* r);
+/* duration in ms of the call's kernels, the clearing of their tables included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_query_result_kernel_ms(kmx_query_result* r);
+/* algorithmic bytes: the bases read + one row per valid k-mer of a partition that is part of the call or not (n_kmers * ceil(n_cols / 8))
+ * + the hits table written */
+uint64_t kmx_query_result_algo_bytes(kmx_query_result* r);
+void     kmx_query_result_free(kmx_query_result* r);
 
 /* ------------------------------------------------------------------ count */
 

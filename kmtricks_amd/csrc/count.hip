@@ -23,6 +23,7 @@
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "skf.hpp"
+#include "kmer_dev.hpp"
 #include "count_sort.hpp"
 
 namespace kmx {
@@ -31,12 +32,6 @@ static bool list_copy_trace() { static const bool on = getenv("KMX_TRACE") != nu
 
 typedef __uint128_t u128;
 
-__device__ __forceinline__ u64 rev_digits64(u64 x)
-{ // reverse the 32 2-bit digits of a word
-  x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
-  x = ((x >> 4) & 0x0F0F0F0F0F0F0F0FULL) | ((x & 0x0F0F0F0F0F0F0F0FULL) << 4);
-  return __builtin_bswap64(x);
-}
 __device__ __forceinline__ u64 revcomp64(u64 x, int k)
 { // A0 C1 T2 G3: complement = digit ^ 2 (gatb kmer/impl/Model.hpp:857-884)
   return (rev_digits64(x) ^ 0xAAAAAAAAAAAAAAAAULL) >> (64 - 2 * k);
@@ -46,34 +41,6 @@ __device__ __forceinline__ u128 revcomp128(u128 x, int k)
   const u64 lo = (u64)x, hi = (u64)(x >> 64);
   const u128 r = ((u128)(rev_digits64(lo) ^ 0xAAAAAAAAAAAAAAAAULL) << 64) | (u128)(rev_digits64(hi) ^ 0xAAAAAAAAAAAAAAAAULL);
   return r >> (128 - 2 * k);
-}
-
-// XXH64 of 8 / 16 bytes, seed 0 (Cyan4973/xxHash specification; KmXXHash sorting_count.hpp:346-363)
-#define XP1 0x9E3779B185EBCA87ULL
-#define XP2 0xC2B2AE3D27D4EB4FULL
-#define XP3 0x165667B19E3779F9ULL
-#define XP4 0x85EBCA77C2B2AE63ULL
-#define XP5 0x27D4EB2F165667C5ULL
-__device__ __forceinline__ u64 rotl64d(u64 x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ u64 xxh64_round(u64 acc, u64 in) { return rotl64d(acc + in * XP2, 31) * XP1; }
-__device__ __forceinline__ u64 xxh64_merge(u64 h, u64 v) { return (h ^ xxh64_round(0, v)) * XP1 + XP4; }
-__device__ __forceinline__ u64 xxh64_words(const u64* w, int nw)
-{
-  if (nw == 4) {      // 32 bytes (Kmer<128>): one stripe through the four accumulators, nothing left over
-    const u64 v1 = xxh64_round(XP1 + XP2, w[0]), v2 = xxh64_round(XP2, w[1]), v3 = xxh64_round(0, w[2]), v4 = xxh64_round(0ULL - XP1, w[3]);
-    u64 h = rotl64d(v1, 1) + rotl64d(v2, 7) + rotl64d(v3, 12) + rotl64d(v4, 18);
-    h = xxh64_merge(h, v1); h = xxh64_merge(h, v2); h = xxh64_merge(h, v3); h = xxh64_merge(h, v4);
-    h += 32;
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
-    return h;
-  }
-  u64 h = XP5 + (u64)nw * 8;
-  for (int i = 0; i < nw; i++) {
-    h ^= rotl64d(w[i] * XP2, 31) * XP1;
-    h = rotl64d(h, 27) * XP1 + XP4;
-  }
-  h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
-  return h;
 }
 
 // ---- decode, one LANE per k-mer (round 3; rounds 1-2 walked a record per thread with byte loads and strided stores) ----------

@@ -93,6 +93,15 @@ hipError_t launch_combine_place(int kw, const CombineBlock* blocks, u32 nb, u32 
 hipError_t launch_combine_total(const CombineBlock* blocks, u32 nb, const u32* tcnt, const u32* src, u64 cap, int drop_last, u32* tot, hipStream_t st);
 hipError_t launch_combine_move(int pa, const CombineBlock* blocks, u32 nb, u32 kb, u32 n_cols, u32 orb, const u32* src, u64 cap, const u32* tot,
                                u8* out, hipStream_t st);
+// query.hip: query sequences against the Bloom matrices of a run (kmx_query_dev)
+void query_chunks(u64 n_bases, u32 n_parts, u32* n_tiles, u32* n_chunks, u32* tiles_per_chunk);      // the walk's layout: tiles of 64 positions, chunks of tiles (a wave each)
+hipError_t launch_query_keys(int kw, const char* bases, const u64* offsets, u32 n_seqs, u64 n_bases, int k, int m, const u16* repart, u64 window,
+                             u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk, u64* keys, u32* hist /* [n_parts][n_chunks] + 1, zeroed */, u32* n_kmers /* zeroed */, hipStream_t st);
+hipError_t launch_query_parts(const u32* cell, u32 n_parts, u32 n_chunks, u32* pstart /* n_parts + 1 */, hipStream_t st);
+hipError_t launch_query_scatter(const u64* keys, const u64* offsets, u32 n_seqs, u64 n_bases, u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk,
+                                u32* cell, u64* recs, hipStream_t st);
+hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
+                               u32* hits, u32 n_cu, hipStream_t st);
 
 }  // namespace kmx
 

@@ -1,0 +1,306 @@
+// query.hip -- `kmx query` on the device: which samples of a Bloom matrix (--mode hash:bf:bin, one .cmbf a partition) hold the k-mers
+// of a set of query sequences.  No reference counterpart in the 1.6.0 tree (kmtricks 1.0's `kmtricks query` moved to kmindex); the
+// addressing is the published one: repartition.hpp:94-103 get_partition, kmer_hash.hpp:244-328 WinHasher.  gfx950, wave64.
+//
+//   k_query_keys     the concatenated base stream is cut in tiles of 64 positions, a WAVE takes a run of tiles (a chunk), a lane one
+//                    position: the bases of the tile and of the 192 behind it become ballot bit planes, a lane's k-mer is k bits of
+//                    each plane at its own position -- canonical form by bit reversal, minimizer = window minimum of mmer_value
+//                    (a sparse table over the 192 m-mer values, wave shuffles), row = XXH64(words) % window.  The query of a position
+//                    is a search of `offsets`, bounded by a gallop from the query of the tile before.  Per valid position one u64
+//                    (partition << 32 | row) at the position's own slot; one add per partition of the tile to its (partition, chunk)
+//                    counter and one per query to n_kmers[query].
+//   scan             launch_filter_scan over the counters laid out [partition][chunk]: every cell's place in partition order, position
+//                    order kept inside a partition (a stable counting sort, one wave the only writer of its cells)
+//   k_query_parts    first record of every partition
+//   k_query_scatter  the same chunks again: (row, query) records to their place
+//   k_query_gather   a group of L lanes (L = the row's dwords rounded up to a power of two, at most 64) takes QG_RUN consecutive records,
+//                    a lane one dword of the row (more when a row has more than 64): rows are loaded at whatever alignment they have,
+//                    summed per bit column in QG_PLANES bit-sliced planes (a ripple-carry add of one bit a row and plane), and the
+//                    non-zero column sums go to hits[query][column] with u32 atomic adds whenever the query changes and at the end.
+//                    Integer adds commute: the table does not depend on scheduling.
+// Nothing holds a row or a query in LDS: no limit on columns or on a query's length below 2^32 positions.
+#include "kmx_host.hpp"
+#include "kmer_dev.hpp"
+
+namespace kmx {
+
+constexpr u32 QK_BLOCK = 256;          // threads of a workgroup of the key / scatter walk: four chunks
+constexpr u32 QG_PLANES = 6;           // bit-sliced counter planes: column sums up to 63
+constexpr u32 QG_RUN = 63;             // records of a gather item: what the planes hold without a flush
+constexpr u64 QK_NONE = ~0ULL;
+
+// bit i of y -> bit 2i (i < 32)
+__device__ __forceinline__ u64 spread32(u32 y) { return (u64)spread16(y & 0xFFFFu) | ((u64)spread16(y >> 16) << 32); }
+// bits [32 w, 32 w + 32) of the 128 bits (lo, hi)
+__device__ __forceinline__ u32 q_bits32(u64 lo, u64 hi, int w) { return w == 0 ? (u32)lo : w == 1 ? (u32)(lo >> 32) : w == 2 ? (u32)hi : (u32)(hi >> 32); }
+// the low k bits of (lo, hi) in reverse order (bit i <- bit k - 1 - i), 1 <= k <= 127; the bits from k on are zero in and out
+__device__ __forceinline__ void q_rev(u64 lo, u64 hi, int k, u64& rlo, u64& rhi)
+{
+  const u64 RL = __brevll(hi), RH = __brevll(lo);      // the 128 bits reversed: RH:RL
+  const int sft = 128 - k;                             // 1 .. 127
+  if (sft >= 64) { rlo = RH >> (sft - 64); rhi = 0; }
+  else { rlo = (RL >> sft) | (RH << (64 - sft)); rhi = RH >> sft; }
+}
+
+// the query that holds position pos: the greatest q in [lo, hi) with offsets[q] <= pos (offsets[lo] <= pos < offsets[hi]; empty
+// queries share their offset with the one behind them and are skipped)
+__device__ __forceinline__ u32 q_query_of(const u64* __restrict__ offsets, u32 lo, u32 hi, u64 pos)
+{
+  while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (offsets[mid] <= pos) lo = mid; else hi = mid; }
+  return lo;
+}
+// ... for the 64 positions of the tile at t0, given a query qs at or in front of position t0's: a gallop finds the first query behind the tile
+__device__ __forceinline__ u32 q_tile_query(const u64* __restrict__ offsets, u32 n_seqs, u32 qs, u64 t0, u64 pos)
+{
+  const u64 last = t0 + 63;
+  u32 step = 1, hi = qs + 1;
+  while (hi < n_seqs && offsets[hi] <= last) { step <<= 1; hi = n_seqs - qs > step ? qs + step : n_seqs; }      // (uniform over the wave)
+  return q_query_of(offsets, qs, hi, pos);
+}
+
+struct QChunks { u32 n_tiles, n_chunks, tiles_per_chunk; };
+
+template <int KW>
+__global__ __launch_bounds__(QK_BLOCK)
+void k_query_keys(const char* __restrict__ bases, const u64* __restrict__ offsets, u32 n_seqs, u64 n_bases, int k, int m,
+                  const u16* __restrict__ repart, u64 window, QChunks ch, u64* __restrict__ keys, u32* __restrict__ hist, u32* __restrict__ n_kmers)
+{
+  const int lane = threadIdx.x & 63;
+  const u32 c = (blockIdx.x * QK_BLOCK + threadIdx.x) >> 6;
+  if (c >= ch.n_chunks) return;
+  const u32 tile0 = c * ch.tiles_per_chunk, tile1 = min(tile0 + ch.tiles_per_chunk, ch.n_tiles);
+  if (tile0 >= tile1) return;
+  const int nbm = k - m + 1;                       // m-mers of a k-mer: 1 .. 124
+  const u32 mmask = (1u << m) - 1;
+  const u64 klo = k >= 64 ? ~0ULL : (1ULL << k) - 1ULL, khi = k > 64 ? (1ULL << (k - 64)) - 1ULL : 0ULL;
+  u32 qs = q_query_of(offsets, 0, n_seqs, (u64)tile0 * 64);      // (position tile0 * 64 < n_bases = offsets[n_seqs])
+  for (u32 t = tile0; t < tile1; t++) {
+    const u64 t0 = (u64)t * 64, pos = t0 + lane;
+    u8 cc[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) cc[i] = pos + 64u * i < n_bases ? (u8)bases[pos + 64u * i] : (u8)'N';
+    u64 I[3], A[4], B[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { if (i < 3) I[i] = __ballot(!nt_valid(cc[i])); A[i] = __ballot((cc[i] >> 1) & 1); B[i] = __ballot((cc[i] >> 2) & 1); }
+    auto fun = [&](u64 x, u64 y) { return lane ? (x >> lane) | (y << (64 - lane)) : x; };
+    const u64 fi_lo = fun(I[0], I[1]), fi_hi = fun(I[1], I[2]);
+    const u64 fa_lo = fun(A[0], A[1]), fa_hi = fun(A[1], A[2]), fa_2 = fun(A[2], A[3]);
+    const u64 fb_lo = fun(B[0], B[1]), fb_hi = fun(B[1], B[2]), fb_2 = fun(B[2], B[3]);
+    // ---- the minimizer: the minimum of the m-mer values at positions lane .. lane + nbm - 1 of the 192 at hand ----
+    auto mval = [&](u64 a, u64 b) {      // the m-mer that starts at bit 0 of (a, b): base j is digit m-1-j
+      const u32 y0 = __brev((u32)a & mmask) >> (32 - m), y1 = __brev((u32)b & mmask) >> (32 - m);
+      return mmer_value(spread16(y0) | (spread16(y1) << 1), m);
+    };
+    u32 v0 = mval(fa_lo, fb_lo), v1 = mval(fa_hi, fb_hi), v2 = mval(fa_2, fb_2);      // positions lane, 64 + lane, 128 + lane
+    int span = 1;                                                                      // v holds the minimum over `span` positions
+#pragma unroll
+    for (int d = 1; d <= 32; d <<= 1) {
+      if (2 * d > nbm) break;                                                          // (uniform)
+      const u32 n0 = min(v0, sk_at(v0, v1, d, lane)), n1 = min(v1, sk_at(v1, v2, d, lane)), n2 = min(v2, sk_at(v2, 0xFFFFFFFFu, d, lane));
+      v0 = n0; v1 = n1; v2 = n2; span = 2 * d;
+    }
+    // (span <= nbm < 2 span, or span = 64 and nbm <= 124: two spans cover the window; the second starts nbm - span < 64 positions on)
+    const u32 mini = nbm > span ? min(v0, sk_at(v0, v1, nbm - span, lane)) : v0;
+    // ---- the canonical k-mer: digit i is base k - 1 - i (A0 C1 T2 G3: plane A the low bit, plane B the high one) ----
+    const u64 a_lo = fa_lo & klo, a_hi = fa_hi & khi, b_lo = fb_lo & klo, b_hi = fb_hi & khi;
+    u64 ra_lo, ra_hi, rb_lo, rb_hi;
+    q_rev(a_lo, a_hi, k, ra_lo, ra_hi); q_rev(b_lo, b_hi, k, rb_lo, rb_hi);
+    const u64 nb_lo = ~b_lo & klo, nb_hi = ~b_hi & khi;      // the reverse complement's digit i is base i ^ 2
+    u64 f[KW], r[KW];
+#pragma unroll
+    for (int w = 0; w < KW; w++) {
+      f[w] = spread32(q_bits32(ra_lo, ra_hi, w)) | (spread32(q_bits32(rb_lo, rb_hi, w)) << 1);
+      r[w] = spread32(q_bits32(a_lo, a_hi, w)) | (spread32(q_bits32(nb_lo, nb_hi, w)) << 1);
+    }
+    bool less = false, decided = false;
+#pragma unroll
+    for (int w = KW - 1; w >= 0; w--) if (!decided && f[w] != r[w]) { less = f[w] < r[w]; decided = true; }
+    u64 cw[KW];
+#pragma unroll
+    for (int w = 0; w < KW; w++) cw[w] = less ? f[w] : r[w];
+    const u64 h = xxh64_words(cw, KW) % window;
+    // ---- which query, and is the k-mer whole and inside it ----
+    const u32 q = q_tile_query(offsets, n_seqs, qs, t0, pos);
+    bool valid = pos < n_bases && (fi_lo & klo) == 0 && (fi_hi & khi) == 0;
+    if (valid) valid = pos >= offsets[q] && pos + (u64)k <= offsets[q + 1];      // (bases in front of offsets[0] belong to no query)
+    const u32 part = valid ? (u32)repart[mini] : 0u;
+    if (pos < n_bases) keys[pos] = valid ? ((u64)part << 32) | h : QK_NONE;
+    u64 vm = __ballot(valid);
+    while (vm) {      // one add per partition of the tile (neighbouring k-mers share their minimizer: a handful)
+      const int l = __builtin_ctzll(vm);
+      const u32 pp = (u32)__shfl((int)part, l);
+      const u64 same = __ballot(valid && part == pp);
+      if (lane == l) atomicAdd(&hist[(size_t)pp * ch.n_chunks + c], (u32)__popcll(same));
+      vm &= ~same;
+    }
+    vm = __ballot(valid);
+    while (vm) {      // one add per query of the tile
+      const int l = __builtin_ctzll(vm);
+      const u32 qq = (u32)__shfl((int)q, l);
+      const u64 same = __ballot(valid && q == qq);
+      if (lane == l) atomicAdd(&n_kmers[qq], (u32)__popcll(same));
+      vm &= ~same;
+    }
+    qs = (u32)__shfl((int)q, 63);      // (lanes behind the last base searched with pos >= n_bases: the walk ends with this tile)
+    if (t0 + 63 >= n_bases) break;
+  }
+}
+
+__global__ void k_query_parts(const u32* __restrict__ cell, u32 n_parts, u32 n_chunks, u32* __restrict__ pstart)
+{
+  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p <= n_parts) pstart[p] = cell[(size_t)p * n_chunks];      // (cell[n_parts * n_chunks]: the total)
+}
+
+__global__ __launch_bounds__(QK_BLOCK)
+void k_query_scatter(const u64* __restrict__ keys, const u64* __restrict__ offsets, u32 n_seqs, u64 n_bases, QChunks ch,
+                     u32* __restrict__ cell, u64* __restrict__ recs)
+{
+  const int lane = threadIdx.x & 63;
+  const u32 c = (blockIdx.x * QK_BLOCK + threadIdx.x) >> 6;
+  if (c >= ch.n_chunks) return;
+  const u32 tile0 = c * ch.tiles_per_chunk, tile1 = min(tile0 + ch.tiles_per_chunk, ch.n_tiles);
+  if (tile0 >= tile1) return;
+  u32 qs = q_query_of(offsets, 0, n_seqs, (u64)tile0 * 64);
+  for (u32 t = tile0; t < tile1; t++) {
+    const u64 t0 = (u64)t * 64, pos = t0 + lane;
+    const u64 key = pos < n_bases ? keys[pos] : QK_NONE;
+    const bool valid = key != QK_NONE;
+    const u32 q = q_tile_query(offsets, n_seqs, qs, t0, pos);
+    const u32 part = (u32)(key >> 32);
+    u64 vm = __ballot(valid);
+    while (vm) {      // the tile's partitions one by one: the lanes of one keep their order
+      const int l = __builtin_ctzll(vm);
+      const u32 pp = (u32)__shfl((int)part, l);
+      const bool mine = valid && part == pp;
+      const u64 same = __ballot(mine);
+      u32 base = 0;
+      if (lane == l) base = atomicAdd(&cell[(size_t)pp * ch.n_chunks + c], (u32)__popcll(same));      // (this wave is the cell's only writer)
+      base = (u32)__shfl((int)base, l);
+      if (mine) recs[base + (u32)__popcll(same & ((1ULL << lane) - 1ULL))] = (key & 0xFFFFFFFFULL) | ((u64)q << 32);
+      vm &= ~same;
+    }
+    qs = (u32)__shfl((int)q, 63);
+    if (t0 + 63 >= n_bases) break;
+  }
+}
+
+struct __attribute__((packed, aligned(1))) QDword { u32 v; };      // a dword at any address: one global_load_dword
+
+// LOG_L: log2 of the lanes of a group (a group's lane wl owns the row's dwords wl, wl + L, ...)
+template <int LOG_L>
+__global__ __launch_bounds__(256)
+void k_query_gather(const u64* __restrict__ recs, const u32* __restrict__ pstart, u32 n_parts, const u8* const* __restrict__ rows,
+                    u32 nb, u32 n_cols, u32* __restrict__ hits)
+{
+  constexpr u32 L = 1u << LOG_L, S = 64u / L;
+  const u32 total = pstart[n_parts];
+  const u32 lane = threadIdx.x & 63u, wl = lane & (L - 1u), sub = lane >> LOG_L;
+  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+  const u64 n_items = ((u64)total + QG_RUN - 1) / QG_RUN;
+  const u32 nw = (nb + 3u) / 4u;                   // dwords of a row, the last one maybe short
+  for (u64 g = wave * S + sub; g < n_items; g += n_waves * S) {
+    const u32 i0 = (u32)(g * QG_RUN), i1 = (u32)min((u64)total, (u64)i0 + QG_RUN);
+    u32 p0 = 0;
+    { u32 lo = 0, hi = n_parts; while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (pstart[mid] <= i0) lo = mid; else hi = mid; } p0 = lo; }      // pstart[p0] <= i0 (pstart[0] = 0)
+    for (u32 ws = wl; ws < nw; ws += L) {          // (one pass for rows of up to 64 dwords: 2048 columns)
+      const u32 whole = 4u * ws + 4u <= nb;
+      const u32 col0 = 32u * ws;
+      const u32 cmask = n_cols - col0 >= 32u ? 0xFFFFFFFFu : (1u << (n_cols - col0)) - 1u;      // the padding bits of the last byte are never read into a sum
+      u32 pl[QG_PLANES];
+#pragma unroll
+      for (u32 j = 0; j < QG_PLANES; j++) pl[j] = 0;
+      auto flush = [&](u32 q) {
+        u32 any = 0;
+#pragma unroll
+        for (u32 j = 0; j < QG_PLANES; j++) any |= pl[j];
+        for (u32 left = any; left; left &= left - 1u) {
+          const u32 b = (u32)__builtin_ctz(left);
+          u32 cnt = 0;
+#pragma unroll
+          for (u32 j = 0; j < QG_PLANES; j++) cnt |= ((pl[j] >> b) & 1u) << j;
+          atomicAdd(&hits[(u64)q * n_cols + col0 + b], cnt);
+        }
+#pragma unroll
+        for (u32 j = 0; j < QG_PLANES; j++) pl[j] = 0;
+      };
+      u32 p = p0, pend = pstart[p0 + 1];
+      const u8* base = rows[p0];
+      u32 cur_q = (u32)(recs[i0] >> 32);
+      for (u32 i = i0; i < i1; i++) {
+        const u64 rec = recs[i];
+        const u32 q = (u32)(rec >> 32);
+        while (i >= pend) { p++; pend = pstart[p + 1]; base = rows[p]; }      // (i < total = pstart[n_parts]: p stays below n_parts)
+        if (q != cur_q) { flush(cur_q); cur_q = q; }
+        if (!base) continue;                       // a partition that is not part of this call
+        const u8* rp = base + (u64)(u32)rec * nb + 4u * ws;      // 64-bit row offsets: window * nb passes 4 GiB
+        u32 x;
+        if (whole) x = reinterpret_cast<const QDword*>(rp)->v;
+        else { x = 0; for (u32 b = 0; 4u * ws + b < nb; b++) x |= (u32)rp[b] << (8u * b); }
+        x &= cmask;
+#pragma unroll
+        for (u32 j = 0; j < QG_PLANES; j++) { const u32 carry = pl[j] & x; pl[j] ^= x; x = carry; }
+      }
+      flush(cur_q);
+    }
+  }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+void query_chunks(u64 n_bases, u32 n_parts, u32* n_tiles, u32* n_chunks, u32* tiles_per_chunk)
+{
+  const u32 tiles = (u32)((n_bases + 63) / 64);
+  u32 chunks = std::max(1u, std::min(tiles, 2048u));
+  while (chunks > 1 && (u64)chunks * n_parts > 262144) chunks >>= 1;       // (the scan of the cells is one workgroup's: at most 262144 of them)
+  const u32 tpc = std::max(1u, (tiles + chunks - 1) / chunks);
+  *n_tiles = tiles; *tiles_per_chunk = tpc; *n_chunks = std::max(1u, (tiles + tpc - 1) / tpc);
+}
+
+hipError_t launch_query_keys(int kw, const char* bases, const u64* offsets, u32 n_seqs, u64 n_bases, int k, int m, const u16* repart, u64 window,
+                             u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk, u64* keys, u32* hist, u32* n_kmers, hipStream_t st)
+{
+  const QChunks ch{n_tiles, n_chunks, tiles_per_chunk};
+  const u32 grid = (n_chunks + QK_BLOCK / 64 - 1) / (QK_BLOCK / 64);
+  switch (kw) {
+    case 1: hipLaunchKernelGGL(k_query_keys<1>, dim3(grid), dim3(QK_BLOCK), 0, st, bases, offsets, n_seqs, n_bases, k, m, repart, window, ch, keys, hist, n_kmers); break;
+    case 2: hipLaunchKernelGGL(k_query_keys<2>, dim3(grid), dim3(QK_BLOCK), 0, st, bases, offsets, n_seqs, n_bases, k, m, repart, window, ch, keys, hist, n_kmers); break;
+    case 3: hipLaunchKernelGGL(k_query_keys<3>, dim3(grid), dim3(QK_BLOCK), 0, st, bases, offsets, n_seqs, n_bases, k, m, repart, window, ch, keys, hist, n_kmers); break;
+    case 4: hipLaunchKernelGGL(k_query_keys<4>, dim3(grid), dim3(QK_BLOCK), 0, st, bases, offsets, n_seqs, n_bases, k, m, repart, window, ch, keys, hist, n_kmers); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_query_parts(const u32* cell, u32 n_parts, u32 n_chunks, u32* pstart, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_query_parts, dim3((n_parts + 256) / 256), dim3(256), 0, st, cell, n_parts, n_chunks, pstart);
+  return hipGetLastError();
+}
+
+hipError_t launch_query_scatter(const u64* keys, const u64* offsets, u32 n_seqs, u64 n_bases, u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk,
+                                u32* cell, u64* recs, hipStream_t st)
+{
+  const QChunks ch{n_tiles, n_chunks, tiles_per_chunk};
+  const u32 grid = (n_chunks + QK_BLOCK / 64 - 1) / (QK_BLOCK / 64);
+  hipLaunchKernelGGL(k_query_scatter, dim3(grid), dim3(QK_BLOCK), 0, st, keys, offsets, n_seqs, n_bases, ch, cell, recs);
+  return hipGetLastError();
+}
+
+hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
+                               u32* hits, u32 n_cu, hipStream_t st)
+{
+  const u32 nw = (nb + 3) / 4;
+  int log_l = 0;
+  while (log_l < 6 && (1u << log_l) < nw) log_l++;
+  const u64 groups = (rec_bound + QG_RUN - 1) / QG_RUN, per_block = 4ull * (64u >> log_l);      // groups of lanes a workgroup holds
+  const u32 grid = (u32)std::max<u64>(1, std::min<u64>((groups + per_block - 1) / per_block, (u64)std::max(n_cu, 1u) * 8));
+#define KMX_QG(LL) hipLaunchKernelGGL(k_query_gather<LL>, dim3(grid), dim3(256), 0, st, recs, pstart, n_parts, rows, nb, n_cols, hits)
+  switch (log_l) {
+    case 0: KMX_QG(0); break; case 1: KMX_QG(1); break; case 2: KMX_QG(2); break; case 3: KMX_QG(3); break;
+    case 4: KMX_QG(4); break; case 5: KMX_QG(5); break; default: KMX_QG(6); break;
+  }
+#undef KMX_QG
+  return hipGetLastError();
+}
+
+}  // namespace kmx

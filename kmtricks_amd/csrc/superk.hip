@@ -30,35 +30,9 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "skf.hpp"
+#include "kmer_dev.hpp"
 
 namespace kmx {
-
-__device__ __forceinline__ bool nt_valid(u8 c)
-{ // gatb tools/misc/api/Data.hpp:179-196
-  const u8 u = c & 0xDF;
-  return u == 'A' || u == 'C' || u == 'G' || u == 'T';
-}
-
-// value of an m-mer as the reference's minimizer table gives it: min(x, revcomp_m(x)), or 4^m - 1 when
-// that contains AA anywhere but as a prefix (Model.hpp:1040-1064, 1220-1251) -- computed, not looked up
-__device__ __forceinline__ u32 mmer_value(u32 x, int m)
-{
-  const u32 n1 = (1u << (2 * m)) - 1;                                     // m <= 15
-  u32 t = __brev(x);
-  t = ((t >> 1) & 0x55555555u) | ((t & 0x55555555u) << 1);                 // digits reversed, bits of a digit in order
-  const u32 rc = (t >> (32 - 2 * m)) ^ (0xAAAAAAAAu & n1);                 // complement: A0 C1 T2 G3 -> digit ^ 2
-  const u32 v = rc < x ? rc : x;
-  const u64 mask_ma1 = 0x5555555555555555ULL & ((1ULL << ((m - 2) * 2)) - 1);
-  u64 a1 = v; a1 = ~(a1 | (a1 >> 2)); a1 = ((a1 >> 1) & a1) & mask_ma1;
-  return a1 ? n1 : v;
-}
-// bit i of y -> bit 2i (i < 16)
-__device__ __forceinline__ u32 spread16(u32 y)
-{
-  y = (y | (y << 8)) & 0x00FF00FFu; y = (y | (y << 4)) & 0x0F0F0F0Fu;
-  y = (y | (y << 2)) & 0x33333333u; y = (y | (y << 1)) & 0x55555555u;
-  return y;
-}
 
 // One WAVE per read, one lane per k-mer position (a chunk = 64 consecutive base positions):
 //   * the chunk's bases become three 64-bit bit planes (two code bits, one "invalid" bit) with ballots;
@@ -354,12 +328,6 @@ void k_superk_wave(const char* __restrict__ bases, const u64* __restrict__ offse
 //      minimum over a window comes from a sparse table over the 192 values (spans of 32 and 64, shuffles across the three
 //      registers); a chunk owns 63 k-mers.  Two passes (count, emit), statistics by atomics: the per-partition pass over the sorted
 //      descriptors (k_part_stats) carries the strands of at most 60 k-mers a descriptor.
-__device__ __forceinline__ u32 sk_at(u32 a, u32 b, int d, int lane)      // the value at position lane + d of the 128 positions (a: 0 .. 63, b: 64 .. 127), 0 <= d < 64
-{
-  const int src = (lane + d) & 63;
-  const u32 x = (u32)__shfl((int)a, src), y = (u32)__shfl((int)b, src);
-  return lane + d < 64 ? x : y;
-}
 __device__ __forceinline__ u32 sk_bit(u64 lo, u64 hi, int i) { return (u32)((i < 64 ? lo >> i : hi >> (i - 64)) & 1ULL); }
 // the k bits (lo, hi) in reverse order (bit i <- bit k - 1 - i), 64 <= k <= 127
 __device__ __forceinline__ void sk_rev(u64 lo, u64 hi, int k, u64& rlo, u64& rhi)

@@ -510,16 +510,20 @@ class SeqReader {
     p = tmp.data(); n = tmp.size();
     return true;
   }
+  // (kmx query) from here on next() keeps the name of the record it returns: the first word of its header line
+  void keep_names() { names_ = true; }
+  const std::string& name() const { return name_; }
   bool next(std::string& seq) {
     seq.clear();
     char c;
     if (!have_hdr_) {      // up to the next header line
-      while (peek(c)) { if (c == '>' || c == '@') { hdr_ = c; have_hdr_ = true; skip_line(); break; } skip_line(); }
+      while (peek(c)) { if (c == '>' || c == '@') { hdr_ = c; have_hdr_ = true; header_line(); break; } skip_line(); }
       if (!have_hdr_) return false;
     }
     have_hdr_ = false;
+    if (names_) name_ = next_name_;
     if (hdr_ == '>') {
-      while (peek(c)) { if (c == '>') { have_hdr_ = true; hdr_ = '>'; skip_line(); break; } take_line(seq); }
+      while (peek(c)) { if (c == '>') { have_hdr_ = true; hdr_ = '>'; header_line(); break; } take_line(seq); }
       return true;
     }
     // FASTQ: sequence lines until '+', then as many quality characters as bases
@@ -555,6 +559,22 @@ class SeqReader {
     }
     return n - (n && last == '\r' ? 1 : 0);
   }
+  // a header line is dropped, or (keep_names) its first word behind the '>' / '@' becomes the next record's name
+  void header_line() {
+    if (!names_) { skip_line(); return; }
+    next_name_.clear();
+    bool open = true;
+    for (;;) {
+      if (pos_ == end_ && !fill()) break;
+      const char* b = buf_.get() + pos_;
+      const char* nl = (const char*)memchr(b, '\n', end_ - pos_);
+      const size_t m = nl ? (size_t)(nl - b) : end_ - pos_;
+      for (size_t i = 0; i < m && open; i++) { const char c = b[i]; if (c == ' ' || c == '\t' || c == '\r') open = false; else next_name_ += c; }
+      pos_ += m + (nl ? 1 : 0);
+      if (nl) break;
+    }
+    if (!next_name_.empty()) next_name_.erase(0, 1);
+  }
   // the rest of the current line goes behind `s`, blanks, tabs and carriage returns left out
   void take_line(std::string& s) {
     for (;;) {
@@ -571,6 +591,7 @@ class SeqReader {
     }
   }
   gzFile gz_ = nullptr; int fd_ = -1; std::string path_; char hdr_ = 0; bool have_hdr_ = false, eof_ = false;
+  bool names_ = false; std::string name_, next_name_;
   std::unique_ptr<char[]> buf_; size_t pos_ = 0, end_ = 0;
 };
 

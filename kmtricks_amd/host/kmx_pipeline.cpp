@@ -1329,10 +1329,12 @@ int run(int argc, char** argv)
 
 int kmx_tools_main(int argc, char** argv);      // kmx_tools.cpp: dump, aggregate
 int kmx_filter_main(int argc, char** argv);     // kmx_filter.cpp: filter
+int kmx_query_main(int argc, char** argv);      // kmx_query.cpp: query
 
 int main(int argc, char** argv)
 {
   if (argc >= 2 && std::string(argv[1]) == "filter") { try { return kmx_filter_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "query") { try { return kmx_query_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

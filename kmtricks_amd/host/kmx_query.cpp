@@ -1,0 +1,219 @@
+// kmx_query.cpp -- `kmx query`: which samples of a `--mode hash:bf:bin` run hold the k-mers of a set of sequences (what kmtricks 1.0
+// shipped as `kmtricks query`, doc/changelogs/v1.0.0.md, and kmindex does today; no counterpart in the 1.6.0 tree).  The index is the
+// run directory as `kmx pipeline` / kmtricks leave it; the queries go through kmx_query_host in batches, the partitions' matrices in
+// groups that fit the device, a group's hits added on the device to the table of the groups before it.  Every check that needs no
+// GPU comes before kmx_create.
+#include <kmx.h>
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <thread>
+#include "kmx_io.hpp"
+#include "kmx_run.hpp"
+
+namespace fs = std::filesystem;
+using namespace kmxio;
+
+namespace {
+
+struct QOpt {
+  std::string index, query, out, format = "matrix";
+  double threshold = 0.7;
+  uint32_t gpus = 1, threads = 8;
+  uint64_t batch_mb = 0;      // 0: sized from the device's free memory
+  bool verbose = false;
+};
+
+const char* USAGE = "usage: kmx query --index <run dir made with --mode hash:bf:bin> --query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] "
+                    "[--format matrix|list] [--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
+
+QOpt parse(int argc, char** argv)
+{
+  QOpt o;
+  auto need = [&](int& i) -> std::string { if (i + 1 >= argc) die(std::string("missing value for ") + argv[i] + "\n" + USAGE); return argv[++i]; };
+  auto num = [&](int& i) -> unsigned long { const std::string v = need(i); try { size_t n = 0; const unsigned long x = std::stoul(v, &n); if (n != v.size()) throw 1; return x; } catch (...) { die(std::string("bad number for ") + argv[i - 1] + ": " + v); } };
+  for (int i = 2; i < argc; i++) {
+    const std::string a = argv[i];
+    if (a == "--index") o.index = need(i);
+    else if (a == "--query") o.query = need(i);
+    else if (a == "--output") o.out = need(i);
+    else if (a == "--threshold") { const std::string v = need(i); try { size_t n = 0; o.threshold = std::stod(v, &n); if (n != v.size()) throw 1; } catch (...) { die("bad number for --threshold: " + v); } }
+    else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list") die("--format must be matrix or list"); }
+    else if (a == "--gpus") o.gpus = num(i);
+    else if (a == "--query-batch-mb") o.batch_mb = num(i);
+    else if (a == "-t" || a == "--threads") o.threads = num(i);
+    else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
+    else die("unknown option " + a + "\n" + USAGE);
+  }
+  if (o.index.empty()) die(std::string("--index is required\n") + USAGE);
+  if (o.query.empty()) die(std::string("--query is required\n") + USAGE);
+  if (o.gpus < 1 || o.gpus > 16) die("--gpus must be in [1, 16]");
+  if (o.threshold < 0.0 || o.threshold > 1.0) die("--threshold must be in [0, 1]");
+  return o;
+}
+
+void chk(kmx_ctx* c, int rc, const char* what) { if (rc != KMX_OK) die(std::string(what) + ": " + kmx_last_error(c)); }
+
+// `key=value` of the run's options.txt (cmd/all.hpp:85-125: one line of them)
+std::string option_of(const std::string& line, const std::string& key)
+{
+  const size_t at = line.find(" " + key + "="); if (at == std::string::npos) return "";
+  const size_t b = at + key.size() + 2, e = line.find(',', b);
+  std::string v = line.substr(b, e == std::string::npos ? std::string::npos : e - b);
+  while (!v.empty() && (v.back() == '\n' || v.back() == '\r' || v.back() == ' ')) v.pop_back();
+  return v;
+}
+
+constexpr size_t CMBF_HEADER = 49;
+
+}  // namespace
+
+int kmx_query_main(int argc, char** argv)
+{
+  const QOpt o = parse(argc, argv);
+  // ---- the index: a run directory of --mode hash:bf:bin ----
+  if (!fs::exists(o.index + "/kmtricks.fof")) die(o.index + " is not a kmtricks runtime directory.");
+  std::string opt; { std::ifstream f(o.index + "/options.txt"); if (!f) die("Unable to read at " + o.index + "/options.txt"); std::getline(f, opt); }
+  const std::string mode = option_of(opt, "count_format") + ":" + option_of(opt, "mode") + ":" + option_of(opt, "format");
+  if (mode != "hash:bf:bin") die("kmx query needs a run made with --mode hash:bf:bin; " + o.index + " was made with " + mode);
+  uint32_t k = 0;
+  try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(o.index + "/options.txt names no kmer_size"); }
+  uint64_t W = 0, P = 0; uint32_t msize = 0;
+  { std::vector<uint8_t> hi = slurp(o.index + "/hash.info");
+    if (hi.size() < 36) die(o.index + "/hash.info: Invalid file format.");
+    P = rd<uint64_t>(&hi[8]); W = rd<uint64_t>(&hi[16]); msize = rd<uint32_t>(&hi[32]); }
+  uint16_t rp = 0;
+  const std::vector<uint16_t> table = read_repartition(o.index + "/repartition_gatb/repartition.minimRepart", &rp);
+  if (k < 8 || k > 127 || msize < 4 || msize > 15 || msize >= k || table.size() != ((size_t)1 << (2 * msize)) || P == 0 || P != rp || W == 0)
+    die("the index's options.txt, hash.info and repartition table do not fit together");
+  for (uint16_t t : table) if (t >= P) die("the index's repartition table names a partition the run does not have");
+  const std::vector<Sample> samples = parse_fof(o.index + "/kmtricks.fof", 1);
+  const uint32_t N = (uint32_t)samples.size(), nb = (N + 7) / 8;
+  const uint64_t body = W * nb;
+  std::vector<std::string> files(P);
+  for (uint64_t p = 0; p < P; p++) {
+    files[p] = o.index + "/matrices/matrix_" + std::to_string(p) + ".cmbf";
+    std::ifstream f(files[p], std::ios::binary);
+    uint8_t h[CMBF_HEADER];
+    if (!f || !f.read((char*)h, CMBF_HEADER)) die("Unable to read at " + files[p]);
+    if (rd<uint64_t>(&h[0]) != MAGIC_BASE || rd<uint64_t>(&h[13]) != MAGIC_BITMATRIX) die("Invalid file format: " + files[p]);
+    if (rd<uint32_t>(&h[21]) != N) die(files[p] + " has rows of " + std::to_string(rd<uint32_t>(&h[21])) + " bits, the index's kmtricks.fof has " + std::to_string(N) + " samples");
+    if (rd<uint64_t>(&h[25]) != W * p || rd<uint64_t>(&h[33]) != W) die(files[p] + ": its window disagrees with the index's hash.info");
+    std::error_code ec;
+    if (fs::file_size(files[p], ec) != CMBF_HEADER + body || ec) die("truncated matrix (its body is not " + std::to_string(W) + " rows): " + files[p]);
+  }
+
+  // ---- the queries ----
+  std::string bases; std::vector<uint64_t> offs{0}; std::vector<std::string> names;
+  { SeqReader rd(o.query); rd.keep_names(); std::string seq; while (rd.next(seq)) { bases += seq; offs.push_back(bases.size()); names.push_back(rd.name()); } }
+  const uint64_t Q = names.size();
+  FILE* out = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
+  if (!out) die("Unable to write at " + o.out);
+
+  // ---- devices; how many bases a batch of queries holds and how many partitions a group (kmx_device_memory, or --query-batch-mb) ----
+  if (kmx_version() != KMX_VERSION) die("libkmx.so is not the version this driver was built for");
+  const uint32_t G = o.gpus, ndev = (uint32_t)std::max(1, kmx_device_count());
+  std::vector<kmx_ctx*> ctxs(G, nullptr);
+  for (uint32_t g = 0; g < G; g++) if (kmx_create((int)(g % ndev), &ctxs[g]) != KMX_OK) die(std::string("kmx_create: ") + kmx_last_error(nullptr));
+  uint64_t budget = o.batch_mb << 20;
+  if (!budget) {
+    uint64_t fr = 0, tot = 0;
+    for (uint32_t g = 0; g < std::min(G, ndev); g++) { uint64_t f = 0; if (kmx_device_memory((int)g, &f, &tot) == KMX_OK && (g == 0 || f < fr)) fr = f; }
+    budget = std::max<uint64_t>(fr / 10 * 6 / std::max<uint32_t>(1, (G + ndev - 1) / ndev), 64ull << 20);
+  }
+  // half for a group's matrices, half for a batch: 17 bytes a base (the bases, 16 of scratch) and a row of the table a query.  A
+  // call's scratch and uploads go back to the context's pool when it has been waited for, so the accumulating first result of a
+  // batch holds its table and n_kmers only while the later groups run
+  const uint64_t group_parts = std::max<uint64_t>(1, (budget / 2) / std::max<uint64_t>(body, 1));
+  const uint64_t batch_bytes = std::max<uint64_t>(budget / 2, 1);
+  std::vector<uint64_t> cut{0};      // batch b = queries [cut[b], cut[b + 1])
+  { uint64_t used = 0;
+    for (uint64_t q = 0; q < Q; q++) {
+      const uint64_t len = offs[q + 1] - offs[q], cost = 17 * len + 4ull * N + 12;
+      if (len > 0xFFFFFFFFull) die("query " + names[q] + " has 2^32 bases or more");
+      if (q > cut.back() && (used + cost > batch_bytes || offs[q + 1] - offs[cut.back()] > 0xFFFFFFFFull)) { cut.push_back(q); used = 0; }
+      used += cost;
+    }
+    cut.push_back(Q); if (Q == 0) cut.pop_back(); }
+  std::vector<std::vector<std::vector<uint32_t>>> groups(G);      // per shard: its partitions (p mod G) in groups
+  size_t n_groups = 0;
+  for (uint64_t p = 0; p < P; p++) { auto& gs = groups[p % G]; if (gs.empty() || gs.back().size() >= group_parts) gs.emplace_back(); gs.back().push_back((uint32_t)p); }
+  for (auto& gs : groups) n_groups = std::max(n_groups, gs.size());
+  if (o.verbose) fprintf(stderr, "[kmx query] %llu queries, %zu bases, k %u, %u samples, %llu partitions of %llu rows: %zu query batches, %zu partition groups a shard, %u shards\n",
+                         (unsigned long long)Q, bases.size(), k, N, (unsigned long long)P, (unsigned long long)W, cut.size() - 1, n_groups, G);
+
+  if (o.format == "matrix") { std::string h = "query\tn_kmers"; for (const Sample& s : samples) { h += '\t'; h += s.id; } h += '\n'; fwrite(h.data(), 1, h.size(), out); }
+  // a shard whose partitions fit one group reads its matrices once; a shard with several groups reads every group again for every
+  // batch of queries (the index does not fit the device, and is not assumed to fit the host either: DESIGN section 11)
+  std::vector<std::vector<std::vector<uint8_t>>> kept(G);
+  for (size_t b = 0; b + 1 < cut.size(); b++) {
+    const uint64_t q0 = cut[b], nq = cut[b + 1] - q0;
+    std::vector<uint64_t> boffs(nq + 1);
+    for (uint64_t i = 0; i <= nq; i++) boffs[i] = offs[q0 + i] - offs[q0];
+    std::vector<uint32_t> hits(nq * N, 0), kmers(nq, 0);
+    std::mutex mu;
+    // every shard sees all queries of the batch; its groups add up on its device, the shards' tables on the host
+    auto shard = [&](uint32_t g) {
+      try {
+        kmx_ctx* ctx = ctxs[g];
+        kmx_query_result* first = nullptr;
+        std::vector<std::vector<uint8_t>> own;
+        const bool keep = groups[g].size() == 1;
+        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+        std::vector<const uint8_t*> rows(P);
+        std::vector<uint32_t> sk(nq);
+        for (size_t gi = 0; gi < groups[g].size(); gi++) {
+          std::fill(rows.begin(), rows.end(), nullptr);
+          const bool loaded = keep && bodies.size() == groups[g][gi].size();
+          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+          for (size_t i = 0; i < groups[g][gi].size(); i++) {
+            const uint32_t p = groups[g][gi][i];
+            if (!loaded) {
+              std::ifstream f(files[p], std::ios::binary);
+              bodies[i].resize(body);
+              if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
+            }
+            rows[p] = bodies[i].data();
+          }
+          kmx_query_task t; memset(&t, 0, sizeof t);
+          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
+          t.rows = rows.data(); t.hits = first ? kmx_query_result_hits_dev(first) : nullptr;
+          kmx_query_result* r = nullptr;
+          chk(ctx, kmx_query_host(ctx, &t, &r), "kmx_query_host");
+          chk(ctx, kmx_query_result_wait(r), "kmx_query");      // (the bodies are reused by the next group)
+          if (!first) first = r; else kmx_query_result_free(r);
+        }
+        if (!first) return;      // (more shards than partitions)
+        std::vector<uint32_t> sh(nq * N);
+        chk(ctx, kmx_query_result_copy_hits(first, sh.data(), sh.size()), "kmx_query_result_copy_hits");
+        chk(ctx, kmx_query_result_copy_kmers(first, sk.data(), sk.size()), "kmx_query_result_copy_kmers");
+        kmx_query_result_free(first);
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+        kmers = sk;      // (every shard walks every query: the same numbers)
+      } catch (const std::exception& e) { die(e.what()); }
+    };
+    std::vector<std::thread> workers;
+    for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
+    shard(0);
+    for (std::thread& w : workers) w.join();
+    std::string txt;
+    for (uint64_t i = 0; i < nq; i++) {
+      const std::string& name = names[q0 + i];
+      if (o.format == "matrix") {
+        txt += name; txt += '\t'; txt += std::to_string(kmers[i]);
+        for (uint32_t c = 0; c < N; c++) { txt += '\t'; txt += std::to_string(hits[i * N + c]); }
+        txt += '\n';
+      } else if (kmers[i] > 0) {
+        for (uint32_t c = 0; c < N; c++)
+          if ((double)hits[i * N + c] >= o.threshold * (double)kmers[i])
+            txt += name + '\t' + samples[c].id + '\t' + std::to_string(hits[i * N + c]) + '\t' + std::to_string(kmers[i]) + '\n';
+      }
+    }
+    if (fwrite(txt.data(), 1, txt.size(), out) != txt.size()) die("write failed: " + (o.out.empty() ? std::string("stdout") : o.out));
+  }
+  if (out != stdout) { if (fclose(out) != 0) die("write failed: " + o.out); } else fflush(stdout);
+  for (uint32_t g = 0; g < G; g++) kmx_destroy(ctxs[g]);
+  return 0;
+}

@@ -46,6 +46,12 @@ class KmxCombineTask(C.Structure):
 COMBINE_DROP_LAST, COMBINE_MAX_BLOCKS = 1, 64
 
 
+class KmxQueryTask(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("kmer_size", C.c_uint32),
+                ("minim_size", C.c_uint32), ("repart", C.c_void_p), ("nb_parts", C.c_uint32), ("n_cols", C.c_uint32),
+                ("window", C.c_uint64), ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -182,6 +188,20 @@ _lib.kmx_combine_result_copy_body.argtypes = [_vp, _vp, C.c_uint64]
 _lib.kmx_combine_result_kernel_ms.restype = C.c_double
 _lib.kmx_combine_result_kernel_ms.argtypes = [_vp]
 _lib.kmx_combine_result_free.argtypes = [_vp]
+
+_lib.kmx_query_dev.argtypes = [_vp, C.POINTER(KmxQueryTask), C.POINTER(_vp)]
+_lib.kmx_query_host.argtypes = [_vp, C.POINTER(KmxQueryTask), C.POINTER(_vp)]
+_lib.kmx_query_result_wait.argtypes = [_vp]
+for _f in ("kmx_query_result_n_seqs", "kmx_query_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_query_result_copy_kmers", "kmx_query_result_copy_hits"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_query_result_hits_dev.restype = _vp
+_lib.kmx_query_result_hits_dev.argtypes = [_vp]
+_lib.kmx_query_result_kernel_ms.restype = C.c_double
+_lib.kmx_query_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_query_result_free.argtypes = [_vp]
 
 
 def filter_want(want):
@@ -596,6 +616,51 @@ class Context:
         finally:
             r.free()
 
+    def query(self, reads, k, m, repart, window, n_cols, matrices, hits_dev=None, keep=False):
+        """kmx_query_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
+        .cmbf (bytes or a uint8 array of window * ceil(n_cols / 8) bytes) or None (the partition is not part of the call);
+        hits_dev None or a device pointer to a uint32 table [queries, n_cols] the call adds to.
+        -> QueryOutput (numpy copies), or with keep the QueryResult itself (the table left in HBM; .free() it)"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        rep = np.ascontiguousarray(repart, dtype=np.uint16)
+        nb = (n_cols + 7) // 8
+        keepalive, rows = [], (C.c_void_p * len(matrices))()
+        for p, mt in enumerate(matrices):
+            if mt is None:
+                continue
+            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+            if len(a) != window * nb:
+                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
+            keepalive.append(a)
+            rows[p] = a.ctypes.data
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        t = KmxQueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows, hits_dev)
+        res = _vp()
+        self._check(_lib.kmx_query_host(self._h, C.byref(t), C.byref(res)), "kmx_query_host")
+        r = QueryResult(self, res, n_cols)
+        r.wait()      # (the host buffers above may go once the call has run)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def query_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, window, n_cols, rows_dev, hits_dev=None, keep=False):
+        """kmx_query_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
+        repartition table; rows_dev[p] a device pointer to partition p's matrix body or None.  -> as query"""
+        rows = (C.c_void_p * len(rows_dev))(*rows_dev)
+        t = KmxQueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, window, rows, hits_dev)
+        res = _vp()
+        self._check(_lib.kmx_query_dev(self._h, C.byref(t), C.byref(res)), "kmx_query_dev")
+        r = QueryResult(self, res, n_cols)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
 
     @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
@@ -684,6 +749,53 @@ class CombineResult:
     def free(self):
         if self._h:
             _lib.kmx_combine_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class QueryOutput:
+    """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose row has the sample's bit set
+    (the table the call added to, when one was given); kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_kmers, hits, kernel_ms, algo_bytes):
+        self.n_kmers, self.hits, self.kernel_ms, self.algo_bytes = n_kmers, hits, kernel_ms, algo_bytes
+
+
+class QueryResult:
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_query_result_wait(self._h), "kmx_query_result_wait")
+
+    def n_seqs(self):
+        return _lib.kmx_query_result_n_seqs(self._h)
+
+    def hits_dev(self):
+        return _lib.kmx_query_result_hits_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_query_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_query_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        q = self.n_seqs()
+        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
+        self._ctx._check(_lib.kmx_query_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_query_result_copy_kmers")
+        self._ctx._check(_lib.kmx_query_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_query_result_copy_hits")
+        return QueryOutput(nk, hits, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_query_result_free(self._h)
             self._h = None
 
     def __del__(self):
