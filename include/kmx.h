@@ -24,6 +24,8 @@
  *                               one partition's matrix rows joined with the new sample's count list
  *   kmx_query_dev / _host       no counterpart in the 1.6.0 tree (kmtricks 1.0's `kmtricks query`): query sequences against the .cmbf
  *                               matrices of a hash:bf:bin run, addressed as kmer_hash.hpp:244-328 and repartition.hpp:94-103 publish
+ *   kmx_kquery_dev / _host      no counterpart either: query sequences against the .count / .pa k-mer matrices of a kmer:count:bin /
+ *                               kmer:pa:bin run -- exact, with abundances (k-mer, minimizer and partition as kmx_query_* has them)
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -393,6 +395,68 @@ double   kmx_query_result_kernel_ms(kmx_query_result* r);
  * + the hits table written */
 uint64_t kmx_query_result_algo_bytes(kmx_query_result* r);
 void     kmx_query_result_free(kmx_query_result* r);
+
+/* ----------------------------------------------------------------- kquery */
+
+/* Which samples of a K-MER matrix hold the k-mers of a query sequence, and how often: exact, where kmx_query_* answers from Bloom
+ * matrices.  The index: the .count / .pa bodies of a `--mode kmer:count:bin` / `kmer:pa:bin` run -- partition p has n_rows[p] rows in
+ * file order, keys strictly ascending (most significant word first), a row laid out as in the filter section above: key_words * 8 key
+ * bytes (low word first), then 4 * n_cols bytes of u32 counts (KMX_MODE_COUNT) or ceil(n_cols / 8) bytes, column i = bit i & 7 of byte
+ * i >> 3 (KMX_MODE_PA).  For every query q and every position whose k bases are all ACGT (either case) and whose k-mer ends inside
+ * the query: c = the canonical k-mer, p = repart[minimizer(c)], both exactly as the query section defines them.  Results:
+ *   n_kmers[q]           the number of such positions
+ *   hits[q * n_cols + i] (u32) the number of them for which c is the key of a row of partition p and that row's count i is non-zero
+ *                        (COUNT) or its bit i is set (PA)
+ *   sums[q * n_cols + i] (u64; COUNT, with want_sums) the sum of that row's count i over the same positions
+ * Every occurrence counts; the padding bits of a PA row never reach a result; a query without a valid k-mer has zeros and is still
+ * reported.  rows: a HOST array of nb_parts pointers; NULL = the partition is not part of this call (its k-mers count in n_kmers and
+ * add nothing else; n_rows[p] is not read).  n_rows: a HOST array in both calls.  hits / sums: NULL (the result owns a zeroed table;
+ * sums only with want_sums), or DEVICE tables of n_seqs * n_cols entries that the call ADDS to: the partition groups of one set of
+ * queries accumulate on the device (integer adds commute: the tables do not depend on order).
+ * LIMITS, each refused before any GPU work: 8 <= kmer_size <= 127, 4 <= minim_size <= 15 and < kmer_size, key_words == ceil(kmer_size
+ * / 32), 1 <= nb_parts <= 65535, n_cols >= 1, mode COUNT or PA, want_sums (or a sums table) with PA, a sums table without want_sums
+ * (KMX_E_INVAL); fewer than 2^31 queries and fewer than 2^32 bases a call, at most 2^32 - 256 rows a partition, a row below 4 GiB,
+ * the Bloom modes -- and hash matrices, which no field tells apart: they are not k-mer matrices -- (KMX_E_UNSUPPORTED).
+ * Scratch from the context's pool: 10 + 8 * key_words bytes a base (the partition, the canonical words, one record). */
+typedef struct {
+  const char*     bases;
+  const uint64_t* offsets;      /* [n_seqs + 1], offsets[0] = 0 */
+  uint64_t        n_seqs;
+  uint32_t        kmer_size, minim_size;
+  const uint16_t* repart;       /* u16[4^minim_size]: minimizer -> partition */
+  uint32_t        nb_parts;
+  uint32_t        n_cols;       /* N: samples of the matrix */
+  uint32_t        key_words;    /* ceil(kmer_size / 32) */
+  uint32_t        mode;         /* KMX_MODE_COUNT | KMX_MODE_PA */
+  const uint64_t* n_rows;       /* HOST [nb_parts]: rows of every partition's matrix */
+  const uint8_t* const* rows;   /* HOST [nb_parts] */
+  uint32_t*       hits;         /* NULL, or a device table to accumulate into */
+  uint64_t*       sums;         /* NULL, or (with want_sums) a device table to accumulate into */
+  uint32_t        want_sums;    /* non-zero: the sums are computed (KMX_MODE_COUNT only) */
+} kmx_kquery_task;
+
+typedef struct kmx_kquery_result kmx_kquery_result;
+
+/* bases, offsets, repart and every rows[p] DEVICE pointers.  The kernels are queued on the context's stream (kmx_stream) and the call
+ * returns; it reads offsets[n_seqs] back first (8 bytes: the grid's size).  The results stay in HBM until they are freed. */
+int kmx_kquery_dev(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out);
+/* HOST pointers (hits and sums, when given, are still device tables): everything is uploaded on a stream of its own.  The host
+ * buffers may be reused once kmx_kquery_result_wait has returned. */
+int kmx_kquery_host(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out);
+int      kmx_kquery_result_wait(kmx_kquery_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t kmx_kquery_result_n_seqs(const kmx_kquery_result* r);
+int      kmx_kquery_result_copy_kmers(kmx_kquery_result* r, uint32_t* host_dst, uint64_t dst_entries);   /* n_seqs entries */
+int      kmx_kquery_result_copy_hits(kmx_kquery_result* r, uint32_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols: the table as it stands */
+int      kmx_kquery_result_copy_sums(kmx_kquery_result* r, uint64_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols; KMX_E_INVAL without want_sums */
+uint32_t* kmx_kquery_result_hits_dev(kmx_kquery_result* r);
+uint64_t* kmx_kquery_result_sums_dev(kmx_kquery_result* r);     /* NULL without want_sums */
+/* duration in ms of the call's kernels, the clearing of their tables included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_kquery_result_kernel_ms(kmx_kquery_result* r);
+/* algorithmic bytes: the bases read + one row (key and payload) per k-mer that met a row + the probes' keys (8 * key_words per valid
+ * k-mer) + the tables written */
+uint64_t kmx_kquery_result_algo_bytes(kmx_kquery_result* r);
+void     kmx_kquery_result_free(kmx_kquery_result* r);
 
 /* ------------------------------------------------------------------ count */
 

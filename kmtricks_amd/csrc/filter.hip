@@ -20,20 +20,6 @@ constexpr u32 FT_TILE = 256;           // rows of a match tile = threads of a wo
 constexpr u32 FT_LDS_DW = 4096;        // dwords of key records staged per tile (16 KB)
 constexpr u32 FT_MAX_GRID = 1u << 18;  // workgroups of a launch: every kernel strides over its work
 
-// a row's key: rows of a PA matrix start at any byte
-template <int KW> __device__ __forceinline__ Key<KW> load_row_key(const u8* p) {
-  if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) return load_key<KW>(p);
-  Key<KW> k;
-#pragma unroll
-  for (int i = 0; i < KW; i++) {
-    u64 w = 0;
-#pragma unroll
-    for (int b = 0; b < 8; b++) w |= (u64)p[8 * i + b] << (8 * b);
-    k.w[i] = w;
-  }
-  return k;
-}
-
 // first record of recs[lo, hi) whose key is not below k (UPPER: is above k); recs in global memory or LDS
 template <int KW, bool UPPER> __device__ __forceinline__ u32 ft_bound(const u8* recs, u32 lo, u32 hi, const Key<KW>& k) {
   constexpr u32 RB = KW * 8 + 4;

@@ -1,5 +1,5 @@
 // kmer_dev.hpp -- the device code that says what a k-mer's minimizer and window hash ARE, shared by the kernels that must agree on
-// them: the split (superk.hip), the count path (count.hip) and the query (query.hip).  One definition each, no copies.
+// them: the split (superk.hip), the count path (count.hip) and the queries (query.hip, kquery.hip).  One definition each, no copies.
 #pragma once
 #include "kmx_dev.hpp"
 
@@ -71,6 +71,126 @@ __device__ __forceinline__ u64 xxh64_words(const u64* w, int nw)
   }
   h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
   return h;
+}
+
+// ---- the walk over a stream of query sequences (query.hip, kquery.hip): tiles of 64 positions, a wave a run of tiles, a lane a position ----
+constexpr u32 QK_BLOCK = 256;          // threads of a workgroup of the key / scatter walk: four chunks
+
+// bit i of y -> bit 2i (i < 32)
+__device__ __forceinline__ u64 spread32(u32 y) { return (u64)spread16(y & 0xFFFFu) | ((u64)spread16(y >> 16) << 32); }
+// bits [32 w, 32 w + 32) of the 128 bits (lo, hi)
+__device__ __forceinline__ u32 q_bits32(u64 lo, u64 hi, int w) { return w == 0 ? (u32)lo : w == 1 ? (u32)(lo >> 32) : w == 2 ? (u32)hi : (u32)(hi >> 32); }
+// the low k bits of (lo, hi) in reverse order (bit i <- bit k - 1 - i), 1 <= k <= 127; the bits from k on are zero in and out
+__device__ __forceinline__ void q_rev(u64 lo, u64 hi, int k, u64& rlo, u64& rhi)
+{
+  const u64 RL = __brevll(hi), RH = __brevll(lo);      // the 128 bits reversed: RH:RL
+  const int sft = 128 - k;                             // 1 .. 127
+  if (sft >= 64) { rlo = RH >> (sft - 64); rhi = 0; }
+  else { rlo = (RL >> sft) | (RH << (64 - sft)); rhi = RH >> sft; }
+}
+
+// the query that holds position pos: the greatest q in [lo, hi) with offsets[q] <= pos (offsets[lo] <= pos < offsets[hi]; empty
+// queries share their offset with the one behind them and are skipped)
+__device__ __forceinline__ u32 q_query_of(const u64* __restrict__ offsets, u32 lo, u32 hi, u64 pos)
+{
+  while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (offsets[mid] <= pos) lo = mid; else hi = mid; }
+  return lo;
+}
+// ... for the 64 positions of the tile at t0, given a query qs at or in front of position t0's: a gallop finds the first query behind the tile
+__device__ __forceinline__ u32 q_tile_query(const u64* __restrict__ offsets, u32 n_seqs, u32 qs, u64 t0, u64 pos)
+{
+  const u64 last = t0 + 63;
+  u32 step = 1, hi = qs + 1;
+  while (hi < n_seqs && offsets[hi] <= last) { step <<= 1; hi = n_seqs - qs > step ? qs + step : n_seqs; }      // (uniform over the wave)
+  return q_query_of(offsets, qs, hi, pos);
+}
+
+struct QChunks { u32 n_tiles, n_chunks, tiles_per_chunk; };
+
+// what a walk needs of (k, m), worked out once a wave
+struct QWalk { int k, m, nbm; u32 mmask; u64 klo, khi; };
+__device__ __forceinline__ QWalk q_walk(int k, int m)
+{
+  QWalk w;
+  w.k = k; w.m = m;
+  w.nbm = k - m + 1;                               // m-mers of a k-mer: 1 .. 124
+  w.mmask = (1u << m) - 1;
+  w.klo = k >= 64 ? ~0ULL : (1ULL << k) - 1ULL; w.khi = k > 64 ? (1ULL << (k - 64)) - 1ULL : 0ULL;
+  return w;
+}
+
+// the k-mer at position pos = tile + lane, by the whole wave: the bases of the tile and of the 192 behind it become ballot bit planes,
+// a lane's k-mer is k bits of each plane at its own position.  -> cw: the canonical k-mer's words, mini: its minimizer (the window
+// minimum of mmer_value); returns whether its k bases are all ACGT (cw and mini mean nothing otherwise)
+template <int KW>
+__device__ __forceinline__ bool q_tile_kmer(const char* __restrict__ bases, u64 n_bases, u64 pos, int lane, const QWalk& wk, u64 (&cw)[KW], u32& mini)
+{
+  const int k = wk.k, m = wk.m, nbm = wk.nbm;
+  const u32 mmask = wk.mmask;
+  const u64 klo = wk.klo, khi = wk.khi;
+  u8 cc[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) cc[i] = pos + 64u * i < n_bases ? (u8)bases[pos + 64u * i] : (u8)'N';
+  u64 I[3], A[4], B[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) { if (i < 3) I[i] = __ballot(!nt_valid(cc[i])); A[i] = __ballot((cc[i] >> 1) & 1); B[i] = __ballot((cc[i] >> 2) & 1); }
+  auto fun = [&](u64 x, u64 y) { return lane ? (x >> lane) | (y << (64 - lane)) : x; };
+  const u64 fi_lo = fun(I[0], I[1]), fi_hi = fun(I[1], I[2]);
+  const u64 fa_lo = fun(A[0], A[1]), fa_hi = fun(A[1], A[2]), fa_2 = fun(A[2], A[3]);
+  const u64 fb_lo = fun(B[0], B[1]), fb_hi = fun(B[1], B[2]), fb_2 = fun(B[2], B[3]);
+  // ---- the minimizer: the minimum of the m-mer values at positions lane .. lane + nbm - 1 of the 192 at hand ----
+  auto mval = [&](u64 a, u64 b) {      // the m-mer that starts at bit 0 of (a, b): base j is digit m-1-j
+    const u32 y0 = __brev((u32)a & mmask) >> (32 - m), y1 = __brev((u32)b & mmask) >> (32 - m);
+    return mmer_value(spread16(y0) | (spread16(y1) << 1), m);
+  };
+  u32 v0 = mval(fa_lo, fb_lo), v1 = mval(fa_hi, fb_hi), v2 = mval(fa_2, fb_2);      // positions lane, 64 + lane, 128 + lane
+  int span = 1;                                                                      // v holds the minimum over `span` positions
+#pragma unroll
+  for (int d = 1; d <= 32; d <<= 1) {
+    if (2 * d > nbm) break;                                                          // (uniform)
+    const u32 n0 = min(v0, sk_at(v0, v1, d, lane)), n1 = min(v1, sk_at(v1, v2, d, lane)), n2 = min(v2, sk_at(v2, 0xFFFFFFFFu, d, lane));
+    v0 = n0; v1 = n1; v2 = n2; span = 2 * d;
+  }
+  // (span <= nbm < 2 span, or span = 64 and nbm <= 124: two spans cover the window; the second starts nbm - span < 64 positions on)
+  mini = nbm > span ? min(v0, sk_at(v0, v1, nbm - span, lane)) : v0;
+  // ---- the canonical k-mer: digit i is base k - 1 - i (A0 C1 T2 G3: plane A the low bit, plane B the high one) ----
+  const u64 a_lo = fa_lo & klo, a_hi = fa_hi & khi, b_lo = fb_lo & klo, b_hi = fb_hi & khi;
+  u64 ra_lo, ra_hi, rb_lo, rb_hi;
+  q_rev(a_lo, a_hi, k, ra_lo, ra_hi); q_rev(b_lo, b_hi, k, rb_lo, rb_hi);
+  const u64 nb_lo = ~b_lo & klo, nb_hi = ~b_hi & khi;      // the reverse complement's digit i is base i ^ 2
+  u64 f[KW], r[KW];
+#pragma unroll
+  for (int w = 0; w < KW; w++) {
+    f[w] = spread32(q_bits32(ra_lo, ra_hi, w)) | (spread32(q_bits32(rb_lo, rb_hi, w)) << 1);
+    r[w] = spread32(q_bits32(a_lo, a_hi, w)) | (spread32(q_bits32(nb_lo, nb_hi, w)) << 1);
+  }
+  bool less = false, decided = false;
+#pragma unroll
+  for (int w = KW - 1; w >= 0; w--) if (!decided && f[w] != r[w]) { less = f[w] < r[w]; decided = true; }
+#pragma unroll
+  for (int w = 0; w < KW; w++) cw[w] = less ? f[w] : r[w];
+  return (fi_lo & klo) == 0 && (fi_hi & khi) == 0;
+}
+
+// the tile's adds: one per partition of the tile to its (partition, chunk) counter, one per query to n_kmers[query]
+__device__ __forceinline__ void q_tile_adds(bool valid, u32 part, u32 q, int lane, u32* __restrict__ hist, u32 n_chunks, u32 c, u32* __restrict__ n_kmers)
+{
+  u64 vm = __ballot(valid);
+  while (vm) {      // one add per partition of the tile (neighbouring k-mers share their minimizer: a handful)
+    const int l = __builtin_ctzll(vm);
+    const u32 pp = (u32)__shfl((int)part, l);
+    const u64 same = __ballot(valid && part == pp);
+    if (lane == l) atomicAdd(&hist[(size_t)pp * n_chunks + c], (u32)__popcll(same));
+    vm &= ~same;
+  }
+  vm = __ballot(valid);
+  while (vm) {      // one add per query of the tile
+    const int l = __builtin_ctzll(vm);
+    const u32 qq = (u32)__shfl((int)q, l);
+    const u64 same = __ballot(valid && q == qq);
+    if (lane == l) atomicAdd(&n_kmers[qq], (u32)__popcll(same));
+    vm &= ~same;
+  }
 }
 
 }  // namespace kmx

@@ -114,6 +114,20 @@ template <int KW> __device__ __forceinline__ Key<KW> load_key(const u8* p) {
   return k;
 }
 
+// a row's key: rows of a PA matrix start at any byte
+template <int KW> __device__ __forceinline__ Key<KW> load_row_key(const u8* p) {
+  if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) return load_key<KW>(p);
+  Key<KW> k;
+#pragma unroll
+  for (int i = 0; i < KW; i++) {
+    u64 w = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) w |= (u64)p[8 * i + b] << (8 * b);
+    k.w[i] = w;
+  }
+  return k;
+}
+
 // ---- wave helpers -------------------------------------------------------------------------------
 __device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
   u32 lo = __shfl_xor((u32)v, m), hi = __shfl_xor((u32)(v >> 32), m);

@@ -102,6 +102,19 @@ hipError_t launch_query_scatter(const u64* keys, const u64* offsets, u32 n_seqs,
                                 u32* cell, u64* recs, hipStream_t st);
 hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
                                u32* hits, u32 n_cu, hipStream_t st);
+// ... over the presence/absence rows of a k-mer matrix: a record's row lies at row * stride + skip, nb bytes; a record of row 0xFFFFFFFF met none
+hipError_t launch_query_gather_keyed(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u64 stride, u32 skip,
+                                     u32 nb, u32 n_cols, u32* hits, u32 n_cu, hipStream_t st);
+// kquery.hip: query sequences against the k-mer matrices of a run (kmx_kquery_dev); the scan and launch_query_parts sort its records too
+hipError_t launch_kquery_keys(int kw, const char* bases, const u64* offsets, u32 n_seqs, u64 n_bases, int k, int m, const u16* repart,
+                              u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk, u16* parts /* [n_bases] */, u64* words /* [kw][n_bases] */,
+                              u32* hist /* [n_parts][n_chunks] + 1, zeroed */, u32* n_kmers /* zeroed */, hipStream_t st);
+hipError_t launch_kquery_scatter(const u16* parts, const u64* offsets, u32 n_seqs, u64 n_bases, u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk,
+                                 u32* cell, u64* recs, hipStream_t st);
+hipError_t launch_kquery_search(int kw, u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, const u32* n_rows,
+                                u64 stride, const u64* words, u64 n_bases, u32* n_found /* zeroed */, u32 n_cu, hipStream_t st);
+hipError_t launch_kquery_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u64 stride, u32 skip,
+                                u32 n_cols, u32* hits, u64* sums /* or null */, u32 n_cu, hipStream_t st);
 
 }  // namespace kmx
 

@@ -5,7 +5,8 @@
 //   k_query_keys     the concatenated base stream is cut in tiles of 64 positions, a WAVE takes a run of tiles (a chunk), a lane one
 //                    position: the bases of the tile and of the 192 behind it become ballot bit planes, a lane's k-mer is k bits of
 //                    each plane at its own position -- canonical form by bit reversal, minimizer = window minimum of mmer_value
-//                    (a sparse table over the 192 m-mer values, wave shuffles), row = XXH64(words) % window.  The query of a position
+//                    (a sparse table over the 192 m-mer values, wave shuffles; q_tile_kmer in kmer_dev.hpp, shared with kquery.hip),
+//                    row = XXH64(words) % window.  The query of a position
 //                    is a search of `offsets`, bounded by a gallop from the query of the tile before.  Per valid position one u64
 //                    (partition << 32 | row) at the position's own slot; one add per partition of the tile to its (partition, chunk)
 //                    counter and one per query to n_kmers[query].
@@ -24,41 +25,10 @@
 
 namespace kmx {
 
-constexpr u32 QK_BLOCK = 256;          // threads of a workgroup of the key / scatter walk: four chunks
 constexpr u32 QG_PLANES = 6;           // bit-sliced counter planes: column sums up to 63
 constexpr u32 QG_RUN = 63;             // records of a gather item: what the planes hold without a flush
 constexpr u64 QK_NONE = ~0ULL;
-
-// bit i of y -> bit 2i (i < 32)
-__device__ __forceinline__ u64 spread32(u32 y) { return (u64)spread16(y & 0xFFFFu) | ((u64)spread16(y >> 16) << 32); }
-// bits [32 w, 32 w + 32) of the 128 bits (lo, hi)
-__device__ __forceinline__ u32 q_bits32(u64 lo, u64 hi, int w) { return w == 0 ? (u32)lo : w == 1 ? (u32)(lo >> 32) : w == 2 ? (u32)hi : (u32)(hi >> 32); }
-// the low k bits of (lo, hi) in reverse order (bit i <- bit k - 1 - i), 1 <= k <= 127; the bits from k on are zero in and out
-__device__ __forceinline__ void q_rev(u64 lo, u64 hi, int k, u64& rlo, u64& rhi)
-{
-  const u64 RL = __brevll(hi), RH = __brevll(lo);      // the 128 bits reversed: RH:RL
-  const int sft = 128 - k;                             // 1 .. 127
-  if (sft >= 64) { rlo = RH >> (sft - 64); rhi = 0; }
-  else { rlo = (RL >> sft) | (RH << (64 - sft)); rhi = RH >> sft; }
-}
-
-// the query that holds position pos: the greatest q in [lo, hi) with offsets[q] <= pos (offsets[lo] <= pos < offsets[hi]; empty
-// queries share their offset with the one behind them and are skipped)
-__device__ __forceinline__ u32 q_query_of(const u64* __restrict__ offsets, u32 lo, u32 hi, u64 pos)
-{
-  while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (offsets[mid] <= pos) lo = mid; else hi = mid; }
-  return lo;
-}
-// ... for the 64 positions of the tile at t0, given a query qs at or in front of position t0's: a gallop finds the first query behind the tile
-__device__ __forceinline__ u32 q_tile_query(const u64* __restrict__ offsets, u32 n_seqs, u32 qs, u64 t0, u64 pos)
-{
-  const u64 last = t0 + 63;
-  u32 step = 1, hi = qs + 1;
-  while (hi < n_seqs && offsets[hi] <= last) { step <<= 1; hi = n_seqs - qs > step ? qs + step : n_seqs; }      // (uniform over the wave)
-  return q_query_of(offsets, qs, hi, pos);
-}
-
-struct QChunks { u32 n_tiles, n_chunks, tiles_per_chunk; };
+constexpr u32 QG_NO_ROW = 0xFFFFFFFFu; // keyed gather: the record's k-mer is no row's key (a partition has at most 2^32 - 256 rows)
 
 template <int KW>
 __global__ __launch_bounds__(QK_BLOCK)
@@ -70,77 +40,20 @@ void k_query_keys(const char* __restrict__ bases, const u64* __restrict__ offset
   if (c >= ch.n_chunks) return;
   const u32 tile0 = c * ch.tiles_per_chunk, tile1 = min(tile0 + ch.tiles_per_chunk, ch.n_tiles);
   if (tile0 >= tile1) return;
-  const int nbm = k - m + 1;                       // m-mers of a k-mer: 1 .. 124
-  const u32 mmask = (1u << m) - 1;
-  const u64 klo = k >= 64 ? ~0ULL : (1ULL << k) - 1ULL, khi = k > 64 ? (1ULL << (k - 64)) - 1ULL : 0ULL;
+  const QWalk wk = q_walk(k, m);
   u32 qs = q_query_of(offsets, 0, n_seqs, (u64)tile0 * 64);      // (position tile0 * 64 < n_bases = offsets[n_seqs])
   for (u32 t = tile0; t < tile1; t++) {
     const u64 t0 = (u64)t * 64, pos = t0 + lane;
-    u8 cc[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) cc[i] = pos + 64u * i < n_bases ? (u8)bases[pos + 64u * i] : (u8)'N';
-    u64 I[3], A[4], B[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { if (i < 3) I[i] = __ballot(!nt_valid(cc[i])); A[i] = __ballot((cc[i] >> 1) & 1); B[i] = __ballot((cc[i] >> 2) & 1); }
-    auto fun = [&](u64 x, u64 y) { return lane ? (x >> lane) | (y << (64 - lane)) : x; };
-    const u64 fi_lo = fun(I[0], I[1]), fi_hi = fun(I[1], I[2]);
-    const u64 fa_lo = fun(A[0], A[1]), fa_hi = fun(A[1], A[2]), fa_2 = fun(A[2], A[3]);
-    const u64 fb_lo = fun(B[0], B[1]), fb_hi = fun(B[1], B[2]), fb_2 = fun(B[2], B[3]);
-    // ---- the minimizer: the minimum of the m-mer values at positions lane .. lane + nbm - 1 of the 192 at hand ----
-    auto mval = [&](u64 a, u64 b) {      // the m-mer that starts at bit 0 of (a, b): base j is digit m-1-j
-      const u32 y0 = __brev((u32)a & mmask) >> (32 - m), y1 = __brev((u32)b & mmask) >> (32 - m);
-      return mmer_value(spread16(y0) | (spread16(y1) << 1), m);
-    };
-    u32 v0 = mval(fa_lo, fb_lo), v1 = mval(fa_hi, fb_hi), v2 = mval(fa_2, fb_2);      // positions lane, 64 + lane, 128 + lane
-    int span = 1;                                                                      // v holds the minimum over `span` positions
-#pragma unroll
-    for (int d = 1; d <= 32; d <<= 1) {
-      if (2 * d > nbm) break;                                                          // (uniform)
-      const u32 n0 = min(v0, sk_at(v0, v1, d, lane)), n1 = min(v1, sk_at(v1, v2, d, lane)), n2 = min(v2, sk_at(v2, 0xFFFFFFFFu, d, lane));
-      v0 = n0; v1 = n1; v2 = n2; span = 2 * d;
-    }
-    // (span <= nbm < 2 span, or span = 64 and nbm <= 124: two spans cover the window; the second starts nbm - span < 64 positions on)
-    const u32 mini = nbm > span ? min(v0, sk_at(v0, v1, nbm - span, lane)) : v0;
-    // ---- the canonical k-mer: digit i is base k - 1 - i (A0 C1 T2 G3: plane A the low bit, plane B the high one) ----
-    const u64 a_lo = fa_lo & klo, a_hi = fa_hi & khi, b_lo = fb_lo & klo, b_hi = fb_hi & khi;
-    u64 ra_lo, ra_hi, rb_lo, rb_hi;
-    q_rev(a_lo, a_hi, k, ra_lo, ra_hi); q_rev(b_lo, b_hi, k, rb_lo, rb_hi);
-    const u64 nb_lo = ~b_lo & klo, nb_hi = ~b_hi & khi;      // the reverse complement's digit i is base i ^ 2
-    u64 f[KW], r[KW];
-#pragma unroll
-    for (int w = 0; w < KW; w++) {
-      f[w] = spread32(q_bits32(ra_lo, ra_hi, w)) | (spread32(q_bits32(rb_lo, rb_hi, w)) << 1);
-      r[w] = spread32(q_bits32(a_lo, a_hi, w)) | (spread32(q_bits32(nb_lo, nb_hi, w)) << 1);
-    }
-    bool less = false, decided = false;
-#pragma unroll
-    for (int w = KW - 1; w >= 0; w--) if (!decided && f[w] != r[w]) { less = f[w] < r[w]; decided = true; }
-    u64 cw[KW];
-#pragma unroll
-    for (int w = 0; w < KW; w++) cw[w] = less ? f[w] : r[w];
+    u64 cw[KW]; u32 mini;
+    const bool whole = q_tile_kmer<KW>(bases, n_bases, pos, lane, wk, cw, mini);
     const u64 h = xxh64_words(cw, KW) % window;
     // ---- which query, and is the k-mer whole and inside it ----
     const u32 q = q_tile_query(offsets, n_seqs, qs, t0, pos);
-    bool valid = pos < n_bases && (fi_lo & klo) == 0 && (fi_hi & khi) == 0;
+    bool valid = pos < n_bases && whole;
     if (valid) valid = pos >= offsets[q] && pos + (u64)k <= offsets[q + 1];      // (bases in front of offsets[0] belong to no query)
     const u32 part = valid ? (u32)repart[mini] : 0u;
     if (pos < n_bases) keys[pos] = valid ? ((u64)part << 32) | h : QK_NONE;
-    u64 vm = __ballot(valid);
-    while (vm) {      // one add per partition of the tile (neighbouring k-mers share their minimizer: a handful)
-      const int l = __builtin_ctzll(vm);
-      const u32 pp = (u32)__shfl((int)part, l);
-      const u64 same = __ballot(valid && part == pp);
-      if (lane == l) atomicAdd(&hist[(size_t)pp * ch.n_chunks + c], (u32)__popcll(same));
-      vm &= ~same;
-    }
-    vm = __ballot(valid);
-    while (vm) {      // one add per query of the tile
-      const int l = __builtin_ctzll(vm);
-      const u32 qq = (u32)__shfl((int)q, l);
-      const u64 same = __ballot(valid && q == qq);
-      if (lane == l) atomicAdd(&n_kmers[qq], (u32)__popcll(same));
-      vm &= ~same;
-    }
+    q_tile_adds(valid, part, q, lane, hist, ch.n_chunks, c, n_kmers);
     qs = (u32)__shfl((int)q, 63);      // (lanes behind the last base searched with pos >= n_bases: the walk ends with this tile)
     if (t0 + 63 >= n_bases) break;
   }
@@ -188,10 +101,12 @@ void k_query_scatter(const u64* __restrict__ keys, const u64* __restrict__ offse
 struct __attribute__((packed, aligned(1))) QDword { u32 v; };      // a dword at any address: one global_load_dword
 
 // LOG_L: log2 of the lanes of a group (a group's lane wl owns the row's dwords wl, wl + L, ...)
-template <int LOG_L>
+// KEYED: the rows of a k-mer matrix (kquery.hip) -- a record's row lies at row * stride + skip (the nb presence/absence bytes behind the
+// key) and a record whose row is QG_NO_ROW met no row; else the rows of a Bloom matrix: row * nb, every record has one
+template <int LOG_L, bool KEYED>
 __global__ __launch_bounds__(256)
 void k_query_gather(const u64* __restrict__ recs, const u32* __restrict__ pstart, u32 n_parts, const u8* const* __restrict__ rows,
-                    u32 nb, u32 n_cols, u32* __restrict__ hits)
+                    u32 nb, u32 n_cols, u32* __restrict__ hits, u64 stride, u32 skip)
 {
   constexpr u32 L = 1u << LOG_L, S = 64u / L;
   const u32 total = pstart[n_parts];
@@ -233,7 +148,9 @@ void k_query_gather(const u64* __restrict__ recs, const u32* __restrict__ pstart
         while (i >= pend) { p++; pend = pstart[p + 1]; base = rows[p]; }      // (i < total = pstart[n_parts]: p stays below n_parts)
         if (q != cur_q) { flush(cur_q); cur_q = q; }
         if (!base) continue;                       // a partition that is not part of this call
-        const u8* rp = base + (u64)(u32)rec * nb + 4u * ws;      // 64-bit row offsets: window * nb passes 4 GiB
+        if (KEYED && (u32)rec == QG_NO_ROW) continue;
+        const u8* rp = KEYED ? base + (u64)(u32)rec * stride + skip + 4u * ws
+                             : base + (u64)(u32)rec * nb + 4u * ws;      // 64-bit row offsets: window * nb passes 4 GiB
         u32 x;
         if (whole) x = reinterpret_cast<const QDword*>(rp)->v;
         else { x = 0; for (u32 b = 0; 4u * ws + b < nb; b++) x |= (u32)rp[b] << (8u * b); }
@@ -286,15 +203,16 @@ hipError_t launch_query_scatter(const u64* keys, const u64* offsets, u32 n_seqs,
   return hipGetLastError();
 }
 
-hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
-                               u32* hits, u32 n_cu, hipStream_t st)
+template <bool KEYED>
+static hipError_t query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
+                               u32* hits, u64 stride, u32 skip, u32 n_cu, hipStream_t st)
 {
   const u32 nw = (nb + 3) / 4;
   int log_l = 0;
   while (log_l < 6 && (1u << log_l) < nw) log_l++;
   const u64 groups = (rec_bound + QG_RUN - 1) / QG_RUN, per_block = 4ull * (64u >> log_l);      // groups of lanes a workgroup holds
   const u32 grid = (u32)std::max<u64>(1, std::min<u64>((groups + per_block - 1) / per_block, (u64)std::max(n_cu, 1u) * 8));
-#define KMX_QG(LL) hipLaunchKernelGGL(k_query_gather<LL>, dim3(grid), dim3(256), 0, st, recs, pstart, n_parts, rows, nb, n_cols, hits)
+#define KMX_QG(LL) hipLaunchKernelGGL((k_query_gather<LL, KEYED>), dim3(grid), dim3(256), 0, st, recs, pstart, n_parts, rows, nb, n_cols, hits, stride, skip)
   switch (log_l) {
     case 0: KMX_QG(0); break; case 1: KMX_QG(1); break; case 2: KMX_QG(2); break; case 3: KMX_QG(3); break;
     case 4: KMX_QG(4); break; case 5: KMX_QG(5); break; default: KMX_QG(6); break;
@@ -302,5 +220,14 @@ hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart
 #undef KMX_QG
   return hipGetLastError();
 }
+
+hipError_t launch_query_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
+                               u32* hits, u32 n_cu, hipStream_t st)
+{ return query_gather<false>(recs, rec_bound, pstart, n_parts, rows, nb, n_cols, hits, nb, 0, n_cu, st); }
+
+// the same gather over the presence/absence rows of a k-mer matrix: records (row, query) as k_kquery_search leaves them (kquery.hip)
+hipError_t launch_query_gather_keyed(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u64 stride, u32 skip,
+                                     u32 nb, u32 n_cols, u32* hits, u32 n_cu, hipStream_t st)
+{ return query_gather<true>(recs, rec_bound, pstart, n_parts, rows, nb, n_cols, hits, stride, skip, n_cu, st); }
 
 }  // namespace kmx

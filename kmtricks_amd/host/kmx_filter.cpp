@@ -69,26 +69,6 @@ struct Part { uint32_t id; bool pa; std::string path; };
 
 void chk(kmx_ctx* c, int rc, const char* what) { if (rc != KMX_OK) die(std::string(what) + ": " + kmx_last_error(c)); }
 
-// a matrix file -> its header's k and column count, and its body with u32 counts (a body of 1- or 2-byte counts is widened)
-std::vector<uint8_t> read_matrix(const Part& pt, uint32_t count_bytes, uint32_t* k, uint32_t* n_cols)
-{
-  std::vector<uint8_t> raw = slurp(pt.path);
-  std::vector<uint8_t> body = body_of(raw, 45, pt.pa ? MAGIC_PA : MAGIC_MATRIX, pt.path);
-  *k = rd<uint32_t>(&raw[21]);
-  *n_cols = rd<uint32_t>(&raw[pt.pa ? 29 : 33]);
-  const size_t kb = (size_t)((*k + 31) / 32) * 8;
-  const size_t rin = kb + (pt.pa ? (*n_cols + 7) / 8 : (size_t)*n_cols * count_bytes);
-  if (*n_cols == 0 || body.size() % rin) throw IoError("truncated matrix (its body is no whole number of rows): " + pt.path);
-  if (pt.pa || count_bytes == 4) return body;
-  const size_t rows = body.size() / rin, rout = kb + (size_t)*n_cols * 4;
-  std::vector<uint8_t> wide(rows * rout, 0);
-  for (size_t r = 0; r < rows; r++) {
-    memcpy(&wide[r * rout], &body[r * rin], kb);
-    for (uint32_t c = 0; c < *n_cols; c++) memcpy(&wide[r * rout + kb + (size_t)c * 4], &body[r * rin + kb + (size_t)c * count_bytes], count_bytes);
-  }
-  return wide;
-}
-
 }  // namespace
 
 int kmx_filter_main(int argc, char** argv)
@@ -165,7 +145,7 @@ int kmx_filter_main(int argc, char** argv)
   std::vector<size_t> mine;
   for (size_t i = 0; i < parts.size(); i++) if (parts[i].id % G == g) mine.push_back(i);
   if (mine.empty()) return;
-  auto load = [&](size_t i) { return std::async(std::launch::async, [&, i] { uint32_t fk = 0, n = 0; std::vector<uint8_t> b = read_matrix(parts[i], o.count_bytes, &fk, &n); return std::make_tuple(std::move(b), fk, n); }); };
+  auto load = [&](size_t i) { return std::async(std::launch::async, [&, i] { uint32_t fk = 0, n = 0; std::vector<uint8_t> b = read_matrix(parts[i].path, parts[i].pa, o.count_bytes, &fk, &n); return std::make_tuple(std::move(b), fk, n); }); };
   auto next_file = load(mine[0]);
   uint8_t* stage[2] = {nullptr, nullptr}; uint64_t stage_bytes = 0;
   for (size_t mi = 0; mi < mine.size(); mi++) {

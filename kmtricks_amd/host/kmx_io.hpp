@@ -254,6 +254,27 @@ inline void matrix_bf_header(Out& o, uint32_t bits, uint64_t first, uint64_t win
   o.base_header(); o.put<uint64_t>(MAGIC_BITMATRIX); o.put<uint32_t>(bits); o.put<uint64_t>(first); o.put<uint64_t>(window); o.put<uint32_t>(0); o.put<uint32_t>(part);
 }
 
+// a k-mer matrix file (.count / .pa, plain or lz4) -> its header's k and column count, and its body with u32 counts (a body of 1- or
+// 2-byte counts is widened); `kmx filter` and `kmx query --kmer-index` read their matrices with it
+inline std::vector<uint8_t> read_matrix(const std::string& path, bool pa, uint32_t count_bytes, uint32_t* k, uint32_t* n_cols)
+{
+  std::vector<uint8_t> raw = slurp(path);
+  std::vector<uint8_t> body = body_of(raw, 45, pa ? MAGIC_PA : MAGIC_MATRIX, path);
+  *k = rd<uint32_t>(&raw[21]);
+  *n_cols = rd<uint32_t>(&raw[pa ? 29 : 33]);
+  const size_t kb = (size_t)((*k + 31) / 32) * 8;
+  const size_t rin = kb + (pa ? (*n_cols + 7) / 8 : (size_t)*n_cols * count_bytes);
+  if (*n_cols == 0 || body.size() % rin) throw IoError("truncated matrix (its body is no whole number of rows): " + path);
+  if (pa || count_bytes == 4) return body;
+  const size_t rows = body.size() / rin, rout = kb + (size_t)*n_cols * 4;
+  std::vector<uint8_t> wide(rows * rout, 0);
+  for (size_t r = 0; r < rows; r++) {
+    memcpy(&wide[r * rout], &body[r * rin], kb);
+    for (uint32_t c = 0; c < *n_cols; c++) memcpy(&wide[r * rout + kb + (size_t)c * 4], &body[r * rin + kb + (size_t)c * count_bytes], count_bytes);
+  }
+  return wide;
+}
+
 // ---- superkmers/<id>/skp.<p> (io/superk_file.hpp:30-35; superk_storage.hpp:187-225, 296-309) ----
 // blocks of <= 32768 bytes of whole records, each preceded by its u32 size
 struct SuperkBlockWriter {

@@ -2,7 +2,7 @@
 // shipped as `kmtricks query`, doc/changelogs/v1.0.0.md, and kmindex does today; no counterpart in the 1.6.0 tree).  The index is the
 // run directory as `kmx pipeline` / kmtricks leave it; the queries go through kmx_query_host in batches, the partitions' matrices in
 // groups that fit the device, a group's hits added on the device to the table of the groups before it.  Every check that needs no
-// GPU comes before kmx_create.
+// GPU comes before kmx_create.  `--kmer-index` asks the same of the k-mer matrices of a kmer:count:bin / kmer:pa:bin run (kquery_main).
 #include <kmx.h>
 #include <algorithm>
 #include <cstring>
@@ -17,15 +17,16 @@ using namespace kmxio;
 namespace {
 
 struct QOpt {
-  std::string index, query, out, format = "matrix";
+  std::string index, kmer_index, query, out, format = "matrix";
   double threshold = 0.7;
   uint32_t gpus = 1, threads = 8;
   uint64_t batch_mb = 0;      // 0: sized from the device's free memory
   bool verbose = false;
 };
 
-const char* USAGE = "usage: kmx query --index <run dir made with --mode hash:bf:bin> --query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] "
-                    "[--format matrix|list] [--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
+const char* USAGE = "usage: kmx query (--index <run dir made with --mode hash:bf:bin> | --kmer-index <run dir made with --mode kmer:count:bin or kmer:pa:bin>) "
+                    "--query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] [--format matrix|list|sums (sums: --kmer-index of a count run)] "
+                    "[--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
 
 QOpt parse(int argc, char** argv)
 {
@@ -35,17 +36,19 @@ QOpt parse(int argc, char** argv)
   for (int i = 2; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "--index") o.index = need(i);
+    else if (a == "--kmer-index") o.kmer_index = need(i);
     else if (a == "--query") o.query = need(i);
     else if (a == "--output") o.out = need(i);
     else if (a == "--threshold") { const std::string v = need(i); try { size_t n = 0; o.threshold = std::stod(v, &n); if (n != v.size()) throw 1; } catch (...) { die("bad number for --threshold: " + v); } }
-    else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list") die("--format must be matrix or list"); }
+    else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list" && o.format != "sums") die("--format must be matrix, list or sums"); }
     else if (a == "--gpus") o.gpus = num(i);
     else if (a == "--query-batch-mb") o.batch_mb = num(i);
     else if (a == "-t" || a == "--threads") o.threads = num(i);
     else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
     else die("unknown option " + a + "\n" + USAGE);
   }
-  if (o.index.empty()) die(std::string("--index is required\n") + USAGE);
+  if (o.index.empty() == o.kmer_index.empty()) die(std::string("exactly one of --index and --kmer-index is required\n") + USAGE);
+  if (o.format == "sums" && o.kmer_index.empty()) die("--format sums needs --kmer-index with a run made with --mode kmer:count:bin");
   if (o.query.empty()) die(std::string("--query is required\n") + USAGE);
   if (o.gpus < 1 || o.gpus > 16) die("--gpus must be in [1, 16]");
   if (o.threshold < 0.0 || o.threshold > 1.0) die("--threshold must be in [0, 1]");
@@ -64,18 +67,202 @@ std::string option_of(const std::string& line, const std::string& key)
   return v;
 }
 
-constexpr size_t CMBF_HEADER = 49;
+constexpr size_t CMBF_HEADER = 49, KMATRIX_HEADER = 45;
+
+// ---- `kmx query --kmer-index`: the same questions asked of the .count / .pa k-mer matrices of a kmer:count:bin / kmer:pa:bin run --
+//      exact, and in count mode with abundances (kmx_kquery_host).  Partition groups, query batches and shards as above. ----
+int kquery_main(const QOpt& o)
+{
+  const std::string& run = o.kmer_index;
+  // ---- the index: a run directory of --mode kmer:count:bin or kmer:pa:bin; every check before kmx_create ----
+  if (!fs::exists(run + "/kmtricks.fof")) die(run + " is not a kmtricks runtime directory.");
+  std::string opt; { std::ifstream f(run + "/options.txt"); if (!f) die("Unable to read at " + run + "/options.txt"); std::getline(f, opt); }
+  const std::string mode = option_of(opt, "count_format") + ":" + option_of(opt, "mode") + ":" + option_of(opt, "format");
+  if (mode != "kmer:count:bin" && mode != "kmer:pa:bin")
+    die("kmx query --kmer-index needs a run made with --mode kmer:count:bin or kmer:pa:bin; " + run + " was made with " + mode + (mode == "hash:bf:bin" ? " (a Bloom index: --index)" : ""));
+  const bool pa = mode == "kmer:pa:bin";
+  if (o.format == "sums" && pa) die("--format sums needs a run made with --mode kmer:count:bin: presence/absence rows have no counts to sum");
+  uint32_t k = 0;
+  try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(run + "/options.txt names no kmer_size"); }
+  GatbConfig gc;
+  if (!GatbConfig::load(run + "/config_gatb/gatb.config", gc)) die("Unable to read at " + run + "/config_gatb/gatb.config");
+  uint16_t rp = 0;
+  const std::vector<uint16_t> table = read_repartition(run + "/repartition_gatb/repartition.minimRepart", &rp);
+  const uint32_t msize = (uint32_t)gc.minim_size, kw = (k + 31) / 32;
+  const uint64_t P = rp;
+  if (k < 8 || k > 127 || gc.kmer_size != k || msize < 4 || msize > 15 || msize >= k || table.size() != ((size_t)1 << (2 * msize)) || P == 0)
+    die("the index's options.txt, gatb.config and repartition table do not fit together");
+  for (uint16_t t : table) if (t >= P) die("the index's repartition table names a partition the run does not have");
+  const std::vector<Sample> samples = parse_fof(run + "/kmtricks.fof", 1);
+  const uint32_t N = (uint32_t)samples.size();
+  const uint64_t stride = 8ull * kw + (pa ? (N + 7) / 8 : 4ull * N);
+  std::vector<std::string> files(P);
+  std::vector<uint64_t> n_rows(P, 0);
+  for (uint64_t p = 0; p < P; p++) {
+    const std::string plain = run + "/matrices/matrix_" + std::to_string(p) + (pa ? ".pa" : ".count");
+    const bool lz = !fs::exists(plain) && fs::exists(plain + ".lz4");
+    files[p] = lz ? plain + ".lz4" : plain;
+    std::ifstream f(files[p], std::ios::binary);
+    uint8_t h[KMATRIX_HEADER];
+    if (!f || !f.read((char*)h, KMATRIX_HEADER)) die("Unable to read at " + plain);
+    if (rd<uint64_t>(&h[0]) != MAGIC_BASE || rd<uint64_t>(&h[13]) != (pa ? MAGIC_PA : MAGIC_MATRIX)) die("Invalid file format: " + files[p]);
+    if (rd<uint32_t>(&h[21]) != k || rd<uint32_t>(&h[25]) != kw)
+      die(files[p] + " was made with k = " + std::to_string(rd<uint32_t>(&h[21])) + " in " + std::to_string(rd<uint32_t>(&h[25])) + " words, the index's options.txt says " + std::to_string(k));
+    const uint32_t cols = rd<uint32_t>(&h[pa ? 29 : 33]);
+    if (cols != N) die(files[p] + " has rows of " + std::to_string(cols) + " columns, the index's kmtricks.fof has " + std::to_string(N) + " samples");
+    if (pa && rd<uint32_t>(&h[33]) != (N + 7) / 8) die("Invalid file format: " + files[p]);
+    uint64_t body = 0;
+    if (h[12]) {      // lz4: the body's size is known once it is unpacked (read_matrix checks that it is whole rows)
+      uint32_t fk = 0, fn = 0;
+      body = read_matrix(files[p], pa, 4, &fk, &fn).size();
+    } else {
+      std::error_code ec;
+      body = fs::file_size(files[p], ec) - KMATRIX_HEADER;
+      if (ec || body % stride) die("truncated matrix (its body is no whole number of rows of " + std::to_string(stride) + " bytes): " + files[p]);
+    }
+    n_rows[p] = body / stride;
+    if (n_rows[p] > 0xFFFFFF00ull) die(files[p] + " has more than 2^32 - 256 rows");
+  }
+
+  // ---- the queries ----
+  std::string bases; std::vector<uint64_t> offs{0}; std::vector<std::string> names;
+  { SeqReader rd(o.query); rd.keep_names(); std::string seq; while (rd.next(seq)) { bases += seq; offs.push_back(bases.size()); names.push_back(rd.name()); } }
+  const uint64_t Q = names.size();
+  FILE* out = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
+  if (!out) die("Unable to write at " + o.out);
+
+  // ---- devices; how many bases a batch of queries holds and which partitions a group ----
+  if (kmx_version() != KMX_VERSION) die("libkmx.so is not the version this driver was built for");
+  const uint32_t G = o.gpus, ndev = (uint32_t)std::max(1, kmx_device_count());
+  std::vector<kmx_ctx*> ctxs(G, nullptr);
+  for (uint32_t g = 0; g < G; g++) if (kmx_create((int)(g % ndev), &ctxs[g]) != KMX_OK) die(std::string("kmx_create: ") + kmx_last_error(nullptr));
+  uint64_t budget = o.batch_mb << 20;
+  if (!budget) {
+    uint64_t fr = 0, tot = 0;
+    for (uint32_t g = 0; g < std::min(G, ndev); g++) { uint64_t f = 0; if (kmx_device_memory((int)g, &f, &tot) == KMX_OK && (g == 0 || f < fr)) fr = f; }
+    budget = std::max<uint64_t>(fr / 10 * 6 / std::max<uint32_t>(1, (G + ndev - 1) / ndev), 64ull << 20);
+  }
+  const bool want_sums = o.format == "sums";
+  // half for a group's matrices, half for a batch: 11 + 8 * key words bytes a base (the bases and the call's scratch) and a row of the
+  // tables a query
+  const uint64_t group_bytes = std::max<uint64_t>(budget / 2, 1), batch_bytes = std::max<uint64_t>(budget / 2, 1);
+  const uint64_t per_base = 11 + 8ull * kw, per_query = (want_sums ? 12ull : 4ull) * N + 12;
+  std::vector<uint64_t> cut{0};      // batch b = queries [cut[b], cut[b + 1])
+  { uint64_t used = 0;
+    for (uint64_t q = 0; q < Q; q++) {
+      const uint64_t len = offs[q + 1] - offs[q], cost = per_base * len + per_query;
+      if (len > 0xFFFFFFFFull) die("query " + names[q] + " has 2^32 bases or more");
+      if (q > cut.back() && (used + cost > batch_bytes || offs[q + 1] - offs[cut.back()] > 0xFFFFFFFFull)) { cut.push_back(q); used = 0; }
+      used += cost;
+    }
+    cut.push_back(Q); if (Q == 0) cut.pop_back(); }
+  std::vector<std::vector<std::vector<uint32_t>>> groups(G);      // per shard: its partitions (p mod G) in groups of at most group_bytes
+  size_t n_groups = 0;
+  { std::vector<uint64_t> fill(G, 0);
+    for (uint64_t p = 0; p < P; p++) {
+      auto& gs = groups[p % G]; const uint64_t b = n_rows[p] * stride;
+      if (gs.empty() || (fill[p % G] + b > group_bytes && !gs.back().empty())) { gs.emplace_back(); fill[p % G] = 0; }
+      gs.back().push_back((uint32_t)p); fill[p % G] += b;
+    } }
+  for (auto& gs : groups) n_groups = std::max(n_groups, gs.size());
+  if (o.verbose) fprintf(stderr, "[kmx query] %llu queries, %zu bases, k %u, %u samples, %llu partitions of k-mer rows (%s): %zu query batches, %zu partition groups a shard, %u shards\n",
+                         (unsigned long long)Q, bases.size(), k, N, (unsigned long long)P, pa ? "pa" : "count", cut.size() - 1, n_groups, G);
+
+  if (o.format != "list") { std::string h = "query\tn_kmers"; for (const Sample& s : samples) { h += '\t'; h += s.id; } h += '\n'; fwrite(h.data(), 1, h.size(), out); }
+  // a shard whose partitions fit one group reads its matrices once; a shard with several groups reads every group again for every
+  // batch of queries
+  std::vector<std::vector<std::vector<uint8_t>>> kept(G);
+  for (size_t b = 0; b + 1 < cut.size(); b++) {
+    const uint64_t q0 = cut[b], nq = cut[b + 1] - q0;
+    std::vector<uint64_t> boffs(nq + 1);
+    for (uint64_t i = 0; i <= nq; i++) boffs[i] = offs[q0 + i] - offs[q0];
+    std::vector<uint32_t> hits(nq * N, 0), kmers(nq, 0);
+    std::vector<uint64_t> sums(want_sums ? nq * N : 0, 0);
+    std::mutex mu;
+    // every shard sees all queries of the batch; its groups add up on its device, the shards' tables on the host
+    auto shard = [&](uint32_t g) {
+      try {
+        kmx_ctx* ctx = ctxs[g];
+        kmx_kquery_result* first = nullptr;
+        std::vector<std::vector<uint8_t>> own;
+        const bool keep = groups[g].size() == 1;
+        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+        std::vector<const uint8_t*> rows(P);
+        std::vector<uint32_t> sk(nq);
+        static const uint8_t no_rows[8] = {0};      // a partition without a row is still part of the call
+        for (size_t gi = 0; gi < groups[g].size(); gi++) {
+          std::fill(rows.begin(), rows.end(), nullptr);
+          const bool loaded = keep && bodies.size() == groups[g][gi].size();
+          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+          for (size_t i = 0; i < groups[g][gi].size(); i++) {
+            const uint32_t p = groups[g][gi][i];
+            if (!loaded) {
+              uint32_t fk = 0, fn = 0;
+              bodies[i] = read_matrix(files[p], pa, 4, &fk, &fn);
+              if (fk != k || fn != N || bodies[i].size() != n_rows[p] * stride) die("changed while it was read: " + files[p]);
+            }
+            rows[p] = bodies[i].empty() ? no_rows : bodies[i].data();
+          }
+          kmx_kquery_task t; memset(&t, 0, sizeof t);
+          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N;
+          t.key_words = kw; t.mode = pa ? KMX_MODE_PA : KMX_MODE_COUNT; t.n_rows = n_rows.data(); t.rows = rows.data();
+          t.want_sums = want_sums ? 1 : 0;
+          t.hits = first ? kmx_kquery_result_hits_dev(first) : nullptr;
+          t.sums = first && want_sums ? kmx_kquery_result_sums_dev(first) : nullptr;
+          kmx_kquery_result* r = nullptr;
+          chk(ctx, kmx_kquery_host(ctx, &t, &r), "kmx_kquery_host");
+          chk(ctx, kmx_kquery_result_wait(r), "kmx_kquery");      // (the bodies are reused by the next group)
+          if (!first) first = r; else kmx_kquery_result_free(r);
+        }
+        if (!first) return;      // (more shards than partitions)
+        std::vector<uint32_t> sh(nq * N);
+        std::vector<uint64_t> ss(want_sums ? nq * N : 0);
+        chk(ctx, kmx_kquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_kquery_result_copy_hits");
+        if (want_sums) chk(ctx, kmx_kquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_kquery_result_copy_sums");
+        chk(ctx, kmx_kquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_kquery_result_copy_kmers");
+        kmx_kquery_result_free(first);
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+        for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
+        kmers = sk;      // (every shard walks every query: the same numbers)
+      } catch (const std::exception& e) { die(e.what()); }
+    };
+    std::vector<std::thread> workers;
+    for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
+    shard(0);
+    for (std::thread& w : workers) w.join();
+    std::string txt;
+    for (uint64_t i = 0; i < nq; i++) {
+      const std::string& name = names[q0 + i];
+      if (o.format != "list") {
+        txt += name; txt += '\t'; txt += std::to_string(kmers[i]);
+        for (uint32_t c = 0; c < N; c++) { txt += '\t'; txt += want_sums ? std::to_string(sums[i * N + c]) : std::to_string(hits[i * N + c]); }
+        txt += '\n';
+      } else if (kmers[i] > 0) {
+        for (uint32_t c = 0; c < N; c++)
+          if ((double)hits[i * N + c] >= o.threshold * (double)kmers[i])
+            txt += name + '\t' + samples[c].id + '\t' + std::to_string(hits[i * N + c]) + '\t' + std::to_string(kmers[i]) + '\n';
+      }
+    }
+    if (fwrite(txt.data(), 1, txt.size(), out) != txt.size()) die("write failed: " + (o.out.empty() ? std::string("stdout") : o.out));
+  }
+  if (out != stdout) { if (fclose(out) != 0) die("write failed: " + o.out); } else fflush(stdout);
+  for (uint32_t g = 0; g < G; g++) kmx_destroy(ctxs[g]);
+  return 0;
+}
 
 }  // namespace
 
 int kmx_query_main(int argc, char** argv)
 {
   const QOpt o = parse(argc, argv);
+  if (!o.kmer_index.empty()) return kquery_main(o);
   // ---- the index: a run directory of --mode hash:bf:bin ----
   if (!fs::exists(o.index + "/kmtricks.fof")) die(o.index + " is not a kmtricks runtime directory.");
   std::string opt; { std::ifstream f(o.index + "/options.txt"); if (!f) die("Unable to read at " + o.index + "/options.txt"); std::getline(f, opt); }
   const std::string mode = option_of(opt, "count_format") + ":" + option_of(opt, "mode") + ":" + option_of(opt, "format");
-  if (mode != "hash:bf:bin") die("kmx query needs a run made with --mode hash:bf:bin; " + o.index + " was made with " + mode);
+  if (mode != "hash:bf:bin") die("kmx query --index needs a run made with --mode hash:bf:bin; " + o.index + " was made with " + mode + (mode == "kmer:count:bin" || mode == "kmer:pa:bin" ? " (a k-mer run: --kmer-index)" : ""));
   uint32_t k = 0;
   try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(o.index + "/options.txt names no kmer_size"); }
   uint64_t W = 0, P = 0; uint32_t msize = 0;

@@ -52,6 +52,13 @@ class KmxQueryTask(C.Structure):
                 ("window", C.c_uint64), ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p)]
 
 
+class KmxKqueryTask(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("kmer_size", C.c_uint32),
+                ("minim_size", C.c_uint32), ("repart", C.c_void_p), ("nb_parts", C.c_uint32), ("n_cols", C.c_uint32),
+                ("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_rows", C.POINTER(C.c_uint64)),
+                ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p), ("sums", C.c_void_p), ("want_sums", C.c_uint32)]
+
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -202,6 +209,24 @@ _lib.kmx_query_result_hits_dev.argtypes = [_vp]
 _lib.kmx_query_result_kernel_ms.restype = C.c_double
 _lib.kmx_query_result_kernel_ms.argtypes = [_vp]
 _lib.kmx_query_result_free.argtypes = [_vp]
+
+_lib.kmx_kquery_dev.argtypes = [_vp, C.POINTER(KmxKqueryTask), C.POINTER(_vp)]
+_lib.kmx_kquery_host.argtypes = [_vp, C.POINTER(KmxKqueryTask), C.POINTER(_vp)]
+_lib.kmx_kquery_result_wait.argtypes = [_vp]
+for _f in ("kmx_kquery_result_n_seqs", "kmx_kquery_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_kquery_result_copy_kmers", "kmx_kquery_result_copy_hits", "kmx_kquery_result_copy_sums"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_kquery_result_hits_dev", "kmx_kquery_result_sums_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_kquery_result_kernel_ms.restype = C.c_double
+_lib.kmx_kquery_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_kquery_result_free.argtypes = [_vp]
+KQUERY_EXPORTS = ["kmx_kquery_dev", "kmx_kquery_host", "kmx_kquery_result_wait", "kmx_kquery_result_n_seqs", "kmx_kquery_result_copy_kmers",
+                  "kmx_kquery_result_copy_hits", "kmx_kquery_result_copy_sums", "kmx_kquery_result_hits_dev", "kmx_kquery_result_sums_dev",
+                  "kmx_kquery_result_kernel_ms", "kmx_kquery_result_algo_bytes", "kmx_kquery_result_free"]
 
 
 def filter_want(want):
@@ -662,6 +687,61 @@ class Context:
         finally:
             r.free()
 
+    def kquery(self, reads, k, m, repart, n_cols, key_words, mode, matrices, n_rows=None, hits_dev=None, sums=False, keep=False):
+        """kmx_kquery_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
+        .count / .pa (bytes or a uint8 array of whole rows: key words, then n_cols u32 counts or ceil(n_cols / 8) bytes) or None (the
+        partition is not part of the call); n_rows None (from the bodies' sizes) or the rows per partition; hits_dev None or a device
+        pointer to a uint32 table [queries, n_cols] the call adds to; sums False, True (the result owns the uint64 table) or a device
+        pointer to a uint64 table the call adds to.
+        -> KqueryOutput (numpy copies), or with keep the KqueryResult itself (the tables left in HBM; .free() it)"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        rep = np.ascontiguousarray(repart, dtype=np.uint16)
+        stride = key_words * 8 + (4 * n_cols if mode == MODE_COUNT else (n_cols + 7) // 8)
+        keepalive, rows, nr = [], (C.c_void_p * len(matrices))(), (C.c_uint64 * len(matrices))()
+        for p, mt in enumerate(matrices):
+            if mt is None:
+                continue
+            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+            if n_rows is None and len(a) % stride:
+                raise ValueError(f"partition {p}: {len(a)} bytes are not whole rows of {stride} bytes")
+            nr[p] = len(a) // stride if n_rows is None else n_rows[p]
+            if not len(a):
+                a = np.zeros(1, np.uint8)      # (a partition of no rows is still part of the call)
+            keepalive.append(a)
+            rows[p] = a.ctypes.data
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        want, sums_dev = (1, None) if sums is True else (0, None) if sums is False or sums is None else (1, sums)
+        t = KmxKqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, key_words, mode, nr, rows,
+                          hits_dev, sums_dev, want)
+        res = _vp()
+        self._check(_lib.kmx_kquery_host(self._h, C.byref(t), C.byref(res)), "kmx_kquery_host")
+        r = KqueryResult(self, res, n_cols, bool(want))
+        r.wait()      # (the host buffers above may go once the call has run)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def kquery_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, n_cols, key_words, mode, rows_dev, n_rows, hits_dev=None, sums=False, keep=False):
+        """kmx_kquery_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
+        repartition table; rows_dev[p] a device pointer to partition p's matrix body or None, n_rows[p] its rows.  -> as kquery"""
+        rows = (C.c_void_p * len(rows_dev))(*rows_dev)
+        nr = (C.c_uint64 * len(rows_dev))(*[int(x) for x in n_rows])
+        want, sums_dev = (1, None) if sums is True else (0, None) if sums is False or sums is None else (1, sums)
+        t = KmxKqueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, key_words, mode, nr, rows, hits_dev, sums_dev, want)
+        res = _vp()
+        self._check(_lib.kmx_kquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_kquery_dev")
+        r = KqueryResult(self, res, n_cols, bool(want))
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
     @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
@@ -764,6 +844,61 @@ class QueryOutput:
 
     def __init__(self, n_kmers, hits, kernel_ms, algo_bytes):
         self.n_kmers, self.hits, self.kernel_ms, self.algo_bytes = n_kmers, hits, kernel_ms, algo_bytes
+
+
+class KqueryOutput:
+    """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose k-mer is a row's key with a
+    non-zero count / a set bit in the column; sums uint64[queries, n_cols] (None unless asked for): those rows' counts added up;
+    kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_kmers, hits, sums, kernel_ms, algo_bytes):
+        self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
+
+
+class KqueryResult:
+    def __init__(self, ctx, h, n_cols, has_sums):
+        self._ctx, self._h, self._n, self._sums = ctx, h, n_cols, has_sums
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_kquery_result_wait(self._h), "kmx_kquery_result_wait")
+
+    def n_seqs(self):
+        return _lib.kmx_kquery_result_n_seqs(self._h)
+
+    def hits_dev(self):
+        return _lib.kmx_kquery_result_hits_dev(self._h)
+
+    def sums_dev(self):
+        return _lib.kmx_kquery_result_sums_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_kquery_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_kquery_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        q = self.n_seqs()
+        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
+        self._ctx._check(_lib.kmx_kquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_kquery_result_copy_kmers")
+        self._ctx._check(_lib.kmx_kquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_kquery_result_copy_hits")
+        sums = None
+        if self._sums:
+            sums = np.zeros((q, self._n), np.uint64)
+            self._ctx._check(_lib.kmx_kquery_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_kquery_result_copy_sums")
+        return KqueryOutput(nk, hits, sums, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_kquery_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class QueryResult:
