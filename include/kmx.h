@@ -26,6 +26,8 @@
  *                               matrices of a hash:bf:bin run, addressed as kmer_hash.hpp:244-328 and repartition.hpp:94-103 publish
  *   kmx_kquery_dev / _host      no counterpart either: query sequences against the .count / .pa k-mer matrices of a kmer:count:bin /
  *                               kmer:pa:bin run -- exact, with abundances (k-mer, minimizer and partition as kmx_query_* has them)
+ *   kmx_zquery_dev / _host      no counterpart either: kmx_query_*'s question asked for (k + z)-mers, the findere trick against Bloom
+ *                               false positives -- a position counts for a sample when its z + 1 overlapping k-mers all do
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -457,6 +459,69 @@ double   kmx_kquery_result_kernel_ms(kmx_kquery_result* r);
  * k-mer) + the tables written */
 uint64_t kmx_kquery_result_algo_bytes(kmx_kquery_result* r);
 void     kmx_kquery_result_free(kmx_kquery_result* r);
+
+/* ----------------------------------------------------------------- zquery */
+
+/* The findere trick over the Bloom matrices of the query section: the index stays as it is, with k-mers of the run's k; the query asks
+ * for (k + z)-mers.  A (k + z)-mer is present in a sample only when all of its z + 1 overlapping k-mers are: a false positive needs
+ * z + 1 Bloom errors in a row.  Everything of the query section stands: the index, what a valid position is, the canonical k-mer, the
+ * partition, the row, the masking of padding bits.  Let K = kmer_size + z.  Position j of query q is a K-POSITION when j + K <= the
+ * query's end and all K bases from j on are ACGT (either case) -- positions j and j + z are both valid k-mer positions of q.  Results:
+ *   n_kmers[q]           the number of K-positions of q
+ *   hits[q * n_cols + i] the number of K-positions j for which bit i is set in the row of EVERY k-mer at j, j + 1, ..., j + z
+ * Every occurrence counts; z = 0 is the query section's result, bit for bit.
+ * A SERIES is one or more calls over the same bases and offsets, each with a different set of non-NULL rows[p] (the partition groups
+ * of an index that does not fit the device), all sharing one `bits` table: per base one row of kmx_zquery_bits_bytes(1, n_cols) bytes,
+ * the k-mer's matrix row at that position masked to the columns below n_cols (zeros where no k-mer is or its partition was in no call).
+ * The first call passes bits = NULL and its result owns a zeroed table (kmx_zquery_result_bits_dev; the result is kept until the
+ * series has ended); the later calls pass that table.  The call with last != 0 ends the series: it runs the window pass over the table
+ * and produces n_kmers and hits.  A k-mer whose partition is in no call of the series has a row of zeros: its windows count in n_kmers
+ * and add no hit.  A single call with every partition and last = 1 is the common case.  hits: NULL (the last call's result owns a
+ * zeroed table) or a DEVICE table of n_seqs * n_cols u32 that the window pass ADDS to; read only when last.
+ * LIMITS, each refused before any GPU work: the query section's; z > 8 or z >= kmer_size (KMX_E_INVAL); a bits table of more than
+ * 2^40 bytes (KMX_E_UNSUPPORTED: send the queries in batches).
+ * Scratch from the context's pool: 16 bytes a base, plus the bits table when the result owns it. */
+typedef struct {
+  const char*     bases;
+  const uint64_t* offsets;      /* [n_seqs + 1], offsets[0] = 0 */
+  uint64_t        n_seqs;
+  uint32_t        kmer_size, minim_size;
+  const uint16_t* repart;       /* u16[4^minim_size]: minimizer -> partition */
+  uint32_t        nb_parts;
+  uint32_t        n_cols;       /* N: samples (bits of a row) */
+  uint64_t        window;       /* W: rows of a partition's matrix */
+  const uint8_t* const* rows;   /* [nb_parts] */
+  uint32_t        z;            /* 0 ... 8 and below kmer_size */
+  uint32_t        last;         /* non-zero: this call ends the series: the window pass runs, n_kmers and hits are produced */
+  uint8_t*        bits;         /* NULL: the result owns a zeroed table; else a DEVICE table from an earlier call of the series */
+  uint32_t*       hits;         /* NULL, or a device table the window pass adds to; read only when last */
+} kmx_zquery_task;
+
+typedef struct kmx_zquery_result kmx_zquery_result;
+
+/* bytes of the bits table of n_bases bases: n_bases * pitch, pitch = 4 * ceil(ceil(n_cols / 8) / 4) */
+uint64_t kmx_zquery_bits_bytes(uint64_t n_bases, uint32_t n_cols);
+/* bases, offsets, repart, every rows[p], bits and hits DEVICE pointers (the rows array itself lies in host memory).  The kernels are
+ * queued on the context's stream and the call returns; it reads offsets[n_seqs] back first (8 bytes: the grid's size). */
+int kmx_zquery_dev(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out);
+/* HOST pointers (bits and hits, when given, are still device tables): everything is uploaded on a stream of its own.  The host buffers
+ * may be reused once kmx_zquery_result_wait has returned. */
+int kmx_zquery_host(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out);
+int      kmx_zquery_result_wait(kmx_zquery_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t kmx_zquery_result_n_seqs(const kmx_zquery_result* r);
+/* n_kmers and hits exist once the series has ended: on the result of a call without `last` the copies return KMX_E_INVAL, hits_dev NULL */
+int      kmx_zquery_result_copy_kmers(kmx_zquery_result* r, uint32_t* host_dst, uint64_t dst_entries);   /* n_seqs entries */
+int      kmx_zquery_result_copy_hits(kmx_zquery_result* r, uint32_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols: the table as it stands, the task's when one was given */
+uint32_t* kmx_zquery_result_hits_dev(kmx_zquery_result* r);
+uint8_t* kmx_zquery_result_bits_dev(kmx_zquery_result* r);      /* the series' table: the result's own or the task's */
+/* duration in ms of the call's kernels, the clearing of their tables included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_zquery_result_kernel_ms(kmx_zquery_result* r);
+/* algorithmic bytes, with found = the call's valid k-mers whose partition is part of the call, nb = ceil(n_cols / 8) and pitch as above:
+ * the bases read + found * nb (rows read) + found * pitch (table rows written); and for the last call + (K-positions + z per query
+ * that has any) * pitch (table rows read by the window pass) + 4 * n_seqs * n_cols (the hits table written) */
+uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* r);
+void     kmx_zquery_result_free(kmx_zquery_result* r);
 
 /* ------------------------------------------------------------------ count */
 

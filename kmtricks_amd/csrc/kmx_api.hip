@@ -2433,6 +2433,252 @@ extern "C" void kmx_query_result_free(kmx_query_result* R)
   query_release(R);
 }
 
+// ---- zquery ------------------------------------------------------------------------------------------------------------------------
+// kmx_zquery_dev / kmx_zquery_host: the (k + z)-mers of query sequences against the Bloom matrices of a run (zquery.hip).
+struct kmx_zquery_result {
+  kmx_ctx* ctx = nullptr;
+  u64 n_seqs = 0, n_bases = 0;
+  u32 n_cols = 0, nb = 0, pitch = 0, n_parts = 0, z = 0;
+  bool last = false;
+  u64 *d_keys = nullptr, *d_recs = nullptr;
+  u32 *d_cell = nullptr, *d_pstart = nullptr, *d_kcount = nullptr;      // d_kcount: k_query_keys' k-mers per query (scratch: the result counts K-positions)
+  u32 *d_kmers = nullptr, *d_hits_own = nullptr, *d_hits = nullptr;     // (the last call of a series only)
+  u8 *d_bits_own = nullptr, *d_bits = nullptr;
+  const u8** d_rows = nullptr;
+  const u8** h_rows = nullptr;          // page-locked: the row pointers on their way up
+  std::vector<void*> d_in;              // kmx_zquery_host: the uploads
+  std::vector<bool> in_call;            // partition p is part of the call
+  u32* h_pstart = nullptr;              // page-locked: the first record of every partition, [n_parts] the valid k-mers of the call
+  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
+  bool waited = false; int status = KMX_OK;
+};
+
+extern "C" uint64_t kmx_zquery_bits_bytes(uint64_t n_bases, uint32_t n_cols)
+{ return n_bases * (4ull * ((((u64)n_cols + 7) / 8 + 3) / 4)); }
+
+static kmx_query_task zquery_as_query(const kmx_zquery_task* Z)
+{
+  kmx_query_task q; memset(&q, 0, sizeof q);
+  q.bases = Z->bases; q.offsets = Z->offsets; q.n_seqs = Z->n_seqs; q.kmer_size = Z->kmer_size; q.minim_size = Z->minim_size; q.repart = Z->repart;
+  q.nb_parts = Z->nb_parts; q.n_cols = Z->n_cols; q.window = Z->window; q.rows = Z->rows; q.hits = Z->hits;
+  return q;
+}
+
+// the query section's limits, then the section's own
+static int zquery_check(kmx_ctx* ctx, const kmx_zquery_task* Z, const char* who)
+{
+  const kmx_query_task q = zquery_as_query(Z);
+  const int rc = query_check(ctx, &q, who);
+  if (rc != KMX_OK) return rc;
+  if (Z->z > 8 || Z->z >= Z->kmer_size) return ctx->fail(KMX_E_INVAL, std::string(who) + ": z must be in [0, 8] and below kmer_size");
+  return KMX_OK;
+}
+static int zquery_check_bases(kmx_ctx* ctx, const kmx_zquery_task* Z, u64 n_bases, const char* who)
+{
+  if (n_bases > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, std::string(who) + ": 2^32 bases and more in one call (send the queries in batches)");
+  if (kmx_zquery_bits_bytes(n_bases, Z->n_cols) > (1ull << 40)) return ctx->fail(KMX_E_UNSUPPORTED, std::string(who) + ": a bits table of more than 2^40 bytes (send the queries in batches)");
+  return KMX_OK;
+}
+
+static void zquery_release(kmx_zquery_result* R)
+{
+  kmx_ctx* c = R->ctx;
+  void* blocks[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kcount, R->d_kmers, R->d_hits_own, R->d_bits_own, (void*)R->d_rows};
+  for (void* p : blocks) c->dfree(p);
+  for (void* p : R->d_in) c->dfree(p);
+  c->hfree(R->h_pstart); c->hfree((void*)R->h_rows);
+  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
+  delete R;
+}
+
+// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
+static int zquery_queue(kmx_ctx* ctx, const kmx_zquery_task* K, kmx_zquery_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u64 n_bases = R->n_bases;
+  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, nb = R->nb, kw = (K->kmer_size + 31) / 32;
+  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
+  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
+  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N, bits_bytes = kmx_zquery_bits_bytes(n_bases, N);
+  if (!(R->h_pstart = (u32*)ctx->halloc(4ull * (P + 1))) || !(R->h_rows = (const u8**)ctx->halloc(8ull * P))) return ctx->fail(KMX_E_NOMEM, "kmx_zquery: host allocation failed");
+  R->in_call.assign(P, false);
+  for (u32 p = 0; p <= P; p++) R->h_pstart[p] = 0;
+  for (u32 p = 0; p < P; p++) { R->h_rows[p] = K->rows[p]; R->in_call[p] = K->rows[p] != nullptr; }
+  R->d_keys = (u64*)ctx->dalloc(8 * n_bases);
+  R->d_recs = (u64*)ctx->dalloc(8 * n_bases);
+  R->d_cell = (u32*)ctx->dalloc(4 * cells);
+  R->d_pstart = (u32*)ctx->dalloc(4ull * (P + 1));
+  R->d_kcount = (u32*)ctx->dalloc(4ull * n_seqs);
+  R->d_rows = (const u8**)ctx->dalloc(8ull * P);
+  R->d_bits = K->bits;
+  if (!R->d_bits) R->d_bits = R->d_bits_own = (u8*)ctx->dalloc(bits_bytes);
+  bool ok = R->d_keys && R->d_recs && R->d_cell && R->d_pstart && R->d_kcount && R->d_rows && R->d_bits;
+  if (R->last) {
+    R->d_kmers = (u32*)ctx->dalloc(4ull * n_seqs);
+    R->d_hits = K->hits;
+    if (!R->d_hits) R->d_hits = R->d_hits_own = (u32*)ctx->dalloc(4 * table);
+    ok = ok && R->d_kmers && R->d_hits;
+  }
+  if (!ok) return ctx->fail(KMX_E_NOMEM, "kmx_zquery: device allocation failed");
+  KMX_HIP(ctx, hipMemcpyAsync((void*)R->d_rows, (const void*)R->h_rows, 8ull * P, hipMemcpyHostToDevice, st));
+  if (ctx->profiling) {
+    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
+    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
+  }
+  KMX_HIP(ctx, hipMemsetAsync(R->d_cell, 0, 4 * cells, st));
+  KMX_HIP(ctx, hipMemsetAsync(R->d_pstart, 0, 4ull * (P + 1), st));
+  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kcount, 0, 4ull * n_seqs, st));
+  if (R->d_bits_own && bits_bytes) KMX_HIP(ctx, hipMemsetAsync(R->d_bits_own, 0, bits_bytes, st));
+  if (R->last && n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
+  if (R->d_hits_own && table) KMX_HIP(ctx, hipMemsetAsync(R->d_hits_own, 0, 4 * table, st));
+  if (n_bases) {
+    KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
+                                   n_tiles, n_chunks, tpc, R->d_keys, R->d_cell, R->d_kcount, st));
+    KMX_HIP(ctx, launch_filter_scan(R->d_cell, (u32)(cells - 1), st));
+    KMX_HIP(ctx, launch_query_parts(R->d_cell, P, n_chunks, R->d_pstart, st));
+    KMX_HIP(ctx, launch_zquery_scatter(R->d_keys, n_bases, n_tiles, n_chunks, tpc, R->d_cell, R->d_recs, st));
+    KMX_HIP(ctx, launch_zquery_rows(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, nb, N, R->d_bits, (u32)ctx->n_cu, st));
+    if (R->last)
+      KMX_HIP(ctx, launch_zquery_window(R->d_keys, (const u64*)K->offsets, n_seqs, n_bases, K->z, R->d_bits, nb, N, R->d_kmers, R->d_hits, (u32)ctx->n_cu, st));
+  }
+  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
+  KMX_HIP(ctx, hipMemcpyAsync(R->h_pstart, R->d_pstart, 4ull * (P + 1), hipMemcpyDeviceToHost, st));
+  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
+  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
+  return KMX_OK;
+}
+
+static kmx_zquery_result* zquery_new(kmx_ctx* ctx, const kmx_zquery_task* K, u64 n_bases)
+{
+  kmx_zquery_result* R = new kmx_zquery_result();
+  R->ctx = ctx; R->n_seqs = K->n_seqs; R->n_bases = n_bases; R->n_cols = K->n_cols; R->nb = (K->n_cols + 7) / 8; R->n_parts = K->nb_parts;
+  R->pitch = (u32)kmx_zquery_bits_bytes(1, K->n_cols); R->z = K->z; R->last = K->last != 0;
+  return R;
+}
+
+extern "C" int kmx_zquery_dev(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out)
+{
+  if (!ctx) return KMX_E_INVAL;
+  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_zquery_dev: null argument");
+  *out = nullptr;
+  int rc = zquery_check(ctx, task, "kmx_zquery_dev");
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipSetDevice(ctx->device));
+  u64 ends[1] = {0};      // the grid's size: the end of the last query
+  KMX_HIP(ctx, hipMemcpyAsync(ends, task->offsets + task->n_seqs, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = zquery_check_bases(ctx, task, ends[0], "kmx_zquery_dev")) != KMX_OK) return rc;
+  kmx_zquery_result* R = zquery_new(ctx, task, ends[0]);
+  if ((rc = zquery_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); zquery_release(R); return rc; }
+  *out = R;
+  return KMX_OK;
+}
+
+extern "C" int kmx_zquery_host(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out)
+{
+  if (!ctx) return KMX_E_INVAL;
+  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: null argument");
+  *out = nullptr;
+  int rc = zquery_check(ctx, task, "kmx_zquery_host");
+  if (rc != KMX_OK) return rc;
+  const u64 n_bases = task->offsets[task->n_seqs];
+  if (task->offsets[0] != 0) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: offsets[0] must be 0");
+  for (u64 i = 0; i < task->n_seqs; i++) if (task->offsets[i] > task->offsets[i + 1]) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: offsets must not descend");
+  if ((rc = zquery_check_bases(ctx, task, n_bases, "kmx_zquery_host")) != KMX_OK) return rc;
+  KMX_HIP(ctx, hipSetDevice(ctx->device));
+  kmx_zquery_result* R = zquery_new(ctx, task, n_bases);
+  kmx_zquery_task dt = *task;
+  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
+  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); zquery_release(R); return code; };
+  hipError_t e = hipSuccess;
+  auto upload = [&](const void* src, u64 bytes) -> void* {
+    void* d = ctx->dalloc(bytes);
+    if (!d) return nullptr;
+    R->d_in.push_back(d);
+    if (bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->up);
+    return d;
+  };
+  const u64 row_bytes = task->window * ((task->n_cols + 7) / 8);
+  if (!(dt.bases = (const char*)upload(task->bases, n_bases)) || !(dt.offsets = (const uint64_t*)upload(task->offsets, 8 * (task->n_seqs + 1))) ||
+      !(dt.repart = (const uint16_t*)upload(task->repart, 2ull << (2 * task->minim_size))))
+    return fail(ctx->fail(KMX_E_NOMEM, "kmx_zquery_host: upload allocation failed"));
+  for (u32 p = 0; p < task->nb_parts; p++) {
+    if (!task->rows[p]) continue;
+    if (!(drows[p] = (const uint8_t*)upload(task->rows[p], row_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_zquery_host: upload allocation failed"));
+  }
+  dt.rows = drows.data();
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
+  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_zquery_host: upload: ") + hipGetErrorString(e)));
+  if ((rc = zquery_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
+  *out = R;
+  return KMX_OK;
+}
+
+extern "C" int kmx_zquery_result_wait(kmx_zquery_result* R)
+{
+  if (!R) return KMX_E_INVAL;
+  if (R->waited) return R->status;
+  R->waited = true;
+  const hipError_t e = hipEventSynchronize(R->ev_done);
+  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_zquery: ") + hipGetErrorString(e));
+  // the call has run: its scratch and uploads go back to the pool; the bits table (when the result owns it), n_kmers and hits stay
+  kmx_ctx* c = R->ctx;
+  void* scratch[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kcount, (void*)R->d_rows};
+  for (void* p : scratch) c->dfree(p);
+  R->d_keys = R->d_recs = nullptr; R->d_cell = R->d_pstart = R->d_kcount = nullptr; R->d_rows = nullptr;
+  for (void* p : R->d_in) c->dfree(p);
+  R->d_in.clear();
+  c->hfree((void*)R->h_rows); R->h_rows = nullptr;
+  return R->status = KMX_OK;
+}
+extern "C" uint64_t kmx_zquery_result_n_seqs(const kmx_zquery_result* R) { return R ? R->n_seqs : 0; }
+static int zquery_copy_out(kmx_zquery_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries)
+{
+  const int rc = kmx_zquery_result_wait(R);
+  if (rc != KMX_OK) return rc;
+  if (!R->last) return R->ctx->fail(KMX_E_INVAL, "kmx_zquery: n_kmers and hits belong to the last call of a series");
+  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
+  if (!entries) return KMX_OK;
+  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
+  return kmx_copy_to_host(R->ctx, dst, src, 4 * entries);
+}
+extern "C" int kmx_zquery_result_copy_kmers(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs) : KMX_E_INVAL; }
+extern "C" int kmx_zquery_result_copy_hits(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols) : KMX_E_INVAL; }
+extern "C" uint32_t* kmx_zquery_result_hits_dev(kmx_zquery_result* R) { return R && R->last && kmx_zquery_result_wait(R) == KMX_OK ? R->d_hits : nullptr; }
+extern "C" uint8_t* kmx_zquery_result_bits_dev(kmx_zquery_result* R) { return R && kmx_zquery_result_wait(R) == KMX_OK ? R->d_bits : nullptr; }
+extern "C" double kmx_zquery_result_kernel_ms(kmx_zquery_result* R)
+{
+  if (!R || !R->ev0 || !R->ev1 || kmx_zquery_result_wait(R) != KMX_OK) return -1.0;
+  float ms = 0;
+  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
+}
+extern "C" uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* R)
+{
+  if (!R || kmx_zquery_result_wait(R) != KMX_OK) return 0;
+  u64 found = 0;
+  for (u32 p = 0; p < R->n_parts; p++) if (R->in_call[p]) found += R->h_pstart[p + 1] - R->h_pstart[p];
+  u64 bytes = R->n_bases + found * ((u64)R->nb + R->pitch);
+  if (R->last) {
+    std::vector<u32> nk(R->n_seqs);
+    if (R->n_seqs && kmx_copy_to_host(R->ctx, nk.data(), R->d_kmers, 4 * R->n_seqs) != KMX_OK) return 0;
+    u64 rows = 0;
+    for (u32 n : nk) if (n) rows += (u64)n + R->z;
+    bytes += rows * R->pitch + 4 * R->n_seqs * R->n_cols;
+  }
+  return bytes;
+}
+extern "C" void kmx_zquery_result_free(kmx_zquery_result* R)
+{
+  if (!R) return;
+  (void)hipSetDevice(R->ctx->device);
+  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
+  zquery_release(R);
+}
+
 // ---- kquery ------------------------------------------------------------------------------------------------------------------------
 // kmx_kquery_dev / kmx_kquery_host: query sequences against the k-mer matrices of a run (kquery.hip).
 struct kmx_kquery_result {

@@ -116,6 +116,13 @@ hipError_t launch_kquery_search(int kw, u64* recs, u64 rec_bound, const u32* pst
 hipError_t launch_kquery_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u64 stride, u32 skip,
                                 u32 n_cols, u32* hits, u64* sums /* or null */, u32 n_cu, hipStream_t st);
 
+// zquery.hip: the findere trick over the Bloom matrices of a run (kmx_zquery_dev); keys, scan and launch_query_parts are query.hip's
+hipError_t launch_zquery_scatter(const u64* keys, u64 n_bases, u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk, u32* cell, u64* recs /* (row, position) */,
+                                 hipStream_t st);
+hipError_t launch_zquery_rows(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 n_cols,
+                              u8* bits /* [n_bases] rows of 4 * ceil(nb / 4) bytes */, u32 n_cu, hipStream_t st);
+hipError_t launch_zquery_window(const u64* keys, const u64* offsets, u32 n_seqs, u64 n_bases, u32 z, const u8* bits, u32 nb, u32 n_cols,
+                                u32* n_kmers /* zeroed */, u32* hits, u32 n_cu, hipStream_t st);
 }  // namespace kmx
 
 // ---- split -> count without the super-k-mer streams leaving HBM (kmx_count_reads): superk.hip hands the packed, partition-ordered

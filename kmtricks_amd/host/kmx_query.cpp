@@ -3,6 +3,7 @@
 // run directory as `kmx pipeline` / kmtricks leave it; the queries go through kmx_query_host in batches, the partitions' matrices in
 // groups that fit the device, a group's hits added on the device to the table of the groups before it.  Every check that needs no
 // GPU comes before kmx_create.  `--kmer-index` asks the same of the k-mer matrices of a kmer:count:bin / kmer:pa:bin run (kquery_main).
+// `--z Z` asks the Bloom index for (k + Z)-mers (the findere trick: kmx_zquery_host, one bits table a batch across its partition groups).
 #include <kmx.h>
 #include <algorithm>
 #include <cstring>
@@ -21,12 +22,13 @@ struct QOpt {
   double threshold = 0.7;
   uint32_t gpus = 1, threads = 8;
   uint64_t batch_mb = 0;      // 0: sized from the device's free memory
+  int64_t z = -1;             // --z: (k + z)-mers, the findere trick (zquery_batch); < 0: not given
   bool verbose = false;
 };
 
 const char* USAGE = "usage: kmx query (--index <run dir made with --mode hash:bf:bin> | --kmer-index <run dir made with --mode kmer:count:bin or kmer:pa:bin>) "
                     "--query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] [--format matrix|list|sums (sums: --kmer-index of a count run)] "
-                    "[--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
+                    "[--z INT (--index only: ask for (k + z)-mers, 0 ... 8)] [--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
 
 QOpt parse(int argc, char** argv)
 {
@@ -42,6 +44,7 @@ QOpt parse(int argc, char** argv)
     else if (a == "--threshold") { const std::string v = need(i); try { size_t n = 0; o.threshold = std::stod(v, &n); if (n != v.size()) throw 1; } catch (...) { die("bad number for --threshold: " + v); } }
     else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list" && o.format != "sums") die("--format must be matrix, list or sums"); }
     else if (a == "--gpus") o.gpus = num(i);
+    else if (a == "--z") { const unsigned long v = num(i); if (v > 8) die("--z must be in [0, 8]"); o.z = (int64_t)v; }
     else if (a == "--query-batch-mb") o.batch_mb = num(i);
     else if (a == "-t" || a == "--threads") o.threads = num(i);
     else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
@@ -52,6 +55,8 @@ QOpt parse(int argc, char** argv)
   if (o.query.empty()) die(std::string("--query is required\n") + USAGE);
   if (o.gpus < 1 || o.gpus > 16) die("--gpus must be in [1, 16]");
   if (o.threshold < 0.0 || o.threshold > 1.0) die("--threshold must be in [0, 1]");
+  if (o.z >= 0 && !o.kmer_index.empty()) die("--z removes Bloom false positives: an exact index (--kmer-index) has none");
+  if (o.z >= 0 && o.gpus > 1) die("--z with --gpus above 1 is not supported: shards own partitions, a window's k-mers lie in several shards, and the shards' tables are not joined across devices");
   return o;
 }
 
@@ -265,6 +270,7 @@ int kmx_query_main(int argc, char** argv)
   if (mode != "hash:bf:bin") die("kmx query --index needs a run made with --mode hash:bf:bin; " + o.index + " was made with " + mode + (mode == "kmer:count:bin" || mode == "kmer:pa:bin" ? " (a k-mer run: --kmer-index)" : ""));
   uint32_t k = 0;
   try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(o.index + "/options.txt names no kmer_size"); }
+  if (o.z >= (int64_t)k) die("--z must be below the index's k-mer size (" + std::to_string(k) + ")");
   uint64_t W = 0, P = 0; uint32_t msize = 0;
   { std::vector<uint8_t> hi = slurp(o.index + "/hash.info");
     if (hi.size() < 36) die(o.index + "/hash.info: Invalid file format.");
@@ -313,10 +319,12 @@ int kmx_query_main(int argc, char** argv)
   // batch holds its table and n_kmers only while the later groups run
   const uint64_t group_parts = std::max<uint64_t>(1, (budget / 2) / std::max<uint64_t>(body, 1));
   const uint64_t batch_bytes = std::max<uint64_t>(budget / 2, 1);
+  // (--z: and a row of the position-major bits table a base, kept from a batch's first group to its last)
+  const uint64_t per_base = 17 + (o.z >= 0 ? kmx_zquery_bits_bytes(1, N) : 0);
   std::vector<uint64_t> cut{0};      // batch b = queries [cut[b], cut[b + 1])
   { uint64_t used = 0;
     for (uint64_t q = 0; q < Q; q++) {
-      const uint64_t len = offs[q + 1] - offs[q], cost = 17 * len + 4ull * N + 12;
+      const uint64_t len = offs[q + 1] - offs[q], cost = per_base * len + 4ull * N + 12;
       if (len > 0xFFFFFFFFull) die("query " + names[q] + " has 2^32 bases or more");
       if (q > cut.back() && (used + cost > batch_bytes || offs[q + 1] - offs[cut.back()] > 0xFFFFFFFFull)) { cut.push_back(q); used = 0; }
       used += cost;
@@ -381,10 +389,52 @@ int kmx_query_main(int argc, char** argv)
         kmers = sk;      // (every shard walks every query: the same numbers)
       } catch (const std::exception& e) { die(e.what()); }
     };
-    std::vector<std::thread> workers;
-    for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
-    shard(0);
-    for (std::thread& w : workers) w.join();
+    // --z: one shard; the groups of a batch fill one bits table on the device, the batch's last group runs the window pass.
+    // n_kmers are K-positions
+    auto zshard = [&]() {
+      kmx_ctx* ctx = ctxs[0];
+      kmx_zquery_result* first = nullptr;
+      std::vector<std::vector<uint8_t>> own;
+      const bool keep = groups[0].size() == 1;
+      std::vector<std::vector<uint8_t>>& bodies = keep ? kept[0] : own;
+      std::vector<const uint8_t*> rows(P);
+      for (size_t gi = 0; gi < groups[0].size(); gi++) {
+        std::fill(rows.begin(), rows.end(), nullptr);
+        const bool loaded = keep && bodies.size() == groups[0][gi].size();
+        if (!loaded) bodies.assign(groups[0][gi].size(), std::vector<uint8_t>());
+        for (size_t i = 0; i < groups[0][gi].size(); i++) {
+          const uint32_t p = groups[0][gi][i];
+          if (!loaded) {
+            std::ifstream f(files[p], std::ios::binary);
+            bodies[i].resize(body);
+            if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
+          }
+          rows[p] = bodies[i].data();
+        }
+        const bool last = gi + 1 == groups[0].size();
+        kmx_zquery_task t; memset(&t, 0, sizeof t);
+        t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+        t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
+        t.rows = rows.data(); t.z = (uint32_t)o.z; t.last = last ? 1 : 0;
+        t.bits = first ? kmx_zquery_result_bits_dev(first) : nullptr;
+        kmx_zquery_result* r = nullptr;
+        chk(ctx, kmx_zquery_host(ctx, &t, &r), "kmx_zquery_host");
+        chk(ctx, kmx_zquery_result_wait(r), "kmx_zquery");      // (the bodies are reused by the next group)
+        if (last) {
+          chk(ctx, kmx_zquery_result_copy_hits(r, hits.data(), hits.size()), "kmx_zquery_result_copy_hits");
+          chk(ctx, kmx_zquery_result_copy_kmers(r, kmers.data(), kmers.size()), "kmx_zquery_result_copy_kmers");
+        }
+        if (!first) first = r; else kmx_zquery_result_free(r);      // (the first result owns the table)
+      }
+      kmx_zquery_result_free(first);
+    };
+    if (o.z >= 0) { try { zshard(); } catch (const std::exception& e) { die(e.what()); } }
+    else {
+      std::vector<std::thread> workers;
+      for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
+      shard(0);
+      for (std::thread& w : workers) w.join();
+    }
     std::string txt;
     for (uint64_t i = 0; i < nq; i++) {
       const std::string& name = names[q0 + i];

@@ -52,6 +52,13 @@ class KmxQueryTask(C.Structure):
                 ("window", C.c_uint64), ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p)]
 
 
+class KmxZqueryTask(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("kmer_size", C.c_uint32),
+                ("minim_size", C.c_uint32), ("repart", C.c_void_p), ("nb_parts", C.c_uint32), ("n_cols", C.c_uint32),
+                ("window", C.c_uint64), ("rows", C.POINTER(C.c_void_p)), ("z", C.c_uint32), ("last", C.c_uint32),
+                ("bits", C.c_void_p), ("hits", C.c_void_p)]
+
+
 class KmxKqueryTask(C.Structure):
     _fields_ = [("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("kmer_size", C.c_uint32),
                 ("minim_size", C.c_uint32), ("repart", C.c_void_p), ("nb_parts", C.c_uint32), ("n_cols", C.c_uint32),
@@ -227,6 +234,31 @@ _lib.kmx_kquery_result_free.argtypes = [_vp]
 KQUERY_EXPORTS = ["kmx_kquery_dev", "kmx_kquery_host", "kmx_kquery_result_wait", "kmx_kquery_result_n_seqs", "kmx_kquery_result_copy_kmers",
                   "kmx_kquery_result_copy_hits", "kmx_kquery_result_copy_sums", "kmx_kquery_result_hits_dev", "kmx_kquery_result_sums_dev",
                   "kmx_kquery_result_kernel_ms", "kmx_kquery_result_algo_bytes", "kmx_kquery_result_free"]
+
+_lib.kmx_zquery_bits_bytes.restype = C.c_uint64
+_lib.kmx_zquery_bits_bytes.argtypes = [C.c_uint64, C.c_uint32]
+_lib.kmx_zquery_dev.argtypes = [_vp, C.POINTER(KmxZqueryTask), C.POINTER(_vp)]
+_lib.kmx_zquery_host.argtypes = [_vp, C.POINTER(KmxZqueryTask), C.POINTER(_vp)]
+_lib.kmx_zquery_result_wait.argtypes = [_vp]
+for _f in ("kmx_zquery_result_n_seqs", "kmx_zquery_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_zquery_result_copy_kmers", "kmx_zquery_result_copy_hits"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_zquery_result_hits_dev", "kmx_zquery_result_bits_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_zquery_result_kernel_ms.restype = C.c_double
+_lib.kmx_zquery_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_zquery_result_free.argtypes = [_vp]
+ZQUERY_EXPORTS = ["kmx_zquery_bits_bytes", "kmx_zquery_dev", "kmx_zquery_host", "kmx_zquery_result_wait", "kmx_zquery_result_n_seqs",
+                  "kmx_zquery_result_copy_kmers", "kmx_zquery_result_copy_hits", "kmx_zquery_result_hits_dev", "kmx_zquery_result_bits_dev",
+                  "kmx_zquery_result_kernel_ms", "kmx_zquery_result_algo_bytes", "kmx_zquery_result_free"]
+
+
+def zquery_bits_bytes(n_bases, n_cols):
+    """bytes of the bits table a series of zquery calls shares: n_bases rows of 4 * ceil(ceil(n_cols / 8) / 4) bytes"""
+    return _lib.kmx_zquery_bits_bytes(n_bases, n_cols)
 
 
 def filter_want(want):
@@ -687,6 +719,56 @@ class Context:
         finally:
             r.free()
 
+    @staticmethod
+    def _zquery_result(r, last, keep, owns_bits):
+        if keep:
+            return r
+        if not last and owns_bits:
+            r.free()
+            raise ValueError("a call that opens a series (bits_dev=None, last=False) owns the series' table: keep=True")
+        try:
+            return r.output() if last else None
+        finally:
+            r.free()
+
+    def zquery(self, reads, k, m, repart, window, n_cols, matrices, z, bits_dev=None, hits_dev=None, last=True, keep=False):
+        """kmx_zquery_host: as query, for (k + z)-mers (the findere trick): a position counts for a sample when the rows of its z + 1
+        overlapping k-mers all have the sample's bit.  A series of calls over the same reads, each with other partitions in
+        `matrices`, shares one device table: the first call has bits_dev=None and keep=True (its result owns the table: .bits_dev()),
+        the later ones pass that pointer, the one with last=True produces the result.  hits_dev None or a device pointer to a uint32
+        table [queries, n_cols] the last call adds to.
+        -> QueryOutput (numpy copies) when last, else None; with keep the ZqueryResult itself (.free() it)"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        rep = np.ascontiguousarray(repart, dtype=np.uint16)
+        nb = (n_cols + 7) // 8
+        keepalive, rows = [], (C.c_void_p * len(matrices))()
+        for p, mt in enumerate(matrices):
+            if mt is None:
+                continue
+            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+            if len(a) != window * nb:
+                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
+            keepalive.append(a)
+            rows[p] = a.ctypes.data
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        t = KmxZqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows,
+                          z, 1 if last else 0, bits_dev, hits_dev)
+        res = _vp()
+        self._check(_lib.kmx_zquery_host(self._h, C.byref(t), C.byref(res)), "kmx_zquery_host")
+        r = ZqueryResult(self, res, n_cols)
+        r.wait()      # (the host buffers above may go once the call has run)
+        return self._zquery_result(r, last, keep, bits_dev is None)
+
+    def zquery_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, window, n_cols, rows_dev, z, bits_dev=None, hits_dev=None, last=True, keep=False):
+        """kmx_zquery_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
+        repartition table; rows_dev[p] a device pointer to partition p's matrix body or None.  -> as zquery"""
+        rows = (C.c_void_p * len(rows_dev))(*rows_dev)
+        t = KmxZqueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, window, rows, z, 1 if last else 0, bits_dev, hits_dev)
+        res = _vp()
+        self._check(_lib.kmx_zquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_zquery_dev")
+        return self._zquery_result(ZqueryResult(self, res, n_cols), last, keep, bits_dev is None)
+
     def kquery(self, reads, k, m, repart, n_cols, key_words, mode, matrices, n_rows=None, hits_dev=None, sums=False, keep=False):
         """kmx_kquery_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
         .count / .pa (bytes or a uint8 array of whole rows: key words, then n_cols u32 counts or ceil(n_cols / 8) bytes) or None (the
@@ -892,6 +974,51 @@ class KqueryResult:
     def free(self):
         if self._h:
             _lib.kmx_kquery_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ZqueryResult:
+    """a call of a zquery series: bits_dev() the series' table; hits_dev() and output() on the last call only"""
+
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_zquery_result_wait(self._h), "kmx_zquery_result_wait")
+
+    def n_seqs(self):
+        return _lib.kmx_zquery_result_n_seqs(self._h)
+
+    def hits_dev(self):
+        return _lib.kmx_zquery_result_hits_dev(self._h)
+
+    def bits_dev(self):
+        return _lib.kmx_zquery_result_bits_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_zquery_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_zquery_result_algo_bytes(self._h)
+
+    def output(self):
+        """-> QueryOutput: n_kmers the K-positions of every query, hits those whose z + 1 rows all have the sample's bit"""
+        self.wait()
+        q = self.n_seqs()
+        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
+        self._ctx._check(_lib.kmx_zquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_zquery_result_copy_kmers")
+        self._ctx._check(_lib.kmx_zquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_zquery_result_copy_hits")
+        return QueryOutput(nk, hits, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_zquery_result_free(self._h)
             self._h = None
 
     def __del__(self):
