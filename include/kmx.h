@@ -28,6 +28,8 @@
  *                               kmer:pa:bin run -- exact, with abundances (k-mer, minimizer and partition as kmx_query_* has them)
  *   kmx_zquery_dev / _host      no counterpart either: kmx_query_*'s question asked for (k + z)-mers, the findere trick against Bloom
  *                               false positives -- a position counts for a sample when its z + 1 overlapping k-mers all do
+ *   kmx_dist_dev / _host        no counterpart either (Simka's question): the sample-by-sample shared k-mer tables of a run's matrices --
+ *                               rows that hold both samples, sums of the smaller count -- which the Jaccard and Bray-Curtis distances follow from
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -522,6 +524,66 @@ double   kmx_zquery_result_kernel_ms(kmx_zquery_result* r);
  * that has any) * pitch (table rows read by the window pass) + 4 * n_seqs * n_cols (the hits table written) */
 uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* r);
 void     kmx_zquery_result_free(kmx_zquery_result* r);
+
+/* ------------------------------------------------------------------- dist */
+
+/* How the samples of a matrix relate to each other: the shared k-mer tables that the Jaccard and Bray-Curtis distances follow from
+ * (what Simka computes on the CPU).  Input: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is 8 * key_words key bytes, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ *                                      (.pa and .pa_hash bodies)
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is the key, then N u32 counts; column i is present when its count is non-zero
+ *                                      (.count and .count_hash bodies)
+ *   key_words 0,       KMX_MODE_BF     a row is ceil(N / 8) bytes and has no key (.cmbf bodies)
+ * Keys are never read.  The padding bits of a row's last byte never reach a result.  `rows` needs no alignment (a PA row of a
+ * one-word key and 13 bytes is 21 bytes long).  Outputs: N x N tables of u64, row-major, the full square with both triangles written:
+ *   inter[i * N + j]  the number of rows in which columns i and j are both present; the diagonal is the number of rows that hold sample i
+ *   mins[i * N + j]   (COUNT with want_mins only) the sum over the rows of min(count_i, count_j); the diagonal is the sum of sample i's counts
+ * The call ADDS to the tables it is given: inter / mins are NULL (the result owns a zeroed table) or DEVICE tables of N * N u64.  The
+ * partitions of a run, and the row runs of a partition, accumulate on the device in any order: integer adds commute, so the tables depend
+ * neither on the order nor on how the rows were cut.  n_rows = 0 is legal and adds nothing.
+ * Examples.  PA, N = 3, rows with bits (column 0 = bit 0) 0b011, 0b101, 0b111, 0b000: inter = [[3,2,2],[2,2,1],[2,1,2]].
+ * COUNT, rows (1,2,0), (5,0,7), (3,3,3): the same inter; mins = [[9,4,8],[4,5,3],[8,3,10]]; the Jaccard distance of samples 0 and 1 is
+ * 1 - 2 / (3 + 2 - 2) = 0.333333, their Bray-Curtis distance 1 - 2 * 4 / (9 + 5) = 0.428571.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols = 0; a mode other than COUNT, PA or BF; key_words > 4; key_words = 0
+ * with a mode other than BF; BF with key_words != 0; want_mins, or a mins table, outside COUNT; a mins table without want_mins.
+ * KMX_E_UNSUPPORTED: n_cols > 32768 (a table would be 8 GiB); a row of 4 GiB or more; KMX_MODE_BFC and KMX_MODE_BFT.
+ * Scratch from the context's pool: round_up64(N) / 8 bytes per row (rows rounded up to 64) -- the presence bits, sample-major in blocks
+ * of 64 samples, which the pair kernel reads -- and, for kmx_dist_host, the uploaded rows.  Send a body that does not fit in runs of rows. */
+typedef struct {
+  uint32_t    key_words;     /* 0 (BF) ... 4 */
+  uint32_t    mode;          /* KMX_MODE_COUNT | KMX_MODE_PA | KMX_MODE_BF */
+  uint32_t    n_cols;        /* N: samples of the matrix */
+  uint32_t    want_mins;     /* non-zero: mins is computed (KMX_MODE_COUNT only) */
+  const void* rows;
+  uint64_t    n_rows;
+  uint64_t*   inter;         /* NULL, or a device table to accumulate into */
+  uint64_t*   mins;          /* NULL, or (with want_mins) a device table to accumulate into */
+} kmx_dist_task;
+
+typedef struct kmx_dist_result kmx_dist_result;
+
+/* every pointer a DEVICE pointer -- rows may be kmx_result_body_dev of a merge result, a filter's or a combine's body, the caller's own
+ * memory.  The kernels are queued on the context's stream (kmx_stream), behind whatever produced the rows there, and the call returns
+ * without waiting; the tables stay in HBM until the result is freed (tables of the caller's are the caller's). */
+int kmx_dist_dev(kmx_ctx* ctx, const kmx_dist_task* task, kmx_dist_result** out);
+/* rows a HOST pointer (inter and mins, when given, are still device tables): the rows are uploaded on a stream of their own, so a run
+ * travels while the run before it is worked on.  The host buffer may be reused once kmx_dist_result_wait has returned. */
+int kmx_dist_host(kmx_ctx* ctx, const kmx_dist_task* task, kmx_dist_result** out);
+int       kmx_dist_result_wait(kmx_dist_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t* kmx_dist_result_inter_dev(kmx_dist_result* r);      /* the table as it stands: the result's own or the task's */
+uint64_t* kmx_dist_result_mins_dev(kmx_dist_result* r);       /* NULL without want_mins */
+int       kmx_dist_result_copy_inter(kmx_dist_result* r, uint64_t* host_dst, uint64_t dst_entries);   /* N * N entries */
+int       kmx_dist_result_copy_mins(kmx_dist_result* r, uint64_t* host_dst, uint64_t dst_entries);    /* N * N; KMX_E_INVAL without want_mins */
+/* duration in ms of the call's kernels, the clearing of the tables the result owns included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_dist_result_kernel_ms(kmx_dist_result* r);
+/* the same interval in its parts: clearing + k_dist_slab, k_dist_pairs, k_dist_mins (-1 without want_mins); any pointer may be NULL */
+int       kmx_dist_result_kernel_parts_ms(kmx_dist_result* r, double* slab_ms, double* pairs_ms, double* mins_ms);
+/* algorithmic bytes: the body read once (n_rows * row bytes) + the presence bits written and read once (2 * round_up64(N) / 8 *
+ * round_up64(n_rows)) + the inter table written (8 * N * N); with want_mins the counts read once more (4 * N * n_rows) and the mins
+ * table written */
+uint64_t  kmx_dist_result_algo_bytes(kmx_dist_result* r);
+void      kmx_dist_result_free(kmx_dist_result* r);
 
 /* ------------------------------------------------------------------ count */
 

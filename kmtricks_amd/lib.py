@@ -66,6 +66,11 @@ class KmxKqueryTask(C.Structure):
                 ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p), ("sums", C.c_void_p), ("want_sums", C.c_uint32)]
 
 
+class KmxDistTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("want_mins", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("inter", C.c_void_p), ("mins", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -254,6 +259,24 @@ _lib.kmx_zquery_result_free.argtypes = [_vp]
 ZQUERY_EXPORTS = ["kmx_zquery_bits_bytes", "kmx_zquery_dev", "kmx_zquery_host", "kmx_zquery_result_wait", "kmx_zquery_result_n_seqs",
                   "kmx_zquery_result_copy_kmers", "kmx_zquery_result_copy_hits", "kmx_zquery_result_hits_dev", "kmx_zquery_result_bits_dev",
                   "kmx_zquery_result_kernel_ms", "kmx_zquery_result_algo_bytes", "kmx_zquery_result_free"]
+
+_lib.kmx_dist_dev.argtypes = [_vp, C.POINTER(KmxDistTask), C.POINTER(_vp)]
+_lib.kmx_dist_host.argtypes = [_vp, C.POINTER(KmxDistTask), C.POINTER(_vp)]
+_lib.kmx_dist_result_wait.argtypes = [_vp]
+_lib.kmx_dist_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_dist_result_algo_bytes.argtypes = [_vp]
+for _f in ("kmx_dist_result_copy_inter", "kmx_dist_result_copy_mins"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_dist_result_inter_dev", "kmx_dist_result_mins_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_dist_result_kernel_ms.restype = C.c_double
+_lib.kmx_dist_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_dist_result_kernel_parts_ms.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+_lib.kmx_dist_result_free.argtypes = [_vp]
+DIST_EXPORTS = ["kmx_dist_dev", "kmx_dist_host", "kmx_dist_result_wait", "kmx_dist_result_inter_dev", "kmx_dist_result_mins_dev",
+                "kmx_dist_result_copy_inter", "kmx_dist_result_copy_mins", "kmx_dist_result_kernel_ms", "kmx_dist_result_kernel_parts_ms",
+                "kmx_dist_result_algo_bytes", "kmx_dist_result_free"]
 
 
 def zquery_bits_bytes(n_bases, n_cols):
@@ -825,6 +848,51 @@ class Context:
             r.free()
 
     @staticmethod
+    def _dist_mins(mins):
+        return (1, None) if mins is True else (0, None) if mins is False or mins is None else (1, mins)
+
+    def dist(self, body, n_rows, n_cols, key_words, mode, mins=False, inter_dev=None, mins_dev=None, keep=False):
+        """kmx_dist_host: body the bytes (or a uint8 array) of n_rows whole rows of one partition's matrix (None: from the body's size):
+        key words, then n_cols u32 counts (MODE_COUNT) or ceil(n_cols / 8) bytes (MODE_PA; MODE_BF with key_words 0).  mins: the
+        min-count table is computed too (MODE_COUNT).  inter_dev / mins_dev: None (the result owns a zeroed table) or a device pointer
+        to a uint64 table [n_cols, n_cols] the call adds to (mins_dev implies mins).
+        -> DistOutput (numpy copies), or with keep the DistResult itself (the tables left in HBM; .free() it)"""
+        a = np.frombuffer(body, dtype=np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+        stride = key_words * 8 + (4 * n_cols if mode == MODE_COUNT else (n_cols + 7) // 8)
+        if n_rows is None:
+            if stride == 0 or len(a) % stride:
+                raise ValueError(f"{len(a)} bytes are not whole rows of {stride} bytes")
+            n_rows = len(a) // stride
+        elif len(a) < n_rows * stride:
+            raise ValueError(f"{len(a)} bytes are fewer than {n_rows} rows of {stride} bytes")
+        want, md = self._dist_mins(mins_dev if mins_dev is not None else mins)
+        t = KmxDistTask(key_words, mode, n_cols, want, a.ctypes.data if len(a) else None, n_rows, inter_dev, md)
+        res = _vp()
+        self._check(_lib.kmx_dist_host(self._h, C.byref(t), C.byref(res)), "kmx_dist_host")
+        r = DistResult(self, res, n_cols, bool(want))
+        r.wait()      # (the host buffer above may go once the call has run)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def dist_dev(self, rows_dev, n_rows, n_cols, key_words, mode, mins=False, inter_dev=None, mins_dev=None, keep=False):
+        """kmx_dist_dev: rows_dev a device pointer to n_rows rows (a torch tensor's data_ptr(), MergeResult.body_dev(), ...).  -> as dist"""
+        want, md = self._dist_mins(mins_dev if mins_dev is not None else mins)
+        t = KmxDistTask(key_words, mode, n_cols, want, rows_dev, n_rows, inter_dev, md)
+        res = _vp()
+        self._check(_lib.kmx_dist_dev(self._h, C.byref(t), C.byref(res)), "kmx_dist_dev")
+        r = DistResult(self, res, n_cols, bool(want))
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -926,6 +994,61 @@ class QueryOutput:
 
     def __init__(self, n_kmers, hits, kernel_ms, algo_bytes):
         self.n_kmers, self.hits, self.kernel_ms, self.algo_bytes = n_kmers, hits, kernel_ms, algo_bytes
+
+
+class DistOutput:
+    """inter uint64[n_cols, n_cols]: rows that hold both samples (the table the call added to, when one was given); mins
+    uint64[n_cols, n_cols] (None unless asked for): the sums of the smaller count; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, inter, mins, kernel_ms, algo_bytes):
+        self.inter, self.mins, self.kernel_ms, self.algo_bytes = inter, mins, kernel_ms, algo_bytes
+
+
+class DistResult:
+    def __init__(self, ctx, h, n_cols, has_mins):
+        self._ctx, self._h, self._n, self._mins = ctx, h, n_cols, has_mins
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_dist_result_wait(self._h), "kmx_dist_result_wait")
+
+    def inter_dev(self):
+        return _lib.kmx_dist_result_inter_dev(self._h)
+
+    def mins_dev(self):
+        return _lib.kmx_dist_result_mins_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_dist_result_kernel_ms(self._h)
+
+    def kernel_parts_ms(self):
+        """(clearing + k_dist_slab, k_dist_pairs, k_dist_mins) in ms; -1 where unavailable"""
+        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
+        self._ctx._check(_lib.kmx_dist_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_dist_result_kernel_parts_ms")
+        return a.value, b.value, c.value
+
+    def algo_bytes(self):
+        return _lib.kmx_dist_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        inter = np.zeros((self._n, self._n), np.uint64)
+        self._ctx._check(_lib.kmx_dist_result_copy_inter(self._h, inter.ctypes.data, inter.size), "kmx_dist_result_copy_inter")
+        mins = None
+        if self._mins:
+            mins = np.zeros((self._n, self._n), np.uint64)
+            self._ctx._check(_lib.kmx_dist_result_copy_mins(self._h, mins.ctypes.data, mins.size), "kmx_dist_result_copy_mins")
+        return DistOutput(inter, mins, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_dist_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class KqueryOutput:
