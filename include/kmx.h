@@ -30,6 +30,8 @@
  *                               false positives -- a position counts for a sample when its z + 1 overlapping k-mers all do
  *   kmx_dist_dev / _host        no counterpart either (Simka's question): the sample-by-sample shared k-mer tables of a run's matrices --
  *                               rows that hold both samples, sums of the smaller count -- which the Jaccard and Bray-Curtis distances follow from
+ *   kmx_colsums_dev / _host,    no counterpart either (kmdiff's question): the per-sample totals of a run's matrices, and the rows whose
+ *   kmx_diff_dev / _host        counts differ between case and control samples by a Poisson likelihood-ratio test, kept in file order
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -584,6 +586,114 @@ int       kmx_dist_result_kernel_parts_ms(kmx_dist_result* r, double* slab_ms, d
  * table written */
 uint64_t  kmx_dist_result_algo_bytes(kmx_dist_result* r);
 void      kmx_dist_result_free(kmx_dist_result* r);
+
+/* ------------------------------------------------------------------- diff */
+
+/* Differential k-mer analysis (what kmdiff does on top of kmtricks; no counterpart in the kmtricks tree): with the samples split into
+ * controls and cases, which rows of a matrix are significantly over- or under-represented in one group.
+ * INPUT: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts (.count and .count_hash bodies)
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3 (.pa, .pa_hash);
+ *                                      a sample's "count" is its bit
+ * `rows` needs no alignment.  The padding bits of a PA row never reach a result.  Keys are never read, only moved.
+ * group[N], a HOST array of u8, gives each column its group: 0 control, 1 case, 2 ignored.
+ *
+ * COLUMN SUMS (kmx_colsums_*): the call ADDS per column the sum of its counts (COUNT) or the number of rows that hold it (PA) into a
+ * table of N u64: a DEVICE table of the caller's, or NULL (the result owns a zeroed one).  Partitions and runs of rows accumulate in
+ * any order; n_rows = 0 adds nothing.  These are the per-sample totals T_i the test needs.
+ *
+ * THE TEST (kmx_diff_*): parameters total_ctrl = T0 and total_case = T1 (u64: the sums of T_i over each group, over the whole run),
+ * threshold (double), min_rec (u32).  Per row:
+ *   c0, c1 (u64)  the sums of the row's counts over the control / case columns
+ *   r0, r1 (u32)  the number of control / case columns that are non-zero
+ *   over          1 if c1 * T0 > c0 * T1, 2 if c1 * T0 < c0 * T1, 0 if equal -- compared in exact 128-bit integer arithmetic
+ *   stat          the Poisson likelihood-ratio statistic of "one rate" against "a rate per group" (the per-sample terms cancel: a
+ *                 function of c0, c1, T0, T1 alone).  With c = c0 + c1 and T = T0 + T1:
+ *                   stat = max(0, 2 * [ c1 * ln((c1 * T) / (c * T1)) + c0 * ln((c0 * T) / (c * T0)) ])
+ *                 a term whose c_g is 0 is 0; c = 0 gives 0.  All products, quotients and logs in IEEE double, evaluated in the order
+ *                 written (no fused multiply-add).
+ * A row is KEPT iff r0 + r1 >= min_rec and stat >= threshold.  Threshold 0 keeps every row that passes min_rec; +inf keeps none.
+ * OUTPUTS: the kept rows whole, in the input's order (a valid body of the same row size); one kmx_diff_rec per kept row in the same
+ * order; the count of kept rows.
+ * EXAMPLES.  N = 4, groups (0,0,1,1), T0 = T1 = 100:
+ *   row (0,0,5,5): c0 = 0, c1 = 10, stat = 20 ln 2 = 13.862943611198906, over = 1
+ *   row (3,3,3,3): stat = 0, over = 0
+ *   row (1,2,4,8): c0 = 3, c1 = 12, stat ~ 5.7823427, over = 1
+ * With threshold 3.841458820694126 (p = 0.05, one degree of freedom) rows 0 and 2 are kept, in that order.  Swapping the groups gives
+ * the same stats with over = 2.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols = 0; a mode other than COUNT or PA; key_words 0 or > 4; a group value
+ * > 2; no control column or no case column; total_ctrl or total_case = 0 (or their sum at 2^64 and above); a NaN or negative threshold.
+ * KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT; n_rows > 2^32 - 256 (the placement tiles are the filter's: 256 rows); a
+ * row of 4 GiB or more.
+ * SCRATCH from the context's pool, per kmx_diff call: a 4-byte keep word and a 40-byte record slot per input row, a 4-byte counter per
+ * 256 rows, the group table (N bytes; PA: 2 * ceil(N / 8) bytes of masks) -- all given back when the call has run; the outputs are
+ * sized for every row kept (n_rows * row bytes + 16, and 40 * n_rows) and live until the result is freed; for the _host calls the
+ * uploaded rows.  kmx_colsums: the table when the result owns it, and the upload.  Send a body that does not fit in runs of rows. */
+typedef struct {
+  uint32_t    key_words;     /* 1 ... 4 */
+  uint32_t    mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t    n_cols;        /* N: samples of the matrix */
+  uint32_t    reserved;      /* 0 */
+  const void* rows;
+  uint64_t    n_rows;
+  uint64_t*   sums;          /* NULL, or a device table of N u64 to accumulate into */
+} kmx_colsums_task;
+
+typedef struct {
+  uint32_t       key_words;     /* 1 ... 4 */
+  uint32_t       mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t       n_cols;        /* N: samples of the matrix */
+  uint32_t       min_rec;       /* a kept row has at least this many non-zero control + case columns */
+  const void*    rows;
+  uint64_t       n_rows;
+  const uint8_t* group;         /* HOST: N bytes, 0 control, 1 case, 2 ignored (copied by the call) */
+  uint64_t       total_ctrl;    /* T0 */
+  uint64_t       total_case;    /* T1 */
+  double         threshold;     /* a kept row has stat >= threshold */
+} kmx_diff_task;
+
+typedef struct {
+  uint64_t sum_ctrl;     /* c0 */
+  uint64_t sum_case;     /* c1 */
+  double   stat;
+  uint32_t rec_ctrl;     /* r0 */
+  uint32_t rec_case;     /* r1 */
+  uint32_t row;          /* index in the input */
+  uint32_t over;         /* 1 case, 2 control, 0 neither */
+} kmx_diff_rec;          /* 40 bytes */
+
+typedef struct kmx_colsums_result kmx_colsums_result;
+typedef struct kmx_diff_result kmx_diff_result;
+
+/* _dev: every pointer except `group` a DEVICE pointer -- rows may be kmx_result_body_dev of a merge result, a filter's or a combine's
+ * body, the caller's own memory.  The kernels are queued on the context's stream (kmx_stream) and the call returns without waiting.
+ * _host: rows a HOST pointer (sums, when given, is still a device table): the rows are uploaded on a stream of their own, so a run
+ * travels while the run before it is worked on.  The host buffer may be reused once _result_wait has returned. */
+int kmx_colsums_dev(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out);
+int kmx_colsums_host(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out);
+int       kmx_colsums_result_wait(kmx_colsums_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t* kmx_colsums_result_sums_dev(kmx_colsums_result* r);      /* the table as it stands: the result's own or the task's */
+int       kmx_colsums_result_copy_sums(kmx_colsums_result* r, uint64_t* host_dst, uint64_t dst_entries);   /* N entries */
+double    kmx_colsums_result_kernel_ms(kmx_colsums_result* r);     /* needs kmx_set_profiling(ctx, 1); < 0 if unavailable */
+/* algorithmic bytes: the body read once (n_rows * row bytes) + the table (8 * N) */
+uint64_t  kmx_colsums_result_algo_bytes(kmx_colsums_result* r);
+void      kmx_colsums_result_free(kmx_colsums_result* r);
+
+int kmx_diff_dev(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out);
+int kmx_diff_host(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out);
+int       kmx_diff_result_wait(kmx_diff_result* r);
+uint64_t  kmx_diff_result_rows(kmx_diff_result* r);                /* kept rows */
+uint64_t  kmx_diff_result_row_bytes(const kmx_diff_result* r);
+uint64_t  kmx_diff_result_body_bytes(kmx_diff_result* r);          /* rows * row_bytes */
+const void*         kmx_diff_result_body_dev(kmx_diff_result* r);  /* the kept rows, in HBM until the result is freed */
+int       kmx_diff_result_copy_body(kmx_diff_result* r, void* host_dst, uint64_t dst_bytes);
+const kmx_diff_rec* kmx_diff_result_recs_dev(kmx_diff_result* r);
+int       kmx_diff_result_copy_recs(kmx_diff_result* r, kmx_diff_rec* host_dst, uint64_t dst_entries);
+double    kmx_diff_result_kernel_ms(kmx_diff_result* r);
+/* algorithmic bytes: the body read once + the kept rows written + 40 bytes per kept row */
+uint64_t  kmx_diff_result_algo_bytes(kmx_diff_result* r);
+void      kmx_diff_result_free(kmx_diff_result* r);
 
 /* ------------------------------------------------------------------ count */
 

@@ -71,6 +71,22 @@ class KmxDistTask(C.Structure):
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("inter", C.c_void_p), ("mins", C.c_void_p)]
 
 
+class KmxColsumsTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("reserved", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("sums", C.c_void_p)]
+
+
+class KmxDiffTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("min_rec", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("group", C.c_void_p), ("total_ctrl", C.c_uint64),
+                ("total_case", C.c_uint64), ("threshold", C.c_double)]
+
+
+# kmx_diff_rec: 40 bytes
+DIFF_REC = np.dtype([("sum_ctrl", "<u8"), ("sum_case", "<u8"), ("stat", "<f8"), ("rec_ctrl", "<u4"), ("rec_case", "<u4"),
+                     ("row", "<u4"), ("over", "<u4")])
+assert DIFF_REC.itemsize == 40
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -277,6 +293,36 @@ _lib.kmx_dist_result_free.argtypes = [_vp]
 DIST_EXPORTS = ["kmx_dist_dev", "kmx_dist_host", "kmx_dist_result_wait", "kmx_dist_result_inter_dev", "kmx_dist_result_mins_dev",
                 "kmx_dist_result_copy_inter", "kmx_dist_result_copy_mins", "kmx_dist_result_kernel_ms", "kmx_dist_result_kernel_parts_ms",
                 "kmx_dist_result_algo_bytes", "kmx_dist_result_free"]
+_lib.kmx_colsums_dev.argtypes = [_vp, C.POINTER(KmxColsumsTask), C.POINTER(_vp)]
+_lib.kmx_colsums_host.argtypes = [_vp, C.POINTER(KmxColsumsTask), C.POINTER(_vp)]
+_lib.kmx_colsums_result_wait.argtypes = [_vp]
+_lib.kmx_colsums_result_sums_dev.restype = _vp
+_lib.kmx_colsums_result_sums_dev.argtypes = [_vp]
+_lib.kmx_colsums_result_copy_sums.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_colsums_result_kernel_ms.restype = C.c_double
+_lib.kmx_colsums_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_colsums_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_colsums_result_algo_bytes.argtypes = [_vp]
+_lib.kmx_colsums_result_free.argtypes = [_vp]
+_lib.kmx_diff_dev.argtypes = [_vp, C.POINTER(KmxDiffTask), C.POINTER(_vp)]
+_lib.kmx_diff_host.argtypes = [_vp, C.POINTER(KmxDiffTask), C.POINTER(_vp)]
+_lib.kmx_diff_result_wait.argtypes = [_vp]
+for _f in ("kmx_diff_result_rows", "kmx_diff_result_row_bytes", "kmx_diff_result_body_bytes", "kmx_diff_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_diff_result_body_dev", "kmx_diff_result_recs_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_diff_result_copy_body.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_diff_result_copy_recs.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_diff_result_kernel_ms.restype = C.c_double
+_lib.kmx_diff_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_diff_result_free.argtypes = [_vp]
+DIFF_EXPORTS = ["kmx_colsums_dev", "kmx_colsums_host", "kmx_colsums_result_wait", "kmx_colsums_result_sums_dev", "kmx_colsums_result_copy_sums",
+                "kmx_colsums_result_kernel_ms", "kmx_colsums_result_algo_bytes", "kmx_colsums_result_free",
+                "kmx_diff_dev", "kmx_diff_host", "kmx_diff_result_wait", "kmx_diff_result_rows", "kmx_diff_result_row_bytes",
+                "kmx_diff_result_body_bytes", "kmx_diff_result_body_dev", "kmx_diff_result_copy_body", "kmx_diff_result_recs_dev",
+                "kmx_diff_result_copy_recs", "kmx_diff_result_kernel_ms", "kmx_diff_result_algo_bytes", "kmx_diff_result_free"]
 
 
 def zquery_bits_bytes(n_bases, n_cols):
@@ -893,6 +939,72 @@ class Context:
             r.free()
 
     @staticmethod
+    def _whole_rows(body, n_rows, n_cols, key_words, mode):
+        a = np.frombuffer(body, dtype=np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+        stride = key_words * 8 + (4 * n_cols if mode == MODE_COUNT else (n_cols + 7) // 8)
+        if n_rows is None:
+            if stride == 0 or len(a) % stride:
+                raise ValueError(f"{len(a)} bytes are not whole rows of {stride} bytes")
+            n_rows = len(a) // stride
+        elif len(a) < n_rows * stride:
+            raise ValueError(f"{len(a)} bytes are fewer than {n_rows} rows of {stride} bytes")
+        return a, n_rows
+
+    def _finish(self, r, keep):
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def colsums(self, body, n_rows, n_cols, key_words, mode, sums_dev=None, keep=False):
+        """kmx_colsums_host: body the bytes (or a uint8 array) of n_rows whole rows of one partition's matrix (None: from the body's
+        size).  sums_dev: None (the result owns a zeroed table) or a device pointer to n_cols uint64 the call adds to.
+        -> uint64[n_cols] (a numpy copy of the table as it stands), or with keep the ColsumsResult (.free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t = KmxColsumsTask(key_words, mode, n_cols, 0, a.ctypes.data if len(a) else None, n_rows, sums_dev)
+        res = _vp()
+        self._check(_lib.kmx_colsums_host(self._h, C.byref(t), C.byref(res)), "kmx_colsums_host")
+        r = ColsumsResult(self, res, n_cols)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def colsums_dev(self, rows_dev, n_rows, n_cols, key_words, mode, sums_dev=None, keep=False):
+        """kmx_colsums_dev: rows_dev a device pointer to n_rows rows.  -> as colsums"""
+        t = KmxColsumsTask(key_words, mode, n_cols, 0, rows_dev, n_rows, sums_dev)
+        res = _vp()
+        self._check(_lib.kmx_colsums_dev(self._h, C.byref(t), C.byref(res)), "kmx_colsums_dev")
+        return self._finish(ColsumsResult(self, res, n_cols), keep)
+
+    @staticmethod
+    def _diff_task(rows, n_rows, n_cols, key_words, mode, group, total_ctrl, total_case, threshold, min_rec):
+        g = np.ascontiguousarray(group, dtype=np.uint8).reshape(-1)
+        if len(g) != n_cols:
+            raise ValueError(f"{len(g)} groups for {n_cols} columns")
+        return KmxDiffTask(key_words, mode, n_cols, min_rec, rows, n_rows, g.ctypes.data, total_ctrl, total_case, threshold), g
+
+    def diff(self, body, n_rows, n_cols, key_words, mode, group, total_ctrl, total_case, threshold, min_rec=0, keep=False):
+        """kmx_diff_host: body as for colsums; group: n_cols values 0 (control), 1 (case), 2 (ignored); total_ctrl / total_case: the
+        groups' totals over the whole run (sums of colsums); a row is kept when at least min_rec of its control and case columns are
+        non-zero and its statistic is at least threshold.
+        -> DiffOutput (numpy copies), or with keep the DiffResult itself (the kept rows and records left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, g = self._diff_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, group, total_ctrl, total_case, threshold, min_rec)
+        res = _vp()
+        self._check(_lib.kmx_diff_host(self._h, C.byref(t), C.byref(res)), "kmx_diff_host")
+        r = DiffResult(self, res)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def diff_dev(self, rows_dev, n_rows, n_cols, key_words, mode, group, total_ctrl, total_case, threshold, min_rec=0, keep=False):
+        """kmx_diff_dev: rows_dev a device pointer to n_rows rows (group stays a host array).  -> as diff"""
+        t, g = self._diff_task(rows_dev, n_rows, n_cols, key_words, mode, group, total_ctrl, total_case, threshold, min_rec)
+        res = _vp()
+        self._check(_lib.kmx_diff_dev(self._h, C.byref(t), C.byref(res)), "kmx_diff_dev")
+        return self._finish(DiffResult(self, res), keep)
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -1042,6 +1154,96 @@ class DistResult:
     def free(self):
         if self._h:
             _lib.kmx_dist_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ColsumsResult:
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_colsums_result_wait(self._h), "kmx_colsums_result_wait")
+
+    def sums_dev(self):
+        return _lib.kmx_colsums_result_sums_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_colsums_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_colsums_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        sums = np.zeros(self._n, np.uint64)
+        self._ctx._check(_lib.kmx_colsums_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_colsums_result_copy_sums")
+        return sums
+
+    def free(self):
+        if self._h:
+            _lib.kmx_colsums_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DiffOutput:
+    """body: the kept rows, whole and in the input's order (bytes); recs: one DIFF_REC (kmx_diff_rec, 40 bytes) per kept row in the
+    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+
+class DiffResult:
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_diff_result_wait(self._h), "kmx_diff_result_wait")
+
+    def rows(self):
+        return _lib.kmx_diff_result_rows(self._h)
+
+    def row_bytes(self):
+        return _lib.kmx_diff_result_row_bytes(self._h)
+
+    def body_bytes(self):
+        return _lib.kmx_diff_result_body_bytes(self._h)
+
+    def body_dev(self):
+        return _lib.kmx_diff_result_body_dev(self._h)
+
+    def recs_dev(self):
+        return _lib.kmx_diff_result_recs_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_diff_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_diff_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        body = np.zeros(self.body_bytes(), np.uint8)
+        self._ctx._check(_lib.kmx_diff_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_diff_result_copy_body")
+        recs = np.zeros(self.rows(), DIFF_REC)
+        self._ctx._check(_lib.kmx_diff_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_diff_result_copy_recs")
+        return DiffOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_diff_result_free(self._h)
             self._h = None
 
     def __del__(self):
