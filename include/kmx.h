@@ -28,6 +28,8 @@
  *                               kmer:pa:bin run -- exact, with abundances (k-mer, minimizer and partition as kmx_query_* has them)
  *   kmx_zquery_dev / _host      no counterpart either: kmx_query_*'s question asked for (k + z)-mers, the findere trick against Bloom
  *                               false positives -- a position counts for a sample when its z + 1 overlapping k-mers all do
+ *   kmx_cquery_dev / _host      no counterpart either: kmx_query_*'s question asked of the counting Bloom matrices of a hash:bfc:bin run --
+ *                               per sample the k-mers at or above an abundance class and the sum of the classes' least counts
  *   kmx_dist_dev / _host        no counterpart either (Simka's question): the sample-by-sample shared k-mer tables of a run's matrices --
  *                               rows that hold both samples, sums of the smaller count -- which the Jaccard and Bray-Curtis distances follow from
  *   kmx_colsums_dev / _host,    no counterpart either (kmdiff's question): the per-sample totals of a run's matrices, and the rows whose
@@ -526,6 +528,77 @@ double   kmx_zquery_result_kernel_ms(kmx_zquery_result* r);
  * that has any) * pitch (table rows read by the window pass) + 4 * n_seqs * n_cols (the hits table written) */
 uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* r);
 void     kmx_zquery_result_free(kmx_zquery_result* r);
+
+/* ----------------------------------------------------------------- cquery */
+
+/* Which samples of a COUNTING Bloom matrix hold the k-mers of a query sequence, and at what abundance (what kmindex asks of kmtricks'
+ * --bitw indexes; no counterpart in the 1.6.0 tree).
+ * THE INDEX: the .cmbf bodies of a `--mode hash:bfc:bin` run -- per partition `window` rows of nb = ceil(N * w / 8) bytes, N = n_cols,
+ * w = bitw (the header's `bits` field is N * w).  Bit position t of a row is bit 7 - (t & 7) of byte t >> 3 (bitpacker's MSB-first
+ * order, as the merge writes it).  Sample i's CLASS v_i is the w bits at positions i * w ... i * w + w - 1, the first of them the most
+ * significant: v_i = (R >> (8 * nb - (i + 1) * w)) & (2^w - 1) with R the row read as one big-endian number.  The merge writes
+ * v = min(bit_length(count), 2^w - 1).  The padding bits behind position N * w never reach a result.
+ * ADDRESSING: exactly the query section's -- what a valid position is, the canonical k-mer c, p = repart[minimizer(c)], h = XXH64(c) %
+ * window, row = rows[p] + h * nb, NULL partitions, every occurrence counts.
+ * floor_of(v) = 0 for v = 0, else 2^(min(v, 32) - 1): the smallest count the merge maps to class v.  For the top class 2^w - 1 it is a
+ * LOWER BOUND only (every count of that bit length and above lands there).  The clamp at 32: a count is a u32, so a class above 32
+ * stands only in a body no merge wrote, and such a body is still answered without overflow.
+ * RESULTS per query q and column i:
+ *   n_kmers[q]           the valid positions, as in the query section
+ *   hits[q * n_cols + i] (u32) the positions whose v_i >= min_class
+ *   sums[q * n_cols + i] (u64) the sum of floor_of(v_i) over all valid positions of q whose partition is part of the call; it does not
+ *                        depend on min_class
+ * hits and sums: both NULL (the result owns zeroed tables) or both DEVICE tables of n_seqs * n_cols entries that the call ADDS to (one
+ * without the other: KMX_E_INVAL); the partition groups of one set of queries accumulate on the device in any order.
+ * EXAMPLES.  w = 3, N = 3: nb = 2, the third field lies across the two bytes, 7 padding bits (here all set) follow it.
+ *   row 22 FF: bits 001 000 101 -> classes (1, 0, 5), floors (1, 0, 16)
+ *   row ED 7F: bits 111 011 010 -> classes (7, 3, 2), floors (64, 4, 2)      (7 is the top class: counts of 64 and above)
+ *   row 1B FF: bits 000 110 111 -> classes (0, 6, 7), floors (0, 32, 64)
+ * A query whose three valid positions meet these three rows: min_class 1 gives hits (2, 2, 3), min_class 4 gives hits (1, 1, 2), both
+ * give sums (65, 36, 82).  At w = 8 a byte FF is class 255, clamped: floor 2^31.
+ * LIMITS, each refused before any GPU work: the query section's, unchanged; bitw 0 or above 32, min_class outside 1 ... 2^bitw - 1
+ * (KMX_E_INVAL); bitw 9 ... 32 -- a class never exceeds 32, so 6 bits hold every class and 8 keep a field inside two bytes --, a row of
+ * 4 GiB or more, n_seqs * n_cols >= 2^61 (KMX_E_UNSUPPORTED).
+ * Scratch from the context's pool: 16 bytes a base. */
+typedef struct {
+  const char*     bases;
+  const uint64_t* offsets;      /* [n_seqs + 1], offsets[0] = 0 */
+  uint64_t        n_seqs;
+  uint32_t        kmer_size, minim_size;
+  const uint16_t* repart;       /* u16[4^minim_size]: minimizer -> partition */
+  uint32_t        nb_parts;
+  uint32_t        n_cols;       /* N: samples (fields of a row) */
+  uint64_t        window;       /* W: rows of a partition's matrix */
+  const uint8_t* const* rows;   /* [nb_parts] */
+  uint32_t        bitw;         /* w: bits of a field, 1 ... 8 */
+  uint32_t        min_class;    /* a hit is a class of at least this: 1 ... 2^bitw - 1 */
+  uint32_t*       hits;         /* NULL, or a device table to accumulate into */
+  uint64_t*       sums;         /* NULL with hits, or a device table to accumulate into */
+} kmx_cquery_task;
+
+typedef struct kmx_cquery_result kmx_cquery_result;
+
+/* bases, offsets, repart and every rows[p] DEVICE pointers (the rows array itself lies in host memory).  The kernels are queued on the
+ * context's stream (kmx_stream) and the call returns; it reads offsets[n_seqs] back first (8 bytes: the grid's size).  The results
+ * stay in HBM until they are freed; the call's scratch returns to the pool in kmx_cquery_result_wait. */
+int kmx_cquery_dev(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out);
+/* HOST pointers (hits and sums, when given, are still device tables): everything is uploaded on a stream of its own.  The host buffers
+ * may be reused once kmx_cquery_result_wait has returned. */
+int kmx_cquery_host(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out);
+int      kmx_cquery_result_wait(kmx_cquery_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t kmx_cquery_result_n_seqs(const kmx_cquery_result* r);
+int      kmx_cquery_result_copy_kmers(kmx_cquery_result* r, uint32_t* host_dst, uint64_t dst_entries);   /* n_seqs entries */
+int      kmx_cquery_result_copy_hits(kmx_cquery_result* r, uint32_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols: the table as it stands */
+int      kmx_cquery_result_copy_sums(kmx_cquery_result* r, uint64_t* host_dst, uint64_t dst_entries);    /* n_seqs * n_cols: the table as it stands */
+uint32_t* kmx_cquery_result_hits_dev(kmx_cquery_result* r);
+uint64_t* kmx_cquery_result_sums_dev(kmx_cquery_result* r);
+/* duration in ms of the call's kernels, the clearing of their tables included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double   kmx_cquery_result_kernel_ms(kmx_cquery_result* r);
+/* algorithmic bytes: the bases read + one row per valid k-mer of a partition that is part of the call or not (n_kmers * nb) + both
+ * tables written (12 * n_seqs * n_cols) */
+uint64_t kmx_cquery_result_algo_bytes(kmx_cquery_result* r);
+void     kmx_cquery_result_free(kmx_cquery_result* r);
 
 /* ------------------------------------------------------------------- dist */
 

@@ -115,6 +115,9 @@ hipError_t launch_kquery_search(int kw, u64* recs, u64 rec_bound, const u32* pst
                                 u64 stride, const u64* words, u64 n_bases, u32* n_found /* zeroed */, u32 n_cu, hipStream_t st);
 hipError_t launch_kquery_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u64 stride, u32 skip,
                                 u32 n_cols, u32* hits, u64* sums /* or null */, u32 n_cu, hipStream_t st);
+// cquery.hip: query sequences against the counting Bloom matrices of a run (kmx_cquery_dev); keys, scan, parts and scatter are query.hip's
+hipError_t launch_cquery_gather(const u64* recs, u64 rec_bound, const u32* pstart, u32 n_parts, const u8* const* rows, u32 nb, u32 bitw /* 1 ... 8 */,
+                                u32 n_cols, u32 min_class, u32* hits, u64* sums, u32 n_cu, hipStream_t st);
 
 // zquery.hip: the findere trick over the Bloom matrices of a run (kmx_zquery_dev); keys, scan and launch_query_parts are query.hip's
 hipError_t launch_zquery_scatter(const u64* keys, u64 n_bases, u32 n_tiles, u32 n_chunks, u32 tiles_per_chunk, u32* cell, u64* recs /* (row, position) */,

@@ -4,6 +4,8 @@
 // groups that fit the device, a group's hits added on the device to the table of the groups before it.  Every check that needs no
 // GPU comes before kmx_create.  `--kmer-index` asks the same of the k-mer matrices of a kmer:count:bin / kmer:pa:bin run (kquery_main).
 // `--z Z` asks the Bloom index for (k + Z)-mers (the findere trick: kmx_zquery_host, one bits table a batch across its partition groups).
+// `--index` of a `--mode hash:bfc:bin` run (a counting Bloom index: fields of --bitw bits a sample) goes through kmx_cquery_host: hits are
+// the k-mers whose abundance class is at least --min-class, `--format sums` prints the sums of the classes' least counts.
 #include <kmx.h>
 #include <algorithm>
 #include <cstring>
@@ -23,12 +25,14 @@ struct QOpt {
   uint32_t gpus = 1, threads = 8;
   uint64_t batch_mb = 0;      // 0: sized from the device's free memory
   int64_t z = -1;             // --z: (k + z)-mers, the findere trick (zquery_batch); < 0: not given
+  int64_t min_class = -1;     // --min-class: a counting Bloom index's hit is a class of at least this; < 0: not given (1)
   bool verbose = false;
 };
 
-const char* USAGE = "usage: kmx query (--index <run dir made with --mode hash:bf:bin> | --kmer-index <run dir made with --mode kmer:count:bin or kmer:pa:bin>) "
-                    "--query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] [--format matrix|list|sums (sums: --kmer-index of a count run)] "
-                    "[--z INT (--index only: ask for (k + z)-mers, 0 ... 8)] [--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
+const char* USAGE = "usage: kmx query (--index <run dir made with --mode hash:bf:bin or hash:bfc:bin> | --kmer-index <run dir made with --mode kmer:count:bin or kmer:pa:bin>) "
+                    "--query <fasta|fastq[.gz]> [--output FILE] [--threshold FLOAT] [--format matrix|list|sums (sums: --kmer-index of a count run, --index of a hash:bfc:bin run)] "
+                    "[--z INT (--index of a hash:bf:bin run only: ask for (k + z)-mers, 0 ... 8)] [--min-class INT (--index of a hash:bfc:bin run only: a hit is an abundance class of at least this, default 1)] "
+                    "[--gpus INT] [--query-batch-mb INT] [-t INT (accepted, no effect)] [-v]";
 
 QOpt parse(int argc, char** argv)
 {
@@ -45,17 +49,18 @@ QOpt parse(int argc, char** argv)
     else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list" && o.format != "sums") die("--format must be matrix, list or sums"); }
     else if (a == "--gpus") o.gpus = num(i);
     else if (a == "--z") { const unsigned long v = num(i); if (v > 8) die("--z must be in [0, 8]"); o.z = (int64_t)v; }
+    else if (a == "--min-class") o.min_class = (int64_t)std::min<unsigned long>(num(i), 0xFFFFFFFFul);
     else if (a == "--query-batch-mb") o.batch_mb = num(i);
     else if (a == "-t" || a == "--threads") o.threads = num(i);
     else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
     else die("unknown option " + a + "\n" + USAGE);
   }
   if (o.index.empty() == o.kmer_index.empty()) die(std::string("exactly one of --index and --kmer-index is required\n") + USAGE);
-  if (o.format == "sums" && o.kmer_index.empty()) die("--format sums needs --kmer-index with a run made with --mode kmer:count:bin");
   if (o.query.empty()) die(std::string("--query is required\n") + USAGE);
   if (o.gpus < 1 || o.gpus > 16) die("--gpus must be in [1, 16]");
   if (o.threshold < 0.0 || o.threshold > 1.0) die("--threshold must be in [0, 1]");
   if (o.z >= 0 && !o.kmer_index.empty()) die("--z removes Bloom false positives: an exact index (--kmer-index) has none");
+  if (o.min_class >= 0 && !o.kmer_index.empty()) die("--min-class is for a counting Bloom index (--index of a run made with --mode hash:bfc:bin): an exact index has counts, not classes");
   if (o.z >= 0 && o.gpus > 1) die("--z with --gpus above 1 is not supported: shards own partitions, a window's k-mers lie in several shards, and the shards' tables are not joined across devices");
   return o;
 }
@@ -263,11 +268,23 @@ int kmx_query_main(int argc, char** argv)
 {
   const QOpt o = parse(argc, argv);
   if (!o.kmer_index.empty()) return kquery_main(o);
-  // ---- the index: a run directory of --mode hash:bf:bin ----
+  // ---- the index: a run directory of --mode hash:bf:bin or hash:bfc:bin ----
   if (!fs::exists(o.index + "/kmtricks.fof")) die(o.index + " is not a kmtricks runtime directory.");
   std::string opt; { std::ifstream f(o.index + "/options.txt"); if (!f) die("Unable to read at " + o.index + "/options.txt"); std::getline(f, opt); }
   const std::string mode = option_of(opt, "count_format") + ":" + option_of(opt, "mode") + ":" + option_of(opt, "format");
-  if (mode != "hash:bf:bin") die("kmx query --index needs a run made with --mode hash:bf:bin; " + o.index + " was made with " + mode + (mode == "kmer:count:bin" || mode == "kmer:pa:bin" ? " (a k-mer run: --kmer-index)" : ""));
+  const bool bfc = mode == "hash:bfc:bin";
+  if (mode != "hash:bf:bin" && !bfc) die("kmx query --index needs a run made with --mode hash:bf:bin or hash:bfc:bin; " + o.index + " was made with " + mode + (mode == "kmer:count:bin" || mode == "kmer:pa:bin" ? " (a k-mer run: --kmer-index)" : ""));
+  if (o.format == "sums" && !bfc) die("--format sums needs --kmer-index with a run made with --mode kmer:count:bin");
+  if (o.min_class >= 0 && !bfc) die("--min-class is for a counting Bloom index: " + o.index + " was made with --mode hash:bf:bin, whose rows hold one bit a sample");
+  if (o.z >= 0 && bfc) die("--z is not built for counting Bloom indexes: " + o.index + " was made with --mode hash:bfc:bin");
+  uint32_t w = 1;      // bits of a sample's field in a row
+  if (bfc) {
+    try { w = (uint32_t)std::stoul(option_of(opt, "bwidth")); } catch (...) { die(o.index + "/options.txt names no bwidth"); }
+    if (w < 1 || w > 32) die(o.index + "/options.txt: bwidth must be in [1, 32]");
+    if (w > 8) die(o.index + " was made with --bitw " + std::to_string(w) + ": kmx query reads counting Bloom indexes of --bitw 1 ... 8 (a class never exceeds 32: --bitw 6 holds every class)");
+  }
+  const uint32_t min_class = o.min_class < 0 ? 1u : (uint32_t)o.min_class;
+  if (bfc && (min_class < 1 || min_class > (1u << w) - 1u)) die("--min-class must be in [1, " + std::to_string((1u << w) - 1u) + "] for an index made with --bitw " + std::to_string(w));
   uint32_t k = 0;
   try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(o.index + "/options.txt names no kmer_size"); }
   if (o.z >= (int64_t)k) die("--z must be below the index's k-mer size (" + std::to_string(k) + ")");
@@ -281,7 +298,9 @@ int kmx_query_main(int argc, char** argv)
     die("the index's options.txt, hash.info and repartition table do not fit together");
   for (uint16_t t : table) if (t >= P) die("the index's repartition table names a partition the run does not have");
   const std::vector<Sample> samples = parse_fof(o.index + "/kmtricks.fof", 1);
-  const uint32_t N = (uint32_t)samples.size(), nb = (N + 7) / 8;
+  const uint32_t N = (uint32_t)samples.size();
+  const uint64_t row_bits = (uint64_t)N * w, nb = (row_bits + 7) / 8;      // (w = 1 for a Bloom index: a bit a sample)
+  if (row_bits > 0xFFFFFFFFull) die("rows of 2^32 bits and more");
   const uint64_t body = W * nb;
   std::vector<std::string> files(P);
   for (uint64_t p = 0; p < P; p++) {
@@ -290,7 +309,7 @@ int kmx_query_main(int argc, char** argv)
     uint8_t h[CMBF_HEADER];
     if (!f || !f.read((char*)h, CMBF_HEADER)) die("Unable to read at " + files[p]);
     if (rd<uint64_t>(&h[0]) != MAGIC_BASE || rd<uint64_t>(&h[13]) != MAGIC_BITMATRIX) die("Invalid file format: " + files[p]);
-    if (rd<uint32_t>(&h[21]) != N) die(files[p] + " has rows of " + std::to_string(rd<uint32_t>(&h[21])) + " bits, the index's kmtricks.fof has " + std::to_string(N) + " samples");
+    if (rd<uint32_t>(&h[21]) != row_bits) die(files[p] + " has rows of " + std::to_string(rd<uint32_t>(&h[21])) + " bits, the index's kmtricks.fof has " + std::to_string(N) + " samples" + (bfc ? " of " + std::to_string(w) + " bits" : ""));
     if (rd<uint64_t>(&h[25]) != W * p || rd<uint64_t>(&h[33]) != W) die(files[p] + ": its window disagrees with the index's hash.info");
     std::error_code ec;
     if (fs::file_size(files[p], ec) != CMBF_HEADER + body || ec) die("truncated matrix (its body is not " + std::to_string(W) + " rows): " + files[p]);
@@ -320,11 +339,12 @@ int kmx_query_main(int argc, char** argv)
   const uint64_t group_parts = std::max<uint64_t>(1, (budget / 2) / std::max<uint64_t>(body, 1));
   const uint64_t batch_bytes = std::max<uint64_t>(budget / 2, 1);
   // (--z: and a row of the position-major bits table a base, kept from a batch's first group to its last)
-  const uint64_t per_base = 17 + (o.z >= 0 ? kmx_zquery_bits_bytes(1, N) : 0);
+  // (a counting index: two table rows a query, u32 hits and u64 sums)
+  const uint64_t per_base = 17 + (o.z >= 0 ? kmx_zquery_bits_bytes(1, N) : 0), per_query = (bfc ? 12ull : 4ull) * N + 12;
   std::vector<uint64_t> cut{0};      // batch b = queries [cut[b], cut[b + 1])
   { uint64_t used = 0;
     for (uint64_t q = 0; q < Q; q++) {
-      const uint64_t len = offs[q + 1] - offs[q], cost = per_base * len + 4ull * N + 12;
+      const uint64_t len = offs[q + 1] - offs[q], cost = per_base * len + per_query;
       if (len > 0xFFFFFFFFull) die("query " + names[q] + " has 2^32 bases or more");
       if (q > cut.back() && (used + cost > batch_bytes || offs[q + 1] - offs[cut.back()] > 0xFFFFFFFFull)) { cut.push_back(q); used = 0; }
       used += cost;
@@ -337,7 +357,8 @@ int kmx_query_main(int argc, char** argv)
   if (o.verbose) fprintf(stderr, "[kmx query] %llu queries, %zu bases, k %u, %u samples, %llu partitions of %llu rows: %zu query batches, %zu partition groups a shard, %u shards\n",
                          (unsigned long long)Q, bases.size(), k, N, (unsigned long long)P, (unsigned long long)W, cut.size() - 1, n_groups, G);
 
-  if (o.format == "matrix") { std::string h = "query\tn_kmers"; for (const Sample& s : samples) { h += '\t'; h += s.id; } h += '\n'; fwrite(h.data(), 1, h.size(), out); }
+  const bool want_sums = o.format == "sums";
+  if (o.format != "list") { std::string h = "query\tn_kmers"; for (const Sample& s : samples) { h += '\t'; h += s.id; } h += '\n'; fwrite(h.data(), 1, h.size(), out); }
   // a shard whose partitions fit one group reads its matrices once; a shard with several groups reads every group again for every
   // batch of queries (the index does not fit the device, and is not assumed to fit the host either: DESIGN section 11)
   std::vector<std::vector<std::vector<uint8_t>>> kept(G);
@@ -346,7 +367,55 @@ int kmx_query_main(int argc, char** argv)
     std::vector<uint64_t> boffs(nq + 1);
     for (uint64_t i = 0; i <= nq; i++) boffs[i] = offs[q0 + i] - offs[q0];
     std::vector<uint32_t> hits(nq * N, 0), kmers(nq, 0);
+    std::vector<uint64_t> sums(bfc ? nq * N : 0, 0);
     std::mutex mu;
+    // a counting index: the same walk through kmx_cquery_host, the groups adding into the first result's two tables
+    auto cshard = [&](uint32_t g) {
+      try {
+        kmx_ctx* ctx = ctxs[g];
+        kmx_cquery_result* first = nullptr;
+        std::vector<std::vector<uint8_t>> own;
+        const bool keep = groups[g].size() == 1;
+        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+        std::vector<const uint8_t*> rows(P);
+        std::vector<uint32_t> sk(nq);
+        for (size_t gi = 0; gi < groups[g].size(); gi++) {
+          std::fill(rows.begin(), rows.end(), nullptr);
+          const bool loaded = keep && bodies.size() == groups[g][gi].size();
+          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+          for (size_t i = 0; i < groups[g][gi].size(); i++) {
+            const uint32_t p = groups[g][gi][i];
+            if (!loaded) {
+              std::ifstream f(files[p], std::ios::binary);
+              bodies[i].resize(body);
+              if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
+            }
+            rows[p] = bodies[i].data();
+          }
+          kmx_cquery_task t; memset(&t, 0, sizeof t);
+          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
+          t.rows = rows.data(); t.bitw = w; t.min_class = min_class;
+          t.hits = first ? kmx_cquery_result_hits_dev(first) : nullptr;
+          t.sums = first ? kmx_cquery_result_sums_dev(first) : nullptr;
+          kmx_cquery_result* r = nullptr;
+          chk(ctx, kmx_cquery_host(ctx, &t, &r), "kmx_cquery_host");
+          chk(ctx, kmx_cquery_result_wait(r), "kmx_cquery");      // (the bodies are reused by the next group)
+          if (!first) first = r; else kmx_cquery_result_free(r);
+        }
+        if (!first) return;      // (more shards than partitions)
+        std::vector<uint32_t> sh(nq * N);
+        std::vector<uint64_t> ss(nq * N);
+        chk(ctx, kmx_cquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_cquery_result_copy_hits");
+        chk(ctx, kmx_cquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_cquery_result_copy_sums");
+        chk(ctx, kmx_cquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_cquery_result_copy_kmers");
+        kmx_cquery_result_free(first);
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+        for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
+        kmers = sk;      // (every shard walks every query: the same numbers)
+      } catch (const std::exception& e) { die(e.what()); }
+    };
     // every shard sees all queries of the batch; its groups add up on its device, the shards' tables on the host
     auto shard = [&](uint32_t g) {
       try {
@@ -431,16 +500,16 @@ int kmx_query_main(int argc, char** argv)
     if (o.z >= 0) { try { zshard(); } catch (const std::exception& e) { die(e.what()); } }
     else {
       std::vector<std::thread> workers;
-      for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
-      shard(0);
-      for (std::thread& w : workers) w.join();
+      for (uint32_t g = 1; g < G; g++) { if (bfc) workers.emplace_back(cshard, g); else workers.emplace_back(shard, g); }
+      if (bfc) cshard(0); else shard(0);
+      for (std::thread& t : workers) t.join();
     }
     std::string txt;
     for (uint64_t i = 0; i < nq; i++) {
       const std::string& name = names[q0 + i];
-      if (o.format == "matrix") {
+      if (o.format != "list") {
         txt += name; txt += '\t'; txt += std::to_string(kmers[i]);
-        for (uint32_t c = 0; c < N; c++) { txt += '\t'; txt += std::to_string(hits[i * N + c]); }
+        for (uint32_t c = 0; c < N; c++) { txt += '\t'; txt += want_sums ? std::to_string(sums[i * N + c]) : std::to_string(hits[i * N + c]); }
         txt += '\n';
       } else if (kmers[i] > 0) {
         for (uint32_t c = 0; c < N; c++)

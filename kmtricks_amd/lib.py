@@ -66,6 +66,13 @@ class KmxKqueryTask(C.Structure):
                 ("rows", C.POINTER(C.c_void_p)), ("hits", C.c_void_p), ("sums", C.c_void_p), ("want_sums", C.c_uint32)]
 
 
+class KmxCqueryTask(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("kmer_size", C.c_uint32),
+                ("minim_size", C.c_uint32), ("repart", C.c_void_p), ("nb_parts", C.c_uint32), ("n_cols", C.c_uint32),
+                ("window", C.c_uint64), ("rows", C.POINTER(C.c_void_p)), ("bitw", C.c_uint32), ("min_class", C.c_uint32),
+                ("hits", C.c_void_p), ("sums", C.c_void_p)]
+
+
 class KmxDistTask(C.Structure):
     _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("want_mins", C.c_uint32),
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("inter", C.c_void_p), ("mins", C.c_void_p)]
@@ -255,6 +262,24 @@ _lib.kmx_kquery_result_free.argtypes = [_vp]
 KQUERY_EXPORTS = ["kmx_kquery_dev", "kmx_kquery_host", "kmx_kquery_result_wait", "kmx_kquery_result_n_seqs", "kmx_kquery_result_copy_kmers",
                   "kmx_kquery_result_copy_hits", "kmx_kquery_result_copy_sums", "kmx_kquery_result_hits_dev", "kmx_kquery_result_sums_dev",
                   "kmx_kquery_result_kernel_ms", "kmx_kquery_result_algo_bytes", "kmx_kquery_result_free"]
+
+_lib.kmx_cquery_dev.argtypes = [_vp, C.POINTER(KmxCqueryTask), C.POINTER(_vp)]
+_lib.kmx_cquery_host.argtypes = [_vp, C.POINTER(KmxCqueryTask), C.POINTER(_vp)]
+_lib.kmx_cquery_result_wait.argtypes = [_vp]
+for _f in ("kmx_cquery_result_n_seqs", "kmx_cquery_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_cquery_result_copy_kmers", "kmx_cquery_result_copy_hits", "kmx_cquery_result_copy_sums"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_cquery_result_hits_dev", "kmx_cquery_result_sums_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_cquery_result_kernel_ms.restype = C.c_double
+_lib.kmx_cquery_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_cquery_result_free.argtypes = [_vp]
+CQUERY_EXPORTS = ["kmx_cquery_dev", "kmx_cquery_host", "kmx_cquery_result_wait", "kmx_cquery_result_n_seqs", "kmx_cquery_result_copy_kmers",
+                  "kmx_cquery_result_copy_hits", "kmx_cquery_result_copy_sums", "kmx_cquery_result_hits_dev", "kmx_cquery_result_sums_dev",
+                  "kmx_cquery_result_kernel_ms", "kmx_cquery_result_algo_bytes", "kmx_cquery_result_free"]
 
 _lib.kmx_zquery_bits_bytes.restype = C.c_uint64
 _lib.kmx_zquery_bits_bytes.argtypes = [C.c_uint64, C.c_uint32]
@@ -893,6 +918,54 @@ class Context:
         finally:
             r.free()
 
+    def cquery(self, reads, k, m, repart, window, n_cols, matrices, bitw, min_class=1, hits_dev=None, sums_dev=None, keep=False):
+        """kmx_cquery_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
+        counting .cmbf (bytes or a uint8 array of window * ceil(n_cols * bitw / 8) bytes) or None (the partition is not part of the
+        call); a hit is a class of at least min_class; hits_dev / sums_dev both None or device pointers to a uint32 and a uint64 table
+        [queries, n_cols] the call adds to.
+        -> CqueryOutput (numpy copies), or with keep the CqueryResult itself (the tables left in HBM; .free() it)"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        rep = np.ascontiguousarray(repart, dtype=np.uint16)
+        nb = (n_cols * bitw + 7) // 8
+        keepalive, rows = [], (C.c_void_p * len(matrices))()
+        for p, mt in enumerate(matrices):
+            if mt is None:
+                continue
+            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+            if 1 <= bitw <= 8 and len(a) != window * nb:      # (a bitw the library refuses is the library's to refuse)
+                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
+            keepalive.append(a)
+            rows[p] = a.ctypes.data
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        t = KmxCqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows,
+                          bitw, min_class, hits_dev, sums_dev)
+        res = _vp()
+        self._check(_lib.kmx_cquery_host(self._h, C.byref(t), C.byref(res)), "kmx_cquery_host")
+        r = CqueryResult(self, res, n_cols)
+        r.wait()      # (the host buffers above may go once the call has run)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
+    def cquery_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, window, n_cols, rows_dev, bitw, min_class=1, hits_dev=None, sums_dev=None, keep=False):
+        """kmx_cquery_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
+        repartition table; rows_dev[p] a device pointer to partition p's matrix body or None.  -> as cquery"""
+        rows = (C.c_void_p * len(rows_dev))(*rows_dev)
+        t = KmxCqueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, window, rows, bitw, min_class, hits_dev, sums_dev)
+        res = _vp()
+        self._check(_lib.kmx_cquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_cquery_dev")
+        r = CqueryResult(self, res, n_cols)
+        if keep:
+            return r
+        try:
+            return r.output()
+        finally:
+            r.free()
+
     @staticmethod
     def _dist_mins(mins):
         return (1, None) if mins is True else (0, None) if mins is False or mins is None else (1, mins)
@@ -1299,6 +1372,58 @@ class KqueryResult:
     def free(self):
         if self._h:
             _lib.kmx_kquery_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class CqueryOutput:
+    """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose abundance class in the column is
+    at least min_class; sums uint64[queries, n_cols]: the least counts of the classes (floor_of) added up; kernel_ms < 0 without
+    set_profiling"""
+
+    def __init__(self, n_kmers, hits, sums, kernel_ms, algo_bytes):
+        self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
+
+
+class CqueryResult:
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_cquery_result_wait(self._h), "kmx_cquery_result_wait")
+
+    def n_seqs(self):
+        return _lib.kmx_cquery_result_n_seqs(self._h)
+
+    def hits_dev(self):
+        return _lib.kmx_cquery_result_hits_dev(self._h)
+
+    def sums_dev(self):
+        return _lib.kmx_cquery_result_sums_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_cquery_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_cquery_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        q = self.n_seqs()
+        nk, hits, sums = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32), np.zeros((q, self._n), np.uint64)
+        self._ctx._check(_lib.kmx_cquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_cquery_result_copy_kmers")
+        self._ctx._check(_lib.kmx_cquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_cquery_result_copy_hits")
+        self._ctx._check(_lib.kmx_cquery_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_cquery_result_copy_sums")
+        return CqueryOutput(nk, hits, sums, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_cquery_result_free(self._h)
             self._h = None
 
     def __del__(self):
