@@ -19,7 +19,7 @@
 // The bytes behind nb are never loaded, the fields of columns >= N are never added.
 //
 // The C ABI of the section lies here too (kmx_cquery_*), as dist.hip and diff.hip hold theirs.
-#include "kmx_host.hpp"
+#include "seqquery_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -123,54 +123,30 @@ hipError_t launch_cquery_gather(const u64* recs, u64 rec_bound, const u32* pstar
 using namespace kmx;
 
 // ---- cquery ------------------------------------------------------------------------------------------------------------------------
-// kmx_cquery_dev / kmx_cquery_host: query sequences against the counting Bloom matrices of a run.
-struct kmx_cquery_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_seqs = 0, n_bases = 0;
-  u32 n_cols = 0, nb = 0, n_parts = 0;
-  u64 *d_keys = nullptr, *d_recs = nullptr, *d_sums_own = nullptr, *d_sums = nullptr;
-  u32 *d_cell = nullptr, *d_pstart = nullptr, *d_kmers = nullptr, *d_hits_own = nullptr, *d_hits = nullptr;
-  const u8** d_rows = nullptr;
-  const u8** h_rows = nullptr;          // page-locked: the row pointers on their way up
-  std::vector<void*> d_in;              // kmx_cquery_host: the uploads
-  u32* h_tot = nullptr;                 // page-locked: [0] valid k-mers of the call
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
+// kmx_cquery_dev / kmx_cquery_host: query sequences against the counting Bloom matrices of a run.  The shared host path:
+// seqquery_host.hpp.
+struct kmx_cquery_result : SeqResult {
+  u32 nb = 0;                           // bytes of a row: n_cols fields of bitw bits
+  u32 *d_kmers = nullptr, *d_hits = nullptr;
+  u64* d_sums = nullptr;
 };
 
 static u64 cquery_row_bytes(const kmx_cquery_task* K) { return ((u64)K->n_cols * K->bitw + 7) / 8; }
 
-// the query section's limits, then the section's own
+// the query section's limits, the section's own among them where a task with several faults has always met them
 static int cquery_check(kmx_ctx* ctx, const kmx_cquery_task* K, const char* who)
 {
-  const std::string w(who);
-  if (K->kmer_size < 8 || K->kmer_size > 127) return ctx->fail(KMX_E_INVAL, w + ": kmer_size must be in [8, 127]");
-  if (K->minim_size < 4 || K->minim_size > 15 || K->minim_size >= K->kmer_size) return ctx->fail(KMX_E_INVAL, w + ": minim_size must be in [4, 15] and below kmer_size");
-  if (K->nb_parts < 1 || K->nb_parts > 65535) return ctx->fail(KMX_E_INVAL, w + ": nb_parts must be in [1, 65535]");
-  if (K->n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
-  if (!K->repart || !K->rows) return ctx->fail(KMX_E_INVAL, w + ": null repartition table or row pointer array");
-  if (!K->offsets || (K->n_seqs && !K->bases)) return ctx->fail(KMX_E_INVAL, w + ": null reads");
-  if (K->window == 0) return ctx->fail(KMX_E_INVAL, w + ": a window has at least one row");
-  if (K->bitw == 0 || K->bitw > 32) return ctx->fail(KMX_E_INVAL, w + ": bitw must be in [1, 32]");
-  if (K->bitw > 8) return ctx->fail(KMX_E_UNSUPPORTED, w + ": bitw above 8 (a class never exceeds 32: 6 bits hold every class)");
-  if (K->min_class < 1 || K->min_class > (1u << K->bitw) - 1u) return ctx->fail(KMX_E_INVAL, w + ": min_class must be in [1, 2^bitw - 1]");
-  if ((K->hits == nullptr) != (K->sums == nullptr)) return ctx->fail(KMX_E_INVAL, w + ": hits and sums are both null or both device tables");
-  if (K->window > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": windows of 2^32 rows and more");
-  if (K->n_seqs >= (1ull << 31)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": 2^31 queries and more in one call (send them in batches)");
-  if (cquery_row_bytes(K) > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (K->n_seqs * (u64)K->n_cols >= (1ull << 61)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": tables of 2^61 cells and more (send the queries in batches)");
+  const SeqCheck c{ctx, who};
+  int rc;
+  if ((rc = c.kmer_size(K->kmer_size)) || (rc = c.minim_size(K->minim_size, K->kmer_size)) || (rc = c.nb_parts(K->nb_parts)) || (rc = c.n_cols(K->n_cols)) ||
+      (rc = c.tables(K->repart, K->rows)) || (rc = c.reads(K->offsets, K->n_seqs, K->bases)) || (rc = c.window(K->window))) return rc;
+  if (K->bitw == 0 || K->bitw > 32) return c.no(KMX_E_INVAL, ": bitw must be in [1, 32]");
+  if (K->bitw > 8) return c.no(KMX_E_UNSUPPORTED, ": bitw above 8 (a class never exceeds 32: 6 bits hold every class)");
+  if (K->min_class < 1 || K->min_class > (1u << K->bitw) - 1u) return c.no(KMX_E_INVAL, ": min_class must be in [1, 2^bitw - 1]");
+  if ((K->hits == nullptr) != (K->sums == nullptr)) return c.no(KMX_E_INVAL, ": hits and sums are both null or both device tables");
+  if ((rc = c.window_fits(K->window)) || (rc = c.n_seqs(K->n_seqs)) || (rc = c.row_fits(cquery_row_bytes(K)))) return rc;
+  if (K->n_seqs * (u64)K->n_cols >= (1ull << 61)) return c.no(KMX_E_UNSUPPORTED, ": tables of 2^61 cells and more (send the queries in batches)");
   return KMX_OK;
-}
-
-static void cquery_release(kmx_cquery_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kmers, R->d_hits_own, R->d_sums_own, (void*)R->d_rows};
-  for (void* p : blocks) c->dfree(p);
-  for (void* p : R->d_in) c->dfree(p);
-  c->hfree(R->h_tot); c->hfree((void*)R->h_rows);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
 }
 
 // the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
@@ -182,164 +158,63 @@ static int cquery_queue(kmx_ctx* ctx, const kmx_cquery_task* K, kmx_cquery_resul
   u32 n_tiles = 0, n_chunks = 1, tpc = 1;
   query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
   const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_rows = (const u8**)ctx->halloc(8ull * P))) return ctx->fail(KMX_E_NOMEM, "kmx_cquery: host allocation failed");
-  R->h_tot[0] = 0;
-  for (u32 p = 0; p < P; p++) R->h_rows[p] = K->rows[p];
-  R->d_keys = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_recs = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_cell = (u32*)ctx->dalloc(4 * cells);
-  R->d_pstart = (u32*)ctx->dalloc(4ull * (P + 1));
-  R->d_kmers = (u32*)ctx->dalloc(4ull * n_seqs);
-  R->d_rows = (const u8**)ctx->dalloc(8ull * P);
-  R->d_hits = K->hits; R->d_sums = (u64*)K->sums;
-  if (!R->d_hits) {      // (both or neither: cquery_check)
-    R->d_hits = R->d_hits_own = (u32*)ctx->dalloc(4 * table);
-    R->d_sums = R->d_sums_own = (u64*)ctx->dalloc(8 * table);
-  }
-  if (!R->d_keys || !R->d_recs || !R->d_cell || !R->d_pstart || !R->d_kmers || !R->d_rows || !R->d_hits || !R->d_sums)
-    return ctx->fail(KMX_E_NOMEM, "kmx_cquery: device allocation failed");
-  KMX_HIP(ctx, hipMemcpyAsync((void*)R->d_rows, (const void*)R->h_rows, 8ull * P, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_cell, 0, 4 * cells, st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_pstart, 0, 4ull * (P + 1), st));
+  u64* d_keys = (u64*)R->tmp(8 * n_bases);
+  u64* d_recs = (u64*)R->tmp(8 * n_bases);
+  u32* d_cell = (u32*)R->tmp(4 * cells);
+  u32* d_pstart = (u32*)R->tmp(4ull * (P + 1));
+  R->d_kmers = (u32*)R->keep(4ull * n_seqs);
+  const bool own = !K->hits;      // (hits and sums: both or neither, cquery_check)
+  R->d_hits = own ? (u32*)R->keep(4 * table) : K->hits;
+  R->d_sums = own ? (u64*)R->keep(8 * table) : (u64*)K->sums;
+  const int rc = seq_queue_head(R, K->rows, nullptr, 64);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_cell, 0, 4 * cells, st));
+  KMX_HIP(ctx, hipMemsetAsync(d_pstart, 0, 4ull * (P + 1), st));
   if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
-  if (R->d_hits_own && table) {
-    KMX_HIP(ctx, hipMemsetAsync(R->d_hits_own, 0, 4 * table, st));
-    KMX_HIP(ctx, hipMemsetAsync(R->d_sums_own, 0, 8 * table, st));
+  if (own && table) {
+    KMX_HIP(ctx, hipMemsetAsync(R->d_hits, 0, 4 * table, st));
+    KMX_HIP(ctx, hipMemsetAsync(R->d_sums, 0, 8 * table, st));
   }
   if (n_bases) {
     KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
-                                   n_tiles, n_chunks, tpc, R->d_keys, R->d_cell, R->d_kmers, st));
-    KMX_HIP(ctx, launch_filter_scan(R->d_cell, (u32)(cells - 1), st));
-    KMX_HIP(ctx, launch_query_parts(R->d_cell, P, n_chunks, R->d_pstart, st));
-    KMX_HIP(ctx, launch_query_scatter(R->d_keys, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, R->d_cell, R->d_recs, st));
-    KMX_HIP(ctx, launch_cquery_gather(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, nb, K->bitw, N, K->min_class, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
+                                   n_tiles, n_chunks, tpc, d_keys, d_cell, R->d_kmers, st));
+    KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
+    KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
+    KMX_HIP(ctx, launch_query_scatter(d_keys, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
+    KMX_HIP(ctx, launch_cquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, nb, K->bitw, N, K->min_class, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_pstart + P, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return seq_queue_tail(R, d_pstart + P, 1);      // h_tot[0]: the valid k-mers of the call
 }
 
-static kmx_cquery_result* cquery_new(kmx_ctx* ctx, const kmx_cquery_task* K, u64 n_bases)
+static int cquery_call(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out, bool host, const char* who)
 {
+  u64 n_bases = 0;
+  int rc = seq_args(ctx, task, out, who);
+  if (rc == KMX_OK) rc = cquery_check(ctx, task, who);
+  if (rc == KMX_OK) rc = seq_n_bases(ctx, task->offsets, task->n_seqs, host, who, &n_bases);
+  if (rc != KMX_OK) return rc;
   kmx_cquery_result* R = new kmx_cquery_result();
-  R->ctx = ctx; R->n_seqs = K->n_seqs; R->n_bases = n_bases; R->n_cols = K->n_cols; R->nb = (u32)cquery_row_bytes(K); R->n_parts = K->nb_parts;
-  return R;
-}
-
-extern "C" int kmx_cquery_dev(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_cquery_dev: null argument");
-  *out = nullptr;
-  int rc = cquery_check(ctx, task, "kmx_cquery_dev");
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  u64 ends[1] = {0};      // the grid's size: the end of the last query
-  KMX_HIP(ctx, hipMemcpyAsync(ends, task->offsets + task->n_seqs, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ends[0] > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_cquery_dev: 2^32 bases and more in one call (send the queries in batches)");
-  kmx_cquery_result* R = cquery_new(ctx, task, ends[0]);
-  if ((rc = cquery_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); cquery_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_cquery_host(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_cquery_host: null argument");
-  *out = nullptr;
-  int rc = cquery_check(ctx, task, "kmx_cquery_host");
-  if (rc != KMX_OK) return rc;
-  const u64 n_bases = task->offsets[task->n_seqs];
-  if (task->offsets[0] != 0) return ctx->fail(KMX_E_INVAL, "kmx_cquery_host: offsets[0] must be 0");
-  for (u64 i = 0; i < task->n_seqs; i++) if (task->offsets[i] > task->offsets[i + 1]) return ctx->fail(KMX_E_INVAL, "kmx_cquery_host: offsets must not descend");
-  if (n_bases > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_cquery_host: 2^32 bases and more in one call (send the queries in batches)");
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_cquery_result* R = cquery_new(ctx, task, n_bases);
+  R->init(ctx, "kmx_cquery", *task, n_bases); R->nb = (u32)cquery_row_bytes(task);
   kmx_cquery_task dt = *task;
   std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); cquery_release(R); return code; };
-  hipError_t e = hipSuccess;
-  auto upload = [&](const void* src, u64 bytes) -> void* {
-    void* d = ctx->dalloc(bytes);
-    if (!d) return nullptr;
-    R->d_in.push_back(d);
-    if (bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->up);
-    return d;
-  };
-  const u64 body_bytes = task->window * cquery_row_bytes(task);
-  if (!(dt.bases = (const char*)upload(task->bases, n_bases)) || !(dt.offsets = (const uint64_t*)upload(task->offsets, 8 * (task->n_seqs + 1))) ||
-      !(dt.repart = (const uint16_t*)upload(task->repart, 2ull << (2 * task->minim_size))))
-    return fail(ctx->fail(KMX_E_NOMEM, "kmx_cquery_host: upload allocation failed"));
-  for (u32 p = 0; p < task->nb_parts; p++) {
-    if (!task->rows[p]) continue;
-    if (!(drows[p] = (const uint8_t*)upload(task->rows[p], body_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_cquery_host: upload allocation failed"));
-  }
-  dt.rows = drows.data();
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_cquery_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = cquery_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
+  if (host) rc = seq_upload(R, &dt, drows, who, [&](u32) { return task->window * R->nb; });
+  if (rc == KMX_OK) rc = cquery_queue(ctx, &dt, R);
+  return seq_finish(R, rc, host, out);
 }
+extern "C" int kmx_cquery_dev(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out) { return cquery_call(ctx, task, out, false, "kmx_cquery_dev"); }
+extern "C" int kmx_cquery_host(kmx_ctx* ctx, const kmx_cquery_task* task, kmx_cquery_result** out) { return cquery_call(ctx, task, out, true, "kmx_cquery_host"); }
 
-extern "C" int kmx_cquery_result_wait(kmx_cquery_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_cquery: ") + hipGetErrorString(e));
-  // the call has run: its scratch and uploads go back to the pool; n_kmers and the tables stay (a result kept as the accumulator of
-  // later partition groups holds nothing else)
-  kmx_ctx* c = R->ctx;
-  void* scratch[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, (void*)R->d_rows};
-  for (void* p : scratch) c->dfree(p);
-  R->d_keys = R->d_recs = nullptr; R->d_cell = R->d_pstart = nullptr; R->d_rows = nullptr;
-  for (void* p : R->d_in) c->dfree(p);
-  R->d_in.clear();
-  c->hfree((void*)R->h_rows); R->h_rows = nullptr;
-  return R->status = KMX_OK;
-}
+extern "C" int kmx_cquery_result_wait(kmx_cquery_result* R) { return seq_wait(R); }
 extern "C" uint64_t kmx_cquery_result_n_seqs(const kmx_cquery_result* R) { return R ? R->n_seqs : 0; }
-static int cquery_copy_out(kmx_cquery_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries, u32 entry_bytes)
-{
-  const int rc = kmx_cquery_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!entries) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, (u64)entry_bytes * entries);
-}
 extern "C" int kmx_cquery_result_copy_kmers(kmx_cquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? cquery_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs, 4) : KMX_E_INVAL; }
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs, 4) : KMX_E_INVAL; }
 extern "C" int kmx_cquery_result_copy_hits(kmx_cquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? cquery_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols, 4) : KMX_E_INVAL; }
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols, 4) : KMX_E_INVAL; }
 extern "C" int kmx_cquery_result_copy_sums(kmx_cquery_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? cquery_copy_out(R, host_dst, dst_entries, R->d_sums, R->n_seqs * R->n_cols, 8) : KMX_E_INVAL; }
-extern "C" uint32_t* kmx_cquery_result_hits_dev(kmx_cquery_result* R) { return R && kmx_cquery_result_wait(R) == KMX_OK ? R->d_hits : nullptr; }
-extern "C" uint64_t* kmx_cquery_result_sums_dev(kmx_cquery_result* R) { return R && kmx_cquery_result_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
-extern "C" double kmx_cquery_result_kernel_ms(kmx_cquery_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_cquery_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_sums, R->n_seqs * R->n_cols, 8) : KMX_E_INVAL; }
+extern "C" uint32_t* kmx_cquery_result_hits_dev(kmx_cquery_result* R) { return R && seq_wait(R) == KMX_OK ? R->d_hits : nullptr; }
+extern "C" uint64_t* kmx_cquery_result_sums_dev(kmx_cquery_result* R) { return R && seq_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
+extern "C" double kmx_cquery_result_kernel_ms(kmx_cquery_result* R) { return seq_kernel_ms(R); }
 extern "C" uint64_t kmx_cquery_result_algo_bytes(kmx_cquery_result* R)
-{ return R && kmx_cquery_result_wait(R) == KMX_OK ? R->n_bases + (u64)R->h_tot[0] * R->nb + 12 * R->n_seqs * R->n_cols : 0; }
-extern "C" void kmx_cquery_result_free(kmx_cquery_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  cquery_release(R);
-}
+{ return R && seq_wait(R) == KMX_OK ? R->n_bases + (u64)R->h_tot[0] * R->nb + 12 * R->n_seqs * R->n_cols : 0; }
+extern "C" void kmx_cquery_result_free(kmx_cquery_result* R) { seq_free(R); }

@@ -1,4 +1,5 @@
-// kmx_api.hip -- C ABI of libkmx (include/kmx.h): context, device memory pool, batch merge driver.
+// kmx_api.hip -- C ABI of libkmx (include/kmx.h): context, device memory pool, stores, batch merge driver, filter and combine (the
+// query, dist and diff calls lie beside their kernels).
 // No CPU fallback anywhere: every entry point needs a live HIP device.
 #include "kmx_host.hpp"
 
@@ -2227,688 +2228,4 @@ extern "C" void kmx_combine_result_free(kmx_combine_result* R)
   (void)hipSetDevice(R->ctx->device);
   if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
   combine_release(R);
-}
-
-// ---- query -------------------------------------------------------------------------------------------------------------------------
-// kmx_query_dev / kmx_query_host: query sequences against the Bloom matrices of a run (query.hip).
-struct kmx_query_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_seqs = 0, n_bases = 0;
-  u32 n_cols = 0, nb = 0, n_parts = 0;
-  u64 *d_keys = nullptr, *d_recs = nullptr;
-  u32 *d_cell = nullptr, *d_pstart = nullptr, *d_kmers = nullptr, *d_hits_own = nullptr, *d_hits = nullptr;
-  const u8** d_rows = nullptr;
-  const u8** h_rows = nullptr;          // page-locked: the row pointers on their way up
-  std::vector<void*> d_in;              // kmx_query_host: the uploads
-  u32* h_tot = nullptr;                 // page-locked: [0] valid k-mers of the call
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
-};
-
-static int query_check(kmx_ctx* ctx, const kmx_query_task* K, const char* who)
-{
-  const std::string w(who);
-  if (K->kmer_size < 8 || K->kmer_size > 127) return ctx->fail(KMX_E_INVAL, w + ": kmer_size must be in [8, 127]");
-  if (K->minim_size < 4 || K->minim_size > 15 || K->minim_size >= K->kmer_size) return ctx->fail(KMX_E_INVAL, w + ": minim_size must be in [4, 15] and below kmer_size");
-  if (K->nb_parts < 1 || K->nb_parts > 65535) return ctx->fail(KMX_E_INVAL, w + ": nb_parts must be in [1, 65535]");
-  if (K->n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
-  if (!K->repart || !K->rows) return ctx->fail(KMX_E_INVAL, w + ": null repartition table or row pointer array");
-  if (!K->offsets || (K->n_seqs && !K->bases)) return ctx->fail(KMX_E_INVAL, w + ": null reads");
-  if (K->window == 0) return ctx->fail(KMX_E_INVAL, w + ": a window has at least one row");
-  if (K->window > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": windows of 2^32 rows and more");
-  if (K->n_seqs >= (1ull << 31)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": 2^31 queries and more in one call (send them in batches)");
-  return KMX_OK;
-}
-
-static void query_release(kmx_query_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kmers, R->d_hits_own, (void*)R->d_rows};
-  for (void* p : blocks) c->dfree(p);
-  for (void* p : R->d_in) c->dfree(p);
-  c->hfree(R->h_tot); c->hfree((void*)R->h_rows);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
-
-// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
-static int query_queue(kmx_ctx* ctx, const kmx_query_task* K, kmx_query_result* R)
-{
-  hipStream_t st = ctx->stream;
-  const u64 n_bases = R->n_bases;
-  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, nb = (N + 7) / 8, kw = (K->kmer_size + 31) / 32;
-  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
-  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
-  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_rows = (const u8**)ctx->halloc(8ull * P))) return ctx->fail(KMX_E_NOMEM, "kmx_query: host allocation failed");
-  R->h_tot[0] = 0;
-  for (u32 p = 0; p < P; p++) R->h_rows[p] = K->rows[p];
-  R->d_keys = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_recs = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_cell = (u32*)ctx->dalloc(4 * cells);
-  R->d_pstart = (u32*)ctx->dalloc(4ull * (P + 1));
-  R->d_kmers = (u32*)ctx->dalloc(4ull * n_seqs);
-  R->d_rows = (const u8**)ctx->dalloc(8ull * P);
-  R->d_hits = K->hits;
-  if (!R->d_hits) R->d_hits = R->d_hits_own = (u32*)ctx->dalloc(4 * table);
-  if (!R->d_keys || !R->d_recs || !R->d_cell || !R->d_pstart || !R->d_kmers || !R->d_rows || !R->d_hits)
-    return ctx->fail(KMX_E_NOMEM, "kmx_query: device allocation failed");
-  KMX_HIP(ctx, hipMemcpyAsync((void*)R->d_rows, (const void*)R->h_rows, 8ull * P, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_cell, 0, 4 * cells, st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_pstart, 0, 4ull * (P + 1), st));
-  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
-  if (R->d_hits_own && table) KMX_HIP(ctx, hipMemsetAsync(R->d_hits_own, 0, 4 * table, st));
-  if (n_bases) {
-    KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
-                                   n_tiles, n_chunks, tpc, R->d_keys, R->d_cell, R->d_kmers, st));
-    KMX_HIP(ctx, launch_filter_scan(R->d_cell, (u32)(cells - 1), st));
-    KMX_HIP(ctx, launch_query_parts(R->d_cell, P, n_chunks, R->d_pstart, st));
-    KMX_HIP(ctx, launch_query_scatter(R->d_keys, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, R->d_cell, R->d_recs, st));
-    KMX_HIP(ctx, launch_query_gather(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, nb, N, R->d_hits, (u32)ctx->n_cu, st));
-  }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_pstart + P, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-static kmx_query_result* query_new(kmx_ctx* ctx, const kmx_query_task* K, u64 n_bases)
-{
-  kmx_query_result* R = new kmx_query_result();
-  R->ctx = ctx; R->n_seqs = K->n_seqs; R->n_bases = n_bases; R->n_cols = K->n_cols; R->nb = (K->n_cols + 7) / 8; R->n_parts = K->nb_parts;
-  return R;
-}
-
-extern "C" int kmx_query_dev(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_query_dev: null argument");
-  *out = nullptr;
-  int rc = query_check(ctx, task, "kmx_query_dev");
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  u64 ends[1] = {0};      // the grid's size: the end of the last query
-  KMX_HIP(ctx, hipMemcpyAsync(ends, task->offsets + task->n_seqs, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ends[0] > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_query_dev: 2^32 bases and more in one call (send the queries in batches)");
-  kmx_query_result* R = query_new(ctx, task, ends[0]);
-  if ((rc = query_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); query_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_query_host(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_query_host: null argument");
-  *out = nullptr;
-  int rc = query_check(ctx, task, "kmx_query_host");
-  if (rc != KMX_OK) return rc;
-  const u64 n_bases = task->offsets[task->n_seqs];
-  if (task->offsets[0] != 0) return ctx->fail(KMX_E_INVAL, "kmx_query_host: offsets[0] must be 0");
-  for (u64 i = 0; i < task->n_seqs; i++) if (task->offsets[i] > task->offsets[i + 1]) return ctx->fail(KMX_E_INVAL, "kmx_query_host: offsets must not descend");
-  if (n_bases > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_query_host: 2^32 bases and more in one call (send the queries in batches)");
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_query_result* R = query_new(ctx, task, n_bases);
-  kmx_query_task dt = *task;
-  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); query_release(R); return code; };
-  hipError_t e = hipSuccess;
-  auto upload = [&](const void* src, u64 bytes) -> void* {
-    void* d = ctx->dalloc(bytes);
-    if (!d) return nullptr;
-    R->d_in.push_back(d);
-    if (bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->up);
-    return d;
-  };
-  const u64 row_bytes = task->window * ((task->n_cols + 7) / 8);
-  if (!(dt.bases = (const char*)upload(task->bases, n_bases)) || !(dt.offsets = (const uint64_t*)upload(task->offsets, 8 * (task->n_seqs + 1))) ||
-      !(dt.repart = (const uint16_t*)upload(task->repart, 2ull << (2 * task->minim_size))))
-    return fail(ctx->fail(KMX_E_NOMEM, "kmx_query_host: upload allocation failed"));
-  for (u32 p = 0; p < task->nb_parts; p++) {
-    if (!task->rows[p]) continue;
-    if (!(drows[p] = (const uint8_t*)upload(task->rows[p], row_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_query_host: upload allocation failed"));
-  }
-  dt.rows = drows.data();
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_query_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = query_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_query_result_wait(kmx_query_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_query: ") + hipGetErrorString(e));
-  // the call has run: its scratch and uploads go back to the pool; n_kmers and the table stay (a result kept as the accumulator of
-  // later partition groups holds nothing else)
-  kmx_ctx* c = R->ctx;
-  void* scratch[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, (void*)R->d_rows};
-  for (void* p : scratch) c->dfree(p);
-  R->d_keys = R->d_recs = nullptr; R->d_cell = R->d_pstart = nullptr; R->d_rows = nullptr;
-  for (void* p : R->d_in) c->dfree(p);
-  R->d_in.clear();
-  c->hfree((void*)R->h_rows); R->h_rows = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_query_result_n_seqs(const kmx_query_result* R) { return R ? R->n_seqs : 0; }
-static int query_copy_out(kmx_query_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries)
-{
-  const int rc = kmx_query_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!entries) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, 4 * entries);
-}
-extern "C" int kmx_query_result_copy_kmers(kmx_query_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? query_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs) : KMX_E_INVAL; }
-extern "C" int kmx_query_result_copy_hits(kmx_query_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? query_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols) : KMX_E_INVAL; }
-extern "C" uint32_t* kmx_query_result_hits_dev(kmx_query_result* R) { return R && kmx_query_result_wait(R) == KMX_OK ? R->d_hits : nullptr; }
-extern "C" double kmx_query_result_kernel_ms(kmx_query_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_query_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
-extern "C" uint64_t kmx_query_result_algo_bytes(kmx_query_result* R)
-{ return R && kmx_query_result_wait(R) == KMX_OK ? R->n_bases + (u64)R->h_tot[0] * R->nb + 4 * R->n_seqs * R->n_cols : 0; }
-extern "C" void kmx_query_result_free(kmx_query_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  query_release(R);
-}
-
-// ---- zquery ------------------------------------------------------------------------------------------------------------------------
-// kmx_zquery_dev / kmx_zquery_host: the (k + z)-mers of query sequences against the Bloom matrices of a run (zquery.hip).
-struct kmx_zquery_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_seqs = 0, n_bases = 0;
-  u32 n_cols = 0, nb = 0, pitch = 0, n_parts = 0, z = 0;
-  bool last = false;
-  u64 *d_keys = nullptr, *d_recs = nullptr;
-  u32 *d_cell = nullptr, *d_pstart = nullptr, *d_kcount = nullptr;      // d_kcount: k_query_keys' k-mers per query (scratch: the result counts K-positions)
-  u32 *d_kmers = nullptr, *d_hits_own = nullptr, *d_hits = nullptr;     // (the last call of a series only)
-  u8 *d_bits_own = nullptr, *d_bits = nullptr;
-  const u8** d_rows = nullptr;
-  const u8** h_rows = nullptr;          // page-locked: the row pointers on their way up
-  std::vector<void*> d_in;              // kmx_zquery_host: the uploads
-  std::vector<bool> in_call;            // partition p is part of the call
-  u32* h_pstart = nullptr;              // page-locked: the first record of every partition, [n_parts] the valid k-mers of the call
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
-};
-
-extern "C" uint64_t kmx_zquery_bits_bytes(uint64_t n_bases, uint32_t n_cols)
-{ return n_bases * (4ull * ((((u64)n_cols + 7) / 8 + 3) / 4)); }
-
-static kmx_query_task zquery_as_query(const kmx_zquery_task* Z)
-{
-  kmx_query_task q; memset(&q, 0, sizeof q);
-  q.bases = Z->bases; q.offsets = Z->offsets; q.n_seqs = Z->n_seqs; q.kmer_size = Z->kmer_size; q.minim_size = Z->minim_size; q.repart = Z->repart;
-  q.nb_parts = Z->nb_parts; q.n_cols = Z->n_cols; q.window = Z->window; q.rows = Z->rows; q.hits = Z->hits;
-  return q;
-}
-
-// the query section's limits, then the section's own
-static int zquery_check(kmx_ctx* ctx, const kmx_zquery_task* Z, const char* who)
-{
-  const kmx_query_task q = zquery_as_query(Z);
-  const int rc = query_check(ctx, &q, who);
-  if (rc != KMX_OK) return rc;
-  if (Z->z > 8 || Z->z >= Z->kmer_size) return ctx->fail(KMX_E_INVAL, std::string(who) + ": z must be in [0, 8] and below kmer_size");
-  return KMX_OK;
-}
-static int zquery_check_bases(kmx_ctx* ctx, const kmx_zquery_task* Z, u64 n_bases, const char* who)
-{
-  if (n_bases > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, std::string(who) + ": 2^32 bases and more in one call (send the queries in batches)");
-  if (kmx_zquery_bits_bytes(n_bases, Z->n_cols) > (1ull << 40)) return ctx->fail(KMX_E_UNSUPPORTED, std::string(who) + ": a bits table of more than 2^40 bytes (send the queries in batches)");
-  return KMX_OK;
-}
-
-static void zquery_release(kmx_zquery_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kcount, R->d_kmers, R->d_hits_own, R->d_bits_own, (void*)R->d_rows};
-  for (void* p : blocks) c->dfree(p);
-  for (void* p : R->d_in) c->dfree(p);
-  c->hfree(R->h_pstart); c->hfree((void*)R->h_rows);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
-
-// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
-static int zquery_queue(kmx_ctx* ctx, const kmx_zquery_task* K, kmx_zquery_result* R)
-{
-  hipStream_t st = ctx->stream;
-  const u64 n_bases = R->n_bases;
-  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, nb = R->nb, kw = (K->kmer_size + 31) / 32;
-  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
-  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
-  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N, bits_bytes = kmx_zquery_bits_bytes(n_bases, N);
-  if (!(R->h_pstart = (u32*)ctx->halloc(4ull * (P + 1))) || !(R->h_rows = (const u8**)ctx->halloc(8ull * P))) return ctx->fail(KMX_E_NOMEM, "kmx_zquery: host allocation failed");
-  R->in_call.assign(P, false);
-  for (u32 p = 0; p <= P; p++) R->h_pstart[p] = 0;
-  for (u32 p = 0; p < P; p++) { R->h_rows[p] = K->rows[p]; R->in_call[p] = K->rows[p] != nullptr; }
-  R->d_keys = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_recs = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_cell = (u32*)ctx->dalloc(4 * cells);
-  R->d_pstart = (u32*)ctx->dalloc(4ull * (P + 1));
-  R->d_kcount = (u32*)ctx->dalloc(4ull * n_seqs);
-  R->d_rows = (const u8**)ctx->dalloc(8ull * P);
-  R->d_bits = K->bits;
-  if (!R->d_bits) R->d_bits = R->d_bits_own = (u8*)ctx->dalloc(bits_bytes);
-  bool ok = R->d_keys && R->d_recs && R->d_cell && R->d_pstart && R->d_kcount && R->d_rows && R->d_bits;
-  if (R->last) {
-    R->d_kmers = (u32*)ctx->dalloc(4ull * n_seqs);
-    R->d_hits = K->hits;
-    if (!R->d_hits) R->d_hits = R->d_hits_own = (u32*)ctx->dalloc(4 * table);
-    ok = ok && R->d_kmers && R->d_hits;
-  }
-  if (!ok) return ctx->fail(KMX_E_NOMEM, "kmx_zquery: device allocation failed");
-  KMX_HIP(ctx, hipMemcpyAsync((void*)R->d_rows, (const void*)R->h_rows, 8ull * P, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_cell, 0, 4 * cells, st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_pstart, 0, 4ull * (P + 1), st));
-  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kcount, 0, 4ull * n_seqs, st));
-  if (R->d_bits_own && bits_bytes) KMX_HIP(ctx, hipMemsetAsync(R->d_bits_own, 0, bits_bytes, st));
-  if (R->last && n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
-  if (R->d_hits_own && table) KMX_HIP(ctx, hipMemsetAsync(R->d_hits_own, 0, 4 * table, st));
-  if (n_bases) {
-    KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
-                                   n_tiles, n_chunks, tpc, R->d_keys, R->d_cell, R->d_kcount, st));
-    KMX_HIP(ctx, launch_filter_scan(R->d_cell, (u32)(cells - 1), st));
-    KMX_HIP(ctx, launch_query_parts(R->d_cell, P, n_chunks, R->d_pstart, st));
-    KMX_HIP(ctx, launch_zquery_scatter(R->d_keys, n_bases, n_tiles, n_chunks, tpc, R->d_cell, R->d_recs, st));
-    KMX_HIP(ctx, launch_zquery_rows(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, nb, N, R->d_bits, (u32)ctx->n_cu, st));
-    if (R->last)
-      KMX_HIP(ctx, launch_zquery_window(R->d_keys, (const u64*)K->offsets, n_seqs, n_bases, K->z, R->d_bits, nb, N, R->d_kmers, R->d_hits, (u32)ctx->n_cu, st));
-  }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(R->h_pstart, R->d_pstart, 4ull * (P + 1), hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-static kmx_zquery_result* zquery_new(kmx_ctx* ctx, const kmx_zquery_task* K, u64 n_bases)
-{
-  kmx_zquery_result* R = new kmx_zquery_result();
-  R->ctx = ctx; R->n_seqs = K->n_seqs; R->n_bases = n_bases; R->n_cols = K->n_cols; R->nb = (K->n_cols + 7) / 8; R->n_parts = K->nb_parts;
-  R->pitch = (u32)kmx_zquery_bits_bytes(1, K->n_cols); R->z = K->z; R->last = K->last != 0;
-  return R;
-}
-
-extern "C" int kmx_zquery_dev(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_zquery_dev: null argument");
-  *out = nullptr;
-  int rc = zquery_check(ctx, task, "kmx_zquery_dev");
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  u64 ends[1] = {0};      // the grid's size: the end of the last query
-  KMX_HIP(ctx, hipMemcpyAsync(ends, task->offsets + task->n_seqs, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = zquery_check_bases(ctx, task, ends[0], "kmx_zquery_dev")) != KMX_OK) return rc;
-  kmx_zquery_result* R = zquery_new(ctx, task, ends[0]);
-  if ((rc = zquery_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); zquery_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_zquery_host(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: null argument");
-  *out = nullptr;
-  int rc = zquery_check(ctx, task, "kmx_zquery_host");
-  if (rc != KMX_OK) return rc;
-  const u64 n_bases = task->offsets[task->n_seqs];
-  if (task->offsets[0] != 0) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: offsets[0] must be 0");
-  for (u64 i = 0; i < task->n_seqs; i++) if (task->offsets[i] > task->offsets[i + 1]) return ctx->fail(KMX_E_INVAL, "kmx_zquery_host: offsets must not descend");
-  if ((rc = zquery_check_bases(ctx, task, n_bases, "kmx_zquery_host")) != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_zquery_result* R = zquery_new(ctx, task, n_bases);
-  kmx_zquery_task dt = *task;
-  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); zquery_release(R); return code; };
-  hipError_t e = hipSuccess;
-  auto upload = [&](const void* src, u64 bytes) -> void* {
-    void* d = ctx->dalloc(bytes);
-    if (!d) return nullptr;
-    R->d_in.push_back(d);
-    if (bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->up);
-    return d;
-  };
-  const u64 row_bytes = task->window * ((task->n_cols + 7) / 8);
-  if (!(dt.bases = (const char*)upload(task->bases, n_bases)) || !(dt.offsets = (const uint64_t*)upload(task->offsets, 8 * (task->n_seqs + 1))) ||
-      !(dt.repart = (const uint16_t*)upload(task->repart, 2ull << (2 * task->minim_size))))
-    return fail(ctx->fail(KMX_E_NOMEM, "kmx_zquery_host: upload allocation failed"));
-  for (u32 p = 0; p < task->nb_parts; p++) {
-    if (!task->rows[p]) continue;
-    if (!(drows[p] = (const uint8_t*)upload(task->rows[p], row_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_zquery_host: upload allocation failed"));
-  }
-  dt.rows = drows.data();
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_zquery_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = zquery_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_zquery_result_wait(kmx_zquery_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_zquery: ") + hipGetErrorString(e));
-  // the call has run: its scratch and uploads go back to the pool; the bits table (when the result owns it), n_kmers and hits stay
-  kmx_ctx* c = R->ctx;
-  void* scratch[] = {R->d_keys, R->d_recs, R->d_cell, R->d_pstart, R->d_kcount, (void*)R->d_rows};
-  for (void* p : scratch) c->dfree(p);
-  R->d_keys = R->d_recs = nullptr; R->d_cell = R->d_pstart = R->d_kcount = nullptr; R->d_rows = nullptr;
-  for (void* p : R->d_in) c->dfree(p);
-  R->d_in.clear();
-  c->hfree((void*)R->h_rows); R->h_rows = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_zquery_result_n_seqs(const kmx_zquery_result* R) { return R ? R->n_seqs : 0; }
-static int zquery_copy_out(kmx_zquery_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries)
-{
-  const int rc = kmx_zquery_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (!R->last) return R->ctx->fail(KMX_E_INVAL, "kmx_zquery: n_kmers and hits belong to the last call of a series");
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!entries) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, 4 * entries);
-}
-extern "C" int kmx_zquery_result_copy_kmers(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs) : KMX_E_INVAL; }
-extern "C" int kmx_zquery_result_copy_hits(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols) : KMX_E_INVAL; }
-extern "C" uint32_t* kmx_zquery_result_hits_dev(kmx_zquery_result* R) { return R && R->last && kmx_zquery_result_wait(R) == KMX_OK ? R->d_hits : nullptr; }
-extern "C" uint8_t* kmx_zquery_result_bits_dev(kmx_zquery_result* R) { return R && kmx_zquery_result_wait(R) == KMX_OK ? R->d_bits : nullptr; }
-extern "C" double kmx_zquery_result_kernel_ms(kmx_zquery_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_zquery_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
-extern "C" uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* R)
-{
-  if (!R || kmx_zquery_result_wait(R) != KMX_OK) return 0;
-  u64 found = 0;
-  for (u32 p = 0; p < R->n_parts; p++) if (R->in_call[p]) found += R->h_pstart[p + 1] - R->h_pstart[p];
-  u64 bytes = R->n_bases + found * ((u64)R->nb + R->pitch);
-  if (R->last) {
-    std::vector<u32> nk(R->n_seqs);
-    if (R->n_seqs && kmx_copy_to_host(R->ctx, nk.data(), R->d_kmers, 4 * R->n_seqs) != KMX_OK) return 0;
-    u64 rows = 0;
-    for (u32 n : nk) if (n) rows += (u64)n + R->z;
-    bytes += rows * R->pitch + 4 * R->n_seqs * R->n_cols;
-  }
-  return bytes;
-}
-extern "C" void kmx_zquery_result_free(kmx_zquery_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  zquery_release(R);
-}
-
-// ---- kquery ------------------------------------------------------------------------------------------------------------------------
-// kmx_kquery_dev / kmx_kquery_host: query sequences against the k-mer matrices of a run (kquery.hip).
-struct kmx_kquery_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_seqs = 0, n_bases = 0, stride = 0;
-  u32 n_cols = 0, n_parts = 0, kw = 0;
-  u16* d_parts = nullptr;
-  u64 *d_words = nullptr, *d_recs = nullptr, *d_sums_own = nullptr, *d_sums = nullptr;
-  u32 *d_cell = nullptr, *d_pstart = nullptr, *d_kmers = nullptr, *d_hits_own = nullptr, *d_hits = nullptr, *d_found = nullptr;
-  const u8** d_rows = nullptr;
-  const u8** h_rows = nullptr;          // page-locked: the row pointers and, behind them, the partitions' rows (u32) on their way up
-  std::vector<void*> d_in;              // kmx_kquery_host: the uploads
-  u32* h_tot = nullptr;                 // page-locked: [0] valid k-mers of the call, [1] those that met a row
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
-};
-
-static int kquery_check(kmx_ctx* ctx, const kmx_kquery_task* K, const char* who, u64* stride)
-{
-  const std::string w(who);
-  if (K->kmer_size < 8 || K->kmer_size > 127) return ctx->fail(KMX_E_INVAL, w + ": kmer_size must be in [8, 127]");
-  if (K->minim_size < 4 || K->minim_size > 15 || K->minim_size >= K->kmer_size) return ctx->fail(KMX_E_INVAL, w + ": minim_size must be in [4, 15] and below kmer_size");
-  if (K->key_words != (K->kmer_size + 31) / 32) return ctx->fail(KMX_E_INVAL, w + ": key_words must be ceil(kmer_size / 32)");
-  if (K->nb_parts < 1 || K->nb_parts > 65535) return ctx->fail(KMX_E_INVAL, w + ": nb_parts must be in [1, 65535]");
-  if (K->mode == KMX_MODE_BF || K->mode == KMX_MODE_BFC || K->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter matrices are kmx_query's (KMX_MODE_COUNT and KMX_MODE_PA rows of k-mer matrices only; hash matrices neither)");
-  if (K->mode != KMX_MODE_COUNT && K->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (K->n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
-  if (K->want_sums && K->mode != KMX_MODE_COUNT) return ctx->fail(KMX_E_INVAL, w + ": presence/absence rows have no counts to sum (want_sums needs KMX_MODE_COUNT)");
-  if (K->sums && !K->want_sums) return ctx->fail(KMX_E_INVAL, w + ": a sums table without want_sums");
-  if (!K->repart || !K->rows || !K->n_rows) return ctx->fail(KMX_E_INVAL, w + ": null repartition table, row pointer array or row count array");
-  if (!K->offsets || (K->n_seqs && !K->bases)) return ctx->fail(KMX_E_INVAL, w + ": null reads");
-  *stride = 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? 4ull * K->n_cols : ((u64)K->n_cols + 7) / 8);
-  if (*stride > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  for (u32 p = 0; p < K->nb_parts; p++)
-    if (K->rows[p] && K->n_rows[p] > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in a partition");
-  if (K->n_seqs >= (1ull << 31)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": 2^31 queries and more in one call (send them in batches)");
-  return KMX_OK;
-}
-
-static void kquery_release(kmx_kquery_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_parts, R->d_words, R->d_recs, R->d_cell, R->d_pstart, R->d_kmers, R->d_hits_own, R->d_sums_own, R->d_found, (void*)R->d_rows};
-  for (void* p : blocks) c->dfree(p);
-  for (void* p : R->d_in) c->dfree(p);
-  c->hfree(R->h_tot); c->hfree((void*)R->h_rows);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
-
-// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows and K->n_rows (host arrays)
-static int kquery_queue(kmx_ctx* ctx, const kmx_kquery_task* K, kmx_kquery_result* R)
-{
-  hipStream_t st = ctx->stream;
-  const u64 n_bases = R->n_bases, stride = R->stride;
-  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, kw = K->key_words, skip = 8 * kw;
-  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
-  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
-  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_rows = (const u8**)ctx->halloc(12ull * P))) return ctx->fail(KMX_E_NOMEM, "kmx_kquery: host allocation failed");
-  R->h_tot[0] = R->h_tot[1] = 0;
-  u32* h_nrows = (u32*)(R->h_rows + P);
-  for (u32 p = 0; p < P; p++) { R->h_rows[p] = K->rows[p]; h_nrows[p] = K->rows[p] ? (u32)K->n_rows[p] : 0u; }
-  R->d_parts = (u16*)ctx->dalloc(2 * n_bases);
-  R->d_words = (u64*)ctx->dalloc(8 * n_bases * kw);
-  R->d_recs = (u64*)ctx->dalloc(8 * n_bases);
-  R->d_cell = (u32*)ctx->dalloc(4 * cells);
-  R->d_pstart = (u32*)ctx->dalloc(4ull * (P + 1));
-  R->d_kmers = (u32*)ctx->dalloc(4ull * n_seqs);
-  R->d_rows = (const u8**)ctx->dalloc(12ull * P);
-  R->d_found = (u32*)ctx->dalloc(4);
-  R->d_hits = K->hits;
-  if (!R->d_hits) R->d_hits = R->d_hits_own = (u32*)ctx->dalloc(4 * table);
-  R->d_sums = K->want_sums ? (u64*)K->sums : nullptr;
-  if (K->want_sums && !R->d_sums) R->d_sums = R->d_sums_own = (u64*)ctx->dalloc(8 * table);
-  if (!R->d_parts || !R->d_words || !R->d_recs || !R->d_cell || !R->d_pstart || !R->d_kmers || !R->d_rows || !R->d_found || !R->d_hits || (K->want_sums && !R->d_sums))
-    return ctx->fail(KMX_E_NOMEM, "kmx_kquery: device allocation failed");
-  const u32* d_nrows = (const u32*)(R->d_rows + P);
-  KMX_HIP(ctx, hipMemcpyAsync((void*)R->d_rows, (const void*)R->h_rows, 12ull * P, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_cell, 0, 4 * cells, st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_pstart, 0, 4ull * (P + 1), st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_found, 0, 4, st));
-  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
-  if (R->d_hits_own && table) KMX_HIP(ctx, hipMemsetAsync(R->d_hits_own, 0, 4 * table, st));
-  if (R->d_sums_own && table) KMX_HIP(ctx, hipMemsetAsync(R->d_sums_own, 0, 8 * table, st));
-  if (n_bases) {
-    KMX_HIP(ctx, launch_kquery_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart,
-                                    n_tiles, n_chunks, tpc, R->d_parts, R->d_words, R->d_cell, R->d_kmers, st));
-    KMX_HIP(ctx, launch_filter_scan(R->d_cell, (u32)(cells - 1), st));
-    KMX_HIP(ctx, launch_query_parts(R->d_cell, P, n_chunks, R->d_pstart, st));
-    KMX_HIP(ctx, launch_kquery_scatter(R->d_parts, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, R->d_cell, R->d_recs, st));
-    KMX_HIP(ctx, launch_kquery_search((int)kw, R->d_recs, n_bases, R->d_pstart, P, R->d_rows, d_nrows, stride, R->d_words, n_bases, R->d_found, (u32)ctx->n_cu, st));
-    if (K->mode == KMX_MODE_PA)
-      KMX_HIP(ctx, launch_query_gather_keyed(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, stride, skip, (N + 7) / 8, N, R->d_hits, (u32)ctx->n_cu, st));
-    else
-      KMX_HIP(ctx, launch_kquery_gather(R->d_recs, n_bases, R->d_pstart, P, R->d_rows, stride, skip, N, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
-  }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_pstart + P, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[1], R->d_found, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-static kmx_kquery_result* kquery_new(kmx_ctx* ctx, const kmx_kquery_task* K, u64 n_bases, u64 stride)
-{
-  kmx_kquery_result* R = new kmx_kquery_result();
-  R->ctx = ctx; R->n_seqs = K->n_seqs; R->n_bases = n_bases; R->n_cols = K->n_cols; R->stride = stride; R->n_parts = K->nb_parts; R->kw = K->key_words;
-  return R;
-}
-
-extern "C" int kmx_kquery_dev(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_kquery_dev: null argument");
-  *out = nullptr;
-  u64 stride = 0;
-  int rc = kquery_check(ctx, task, "kmx_kquery_dev", &stride);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  u64 ends[1] = {0};      // the grid's size: the end of the last query
-  KMX_HIP(ctx, hipMemcpyAsync(ends, task->offsets + task->n_seqs, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ends[0] > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_kquery_dev: 2^32 bases and more in one call (send the queries in batches)");
-  kmx_kquery_result* R = kquery_new(ctx, task, ends[0], stride);
-  if ((rc = kquery_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); kquery_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_kquery_host(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_kquery_host: null argument");
-  *out = nullptr;
-  u64 stride = 0;
-  int rc = kquery_check(ctx, task, "kmx_kquery_host", &stride);
-  if (rc != KMX_OK) return rc;
-  const u64 n_bases = task->offsets[task->n_seqs];
-  if (task->offsets[0] != 0) return ctx->fail(KMX_E_INVAL, "kmx_kquery_host: offsets[0] must be 0");
-  for (u64 i = 0; i < task->n_seqs; i++) if (task->offsets[i] > task->offsets[i + 1]) return ctx->fail(KMX_E_INVAL, "kmx_kquery_host: offsets must not descend");
-  if (n_bases > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, "kmx_kquery_host: 2^32 bases and more in one call (send the queries in batches)");
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_kquery_result* R = kquery_new(ctx, task, n_bases, stride);
-  kmx_kquery_task dt = *task;
-  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); kquery_release(R); return code; };
-  hipError_t e = hipSuccess;
-  auto upload = [&](const void* src, u64 bytes) -> void* {
-    void* d = ctx->dalloc(bytes);
-    if (!d) return nullptr;
-    R->d_in.push_back(d);
-    if (bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->up);
-    return d;
-  };
-  if (!(dt.bases = (const char*)upload(task->bases, n_bases)) || !(dt.offsets = (const uint64_t*)upload(task->offsets, 8 * (task->n_seqs + 1))) ||
-      !(dt.repart = (const uint16_t*)upload(task->repart, 2ull << (2 * task->minim_size))))
-    return fail(ctx->fail(KMX_E_NOMEM, "kmx_kquery_host: upload allocation failed"));
-  for (u32 p = 0; p < task->nb_parts; p++) {
-    if (!task->rows[p]) continue;
-    if (!(drows[p] = (const uint8_t*)upload(task->rows[p], task->n_rows[p] * stride))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_kquery_host: upload allocation failed"));
-  }
-  dt.rows = drows.data();
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_kquery_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = kquery_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_kquery_result_wait(kmx_kquery_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_kquery: ") + hipGetErrorString(e));
-  // the call has run: its scratch and uploads go back to the pool; n_kmers and the tables stay
-  kmx_ctx* c = R->ctx;
-  void* scratch[] = {R->d_parts, R->d_words, R->d_recs, R->d_cell, R->d_pstart, R->d_found, (void*)R->d_rows};
-  for (void* p : scratch) c->dfree(p);
-  R->d_parts = nullptr; R->d_words = R->d_recs = nullptr; R->d_cell = R->d_pstart = R->d_found = nullptr; R->d_rows = nullptr;
-  for (void* p : R->d_in) c->dfree(p);
-  R->d_in.clear();
-  c->hfree((void*)R->h_rows); R->h_rows = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_kquery_result_n_seqs(const kmx_kquery_result* R) { return R ? R->n_seqs : 0; }
-static int kquery_copy_out(kmx_kquery_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries, u32 entry_bytes)
-{
-  const int rc = kmx_kquery_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!entries) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  if (!src) return R->ctx->fail(KMX_E_INVAL, "kmx_kquery_result_copy_sums: the call was made without want_sums");
-  return kmx_copy_to_host(R->ctx, dst, src, entry_bytes * entries);
-}
-extern "C" int kmx_kquery_result_copy_kmers(kmx_kquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? kquery_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs, 4) : KMX_E_INVAL; }
-extern "C" int kmx_kquery_result_copy_hits(kmx_kquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{ return R ? kquery_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols, 4) : KMX_E_INVAL; }
-extern "C" int kmx_kquery_result_copy_sums(kmx_kquery_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? kquery_copy_out(R, host_dst, dst_entries, R->d_sums, R->n_seqs * R->n_cols, 8) : KMX_E_INVAL; }
-extern "C" uint32_t* kmx_kquery_result_hits_dev(kmx_kquery_result* R) { return R && kmx_kquery_result_wait(R) == KMX_OK ? R->d_hits : nullptr; }
-extern "C" uint64_t* kmx_kquery_result_sums_dev(kmx_kquery_result* R) { return R && kmx_kquery_result_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
-extern "C" double kmx_kquery_result_kernel_ms(kmx_kquery_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_kquery_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
-extern "C" uint64_t kmx_kquery_result_algo_bytes(kmx_kquery_result* R)
-{
-  if (!R || kmx_kquery_result_wait(R) != KMX_OK) return 0;
-  const u64 table = R->n_seqs * R->n_cols;
-  return R->n_bases + (u64)R->h_tot[1] * R->stride + (u64)R->h_tot[0] * 8 * R->kw + 4 * table + (R->d_sums ? 8 * table : 0);
-}
-extern "C" void kmx_kquery_result_free(kmx_kquery_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  kquery_release(R);
 }

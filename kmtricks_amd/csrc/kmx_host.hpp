@@ -93,6 +93,7 @@ hipError_t launch_combine_place(int kw, const CombineBlock* blocks, u32 nb, u32 
 hipError_t launch_combine_total(const CombineBlock* blocks, u32 nb, const u32* tcnt, const u32* src, u64 cap, int drop_last, u32* tot, hipStream_t st);
 hipError_t launch_combine_move(int pa, const CombineBlock* blocks, u32 nb, u32 kb, u32 n_cols, u32 orb, const u32* src, u64 cap, const u32* tot,
                                u8* out, hipStream_t st);
+// the four sequence-query families; each file holds its C entry points below its kernels, their shared host path is seqquery_host.hpp
 // query.hip: query sequences against the Bloom matrices of a run (kmx_query_dev)
 void query_chunks(u64 n_bases, u32 n_parts, u32* n_tiles, u32* n_chunks, u32* tiles_per_chunk);      // the walk's layout: tiles of 64 positions, chunks of tiles (a wave each)
 hipError_t launch_query_keys(int kw, const char* bases, const u64* offsets, u32 n_seqs, u64 n_bases, int k, int m, const u16* repart, u64 window,

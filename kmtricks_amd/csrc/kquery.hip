@@ -15,7 +15,7 @@
 //                     (KQ_COLS of them a pass): a u32 hit sum and a u64 count sum per column in registers across the records of one
 //                     query, flushed with atomic adds when the query changes and at the run's end
 // Nothing holds a row in LDS: no limit on columns.
-#include "kmx_host.hpp"
+#include "seqquery_host.hpp"
 #include "kmer_dev.hpp"
 
 namespace kmx {
@@ -248,3 +248,118 @@ hipError_t launch_kquery_gather(const u64* recs, u64 rec_bound, const u32* pstar
 }
 
 }  // namespace kmx
+
+using namespace kmx;
+
+// ---- kquery ------------------------------------------------------------------------------------------------------------------------
+// kmx_kquery_dev / kmx_kquery_host: query sequences against the k-mer matrices of a run.  The shared host path: seqquery_host.hpp;
+// h_tot[0] the valid k-mers of the call, [1] those that met a row.
+struct kmx_kquery_result : SeqResult {
+  u64 stride = 0;
+  u32 kw = 0;
+  u32 *d_kmers = nullptr, *d_hits = nullptr;
+  u64* d_sums = nullptr;                // null: the call was made without want_sums
+};
+
+static int kquery_check(kmx_ctx* ctx, const kmx_kquery_task* K, const char* who, u64* stride)
+{
+  const SeqCheck c{ctx, who};
+  int rc;
+  if ((rc = c.kmer_size(K->kmer_size)) || (rc = c.minim_size(K->minim_size, K->kmer_size))) return rc;
+  if (K->key_words != (K->kmer_size + 31) / 32) return c.no(KMX_E_INVAL, ": key_words must be ceil(kmer_size / 32)");
+  if ((rc = c.nb_parts(K->nb_parts))) return rc;
+  if (K->mode == KMX_MODE_BF || K->mode == KMX_MODE_BFC || K->mode == KMX_MODE_BFT)
+    return c.no(KMX_E_UNSUPPORTED, ": Bloom filter matrices are kmx_query's (KMX_MODE_COUNT and KMX_MODE_PA rows of k-mer matrices only; hash matrices neither)");
+  if (K->mode != KMX_MODE_COUNT && K->mode != KMX_MODE_PA) return c.no(KMX_E_INVAL, ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
+  if ((rc = c.n_cols(K->n_cols))) return rc;
+  if (K->want_sums && K->mode != KMX_MODE_COUNT) return c.no(KMX_E_INVAL, ": presence/absence rows have no counts to sum (want_sums needs KMX_MODE_COUNT)");
+  if (K->sums && !K->want_sums) return c.no(KMX_E_INVAL, ": a sums table without want_sums");
+  if (!K->repart || !K->rows || !K->n_rows) return c.no(KMX_E_INVAL, ": null repartition table, row pointer array or row count array");
+  if ((rc = c.reads(K->offsets, K->n_seqs, K->bases))) return rc;
+  *stride = 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? 4ull * K->n_cols : ((u64)K->n_cols + 7) / 8);
+  if ((rc = c.row_fits(*stride))) return rc;
+  for (u32 p = 0; p < K->nb_parts; p++)
+    if (K->rows[p] && K->n_rows[p] > 0xFFFFFF00ull) return c.no(KMX_E_UNSUPPORTED, ": more than 2^32 - 256 rows in a partition");
+  return c.n_seqs(K->n_seqs);
+}
+
+// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows and K->n_rows (host arrays)
+static int kquery_queue(kmx_ctx* ctx, const kmx_kquery_task* K, kmx_kquery_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u64 n_bases = R->n_bases, stride = R->stride;
+  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, kw = K->key_words, skip = 8 * kw;
+  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
+  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
+  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N;
+  u16* d_parts = (u16*)R->tmp(2 * n_bases);
+  u64* d_words = (u64*)R->tmp(8 * n_bases * kw);
+  u64* d_recs = (u64*)R->tmp(8 * n_bases);
+  u32* d_cell = (u32*)R->tmp(4 * cells);
+  u32* d_pstart = (u32*)R->tmp(4ull * (P + 1));
+  R->d_kmers = (u32*)R->keep(4ull * n_seqs);
+  u32* d_found = (u32*)R->tmp(4);
+  u32* hits_own = K->hits ? nullptr : (u32*)R->keep(4 * table);
+  R->d_hits = K->hits ? K->hits : hits_own;
+  u64* sums_own = K->want_sums && !K->sums ? (u64*)R->keep(8 * table) : nullptr;
+  R->d_sums = !K->want_sums ? nullptr : K->sums ? (u64*)K->sums : sums_own;
+  const int rc = seq_queue_head(R, K->rows, K->n_rows, 64);      // the row counts travel as u32 behind the row pointers
+  if (rc != KMX_OK) return rc;
+  const u32* d_nrows = (const u32*)(R->d_rows + P);
+  KMX_HIP(ctx, hipMemsetAsync(d_cell, 0, 4 * cells, st));
+  KMX_HIP(ctx, hipMemsetAsync(d_pstart, 0, 4ull * (P + 1), st));
+  KMX_HIP(ctx, hipMemsetAsync(d_found, 0, 4, st));
+  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
+  if (hits_own && table) KMX_HIP(ctx, hipMemsetAsync(hits_own, 0, 4 * table, st));
+  if (sums_own && table) KMX_HIP(ctx, hipMemsetAsync(sums_own, 0, 8 * table, st));
+  if (n_bases) {
+    KMX_HIP(ctx, launch_kquery_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart,
+                                    n_tiles, n_chunks, tpc, d_parts, d_words, d_cell, R->d_kmers, st));
+    KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
+    KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
+    KMX_HIP(ctx, launch_kquery_scatter(d_parts, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
+    KMX_HIP(ctx, launch_kquery_search((int)kw, d_recs, n_bases, d_pstart, P, R->d_rows, d_nrows, stride, d_words, n_bases, d_found, (u32)ctx->n_cu, st));
+    if (K->mode == KMX_MODE_PA)
+      KMX_HIP(ctx, launch_query_gather_keyed(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, (N + 7) / 8, N, R->d_hits, (u32)ctx->n_cu, st));
+    else
+      KMX_HIP(ctx, launch_kquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, N, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
+  }
+  return seq_queue_tail(R, d_pstart + P, 1, d_found);
+}
+
+static int kquery_call(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out, bool host, const char* who)
+{
+  u64 n_bases = 0, stride = 0;
+  int rc = seq_args(ctx, task, out, who);
+  if (rc == KMX_OK) rc = kquery_check(ctx, task, who, &stride);
+  if (rc == KMX_OK) rc = seq_n_bases(ctx, task->offsets, task->n_seqs, host, who, &n_bases);
+  if (rc != KMX_OK) return rc;
+  kmx_kquery_result* R = new kmx_kquery_result();
+  R->init(ctx, "kmx_kquery", *task, n_bases); R->stride = stride; R->kw = task->key_words;
+  kmx_kquery_task dt = *task;
+  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
+  if (host) rc = seq_upload(R, &dt, drows, who, [&](u32 p) { return task->n_rows[p] * stride; });
+  if (rc == KMX_OK) rc = kquery_queue(ctx, &dt, R);
+  return seq_finish(R, rc, host, out);
+}
+extern "C" int kmx_kquery_dev(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out) { return kquery_call(ctx, task, out, false, "kmx_kquery_dev"); }
+extern "C" int kmx_kquery_host(kmx_ctx* ctx, const kmx_kquery_task* task, kmx_kquery_result** out) { return kquery_call(ctx, task, out, true, "kmx_kquery_host"); }
+
+extern "C" int kmx_kquery_result_wait(kmx_kquery_result* R) { return seq_wait(R); }
+extern "C" uint64_t kmx_kquery_result_n_seqs(const kmx_kquery_result* R) { return R ? R->n_seqs : 0; }
+extern "C" int kmx_kquery_result_copy_kmers(kmx_kquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs, 4) : KMX_E_INVAL; }
+extern "C" int kmx_kquery_result_copy_hits(kmx_kquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols, 4) : KMX_E_INVAL; }
+extern "C" int kmx_kquery_result_copy_sums(kmx_kquery_result* R, uint64_t* host_dst, uint64_t dst_entries)
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_sums, R->n_seqs * R->n_cols, 8, "kmx_kquery_result_copy_sums: the call was made without want_sums") : KMX_E_INVAL; }
+extern "C" uint32_t* kmx_kquery_result_hits_dev(kmx_kquery_result* R) { return R && seq_wait(R) == KMX_OK ? R->d_hits : nullptr; }
+extern "C" uint64_t* kmx_kquery_result_sums_dev(kmx_kquery_result* R) { return R && seq_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
+extern "C" double kmx_kquery_result_kernel_ms(kmx_kquery_result* R) { return seq_kernel_ms(R); }
+extern "C" uint64_t kmx_kquery_result_algo_bytes(kmx_kquery_result* R)
+{
+  if (!R || seq_wait(R) != KMX_OK) return 0;
+  const u64 table = R->n_seqs * R->n_cols;
+  return R->n_bases + (u64)R->h_tot[1] * R->stride + (u64)R->h_tot[0] * 8 * R->kw + 4 * table + (R->d_sums ? 8 * table : 0);
+}
+extern "C" void kmx_kquery_result_free(kmx_kquery_result* R) { seq_free(R); }

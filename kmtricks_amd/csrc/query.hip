@@ -20,7 +20,7 @@
 //                    non-zero column sums go to hits[query][column] with u32 atomic adds whenever the query changes and at the end.
 //                    Integer adds commute: the table does not depend on scheduling.
 // Nothing holds a row or a query in LDS: no limit on columns or on a query's length below 2^32 positions.
-#include "kmx_host.hpp"
+#include "seqquery_host.hpp"
 #include "kmer_dev.hpp"
 
 namespace kmx {
@@ -231,3 +231,75 @@ hipError_t launch_query_gather_keyed(const u64* recs, u64 rec_bound, const u32* 
 { return query_gather<true>(recs, rec_bound, pstart, n_parts, rows, nb, n_cols, hits, stride, skip, n_cu, st); }
 
 }  // namespace kmx
+
+using namespace kmx;
+
+// ---- query -------------------------------------------------------------------------------------------------------------------------
+// kmx_query_dev / kmx_query_host: query sequences against the Bloom matrices of a run.  The shared host path: seqquery_host.hpp.
+struct kmx_query_result : SeqResult {
+  u32 nb = 0;
+  u32 *d_kmers = nullptr, *d_hits = nullptr;      // d_hits: the result's own table or the caller's
+};
+
+// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
+static int query_queue(kmx_ctx* ctx, const kmx_query_task* K, kmx_query_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u64 n_bases = R->n_bases;
+  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, nb = R->nb, kw = (K->kmer_size + 31) / 32;
+  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
+  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
+  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N;
+  u64* d_keys = (u64*)R->tmp(8 * n_bases);
+  u64* d_recs = (u64*)R->tmp(8 * n_bases);
+  u32* d_cell = (u32*)R->tmp(4 * cells);
+  u32* d_pstart = (u32*)R->tmp(4ull * (P + 1));
+  R->d_kmers = (u32*)R->keep(4ull * n_seqs);
+  u32* hits_own = K->hits ? nullptr : (u32*)R->keep(4 * table);
+  R->d_hits = K->hits ? K->hits : hits_own;
+  const int rc = seq_queue_head(R, K->rows, nullptr, 64);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_cell, 0, 4 * cells, st));
+  KMX_HIP(ctx, hipMemsetAsync(d_pstart, 0, 4ull * (P + 1), st));
+  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
+  if (hits_own && table) KMX_HIP(ctx, hipMemsetAsync(hits_own, 0, 4 * table, st));
+  if (n_bases) {
+    KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
+                                   n_tiles, n_chunks, tpc, d_keys, d_cell, R->d_kmers, st));
+    KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
+    KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
+    KMX_HIP(ctx, launch_query_scatter(d_keys, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
+    KMX_HIP(ctx, launch_query_gather(d_recs, n_bases, d_pstart, P, R->d_rows, nb, N, R->d_hits, (u32)ctx->n_cu, st));
+  }
+  return seq_queue_tail(R, d_pstart + P, 1);      // h_tot[0]: the valid k-mers of the call
+}
+
+static int query_call(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out, bool host, const char* who)
+{
+  u64 n_bases = 0;
+  int rc = seq_args(ctx, task, out, who);
+  if (rc == KMX_OK) rc = seq_check_bloom(ctx, task, who);
+  if (rc == KMX_OK) rc = seq_n_bases(ctx, task->offsets, task->n_seqs, host, who, &n_bases);
+  if (rc != KMX_OK) return rc;
+  kmx_query_result* R = new kmx_query_result();
+  R->init(ctx, "kmx_query", *task, n_bases); R->nb = (task->n_cols + 7) / 8;
+  kmx_query_task dt = *task;
+  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
+  if (host) rc = seq_upload(R, &dt, drows, who, [&](u32) { return task->window * R->nb; });
+  if (rc == KMX_OK) rc = query_queue(ctx, &dt, R);
+  return seq_finish(R, rc, host, out);
+}
+extern "C" int kmx_query_dev(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out) { return query_call(ctx, task, out, false, "kmx_query_dev"); }
+extern "C" int kmx_query_host(kmx_ctx* ctx, const kmx_query_task* task, kmx_query_result** out) { return query_call(ctx, task, out, true, "kmx_query_host"); }
+
+extern "C" int kmx_query_result_wait(kmx_query_result* R) { return seq_wait(R); }
+extern "C" uint64_t kmx_query_result_n_seqs(const kmx_query_result* R) { return R ? R->n_seqs : 0; }
+extern "C" int kmx_query_result_copy_kmers(kmx_query_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs, 4) : KMX_E_INVAL; }
+extern "C" int kmx_query_result_copy_hits(kmx_query_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? seq_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols, 4) : KMX_E_INVAL; }
+extern "C" uint32_t* kmx_query_result_hits_dev(kmx_query_result* R) { return R && seq_wait(R) == KMX_OK ? R->d_hits : nullptr; }
+extern "C" double kmx_query_result_kernel_ms(kmx_query_result* R) { return seq_kernel_ms(R); }
+extern "C" uint64_t kmx_query_result_algo_bytes(kmx_query_result* R)
+{ return R && seq_wait(R) == KMX_OK ? R->n_bases + (u64)R->h_tot[0] * R->nb + 4 * R->n_seqs * R->n_cols : 0; }
+extern "C" void kmx_query_result_free(kmx_query_result* R) { seq_free(R); }

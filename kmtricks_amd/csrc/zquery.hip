@@ -16,7 +16,7 @@
 //                     and at the item's end.  j is a K-position when keys[j] and keys[j + z] are both set (z < k: the positions
 //                     between them are valid and lie in the same query).  The lane that owns dword 0 counts them into n_kmers.
 // Nothing holds a row or a query in LDS; no kernel uses scratch memory.
-#include "kmx_host.hpp"
+#include "seqquery_host.hpp"
 #include "kmer_dev.hpp"
 
 namespace kmx {
@@ -203,3 +203,119 @@ hipError_t launch_zquery_window(const u64* keys, const u64* offsets, u32 n_seqs,
 }
 
 }  // namespace kmx
+
+using namespace kmx;
+
+// ---- zquery ------------------------------------------------------------------------------------------------------------------------
+// kmx_zquery_dev / kmx_zquery_host: the (k + z)-mers of query sequences against the Bloom matrices of a run.  The shared host path:
+// seqquery_host.hpp; h_tot holds the first record of every partition, [n_parts] the valid k-mers of the call.
+struct kmx_zquery_result : SeqResult {
+  u32 nb = 0, pitch = 0, z = 0;
+  bool last = false;
+  u32 *d_kmers = nullptr, *d_hits = nullptr;      // (the last call of a series only)
+  u8* d_bits = nullptr;                           // the series' table: the result's own (a series' first call) or the caller's
+  std::vector<bool> in_call;                      // partition p is part of the call
+};
+
+extern "C" uint64_t kmx_zquery_bits_bytes(uint64_t n_bases, uint32_t n_cols)
+{ return n_bases * (4ull * ((((u64)n_cols + 7) / 8 + 3) / 4)); }
+
+// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer but K->rows (a host array of device pointers)
+static int zquery_queue(kmx_ctx* ctx, const kmx_zquery_task* K, kmx_zquery_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u64 n_bases = R->n_bases;
+  const u32 n_seqs = (u32)R->n_seqs, P = K->nb_parts, N = K->n_cols, nb = R->nb, kw = (K->kmer_size + 31) / 32;
+  u32 n_tiles = 0, n_chunks = 1, tpc = 1;
+  query_chunks(n_bases, P, &n_tiles, &n_chunks, &tpc);
+  const u64 cells = (u64)P * n_chunks + 1, table = (u64)n_seqs * N, bits_bytes = kmx_zquery_bits_bytes(n_bases, N);
+  R->in_call.assign(P, false);
+  for (u32 p = 0; p < P; p++) R->in_call[p] = K->rows[p] != nullptr;
+  u64* d_keys = (u64*)R->tmp(8 * n_bases);
+  u64* d_recs = (u64*)R->tmp(8 * n_bases);
+  u32* d_cell = (u32*)R->tmp(4 * cells);
+  u32* d_pstart = (u32*)R->tmp(4ull * (P + 1));
+  u32* d_kcount = (u32*)R->tmp(4ull * n_seqs);      // k_query_keys' k-mers per query (the result counts K-positions)
+  u8* bits_own = K->bits ? nullptr : (u8*)R->keep(bits_bytes);
+  R->d_bits = K->bits ? K->bits : bits_own;
+  u32* hits_own = nullptr;
+  if (R->last) {
+    R->d_kmers = (u32*)R->keep(4ull * n_seqs);
+    if (!K->hits) hits_own = (u32*)R->keep(4 * table);
+    R->d_hits = K->hits ? K->hits : hits_own;
+  }
+  const int rc = seq_queue_head(R, K->rows, nullptr, 4ull * (P + 1));
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_cell, 0, 4 * cells, st));
+  KMX_HIP(ctx, hipMemsetAsync(d_pstart, 0, 4ull * (P + 1), st));
+  if (n_seqs) KMX_HIP(ctx, hipMemsetAsync(d_kcount, 0, 4ull * n_seqs, st));
+  if (bits_own && bits_bytes) KMX_HIP(ctx, hipMemsetAsync(bits_own, 0, bits_bytes, st));
+  if (R->last && n_seqs) KMX_HIP(ctx, hipMemsetAsync(R->d_kmers, 0, 4ull * n_seqs, st));
+  if (hits_own && table) KMX_HIP(ctx, hipMemsetAsync(hits_own, 0, 4 * table, st));
+  if (n_bases) {
+    KMX_HIP(ctx, launch_query_keys((int)kw, K->bases, (const u64*)K->offsets, n_seqs, n_bases, (int)K->kmer_size, (int)K->minim_size, K->repart, K->window,
+                                   n_tiles, n_chunks, tpc, d_keys, d_cell, d_kcount, st));
+    KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
+    KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
+    KMX_HIP(ctx, launch_zquery_scatter(d_keys, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
+    KMX_HIP(ctx, launch_zquery_rows(d_recs, n_bases, d_pstart, P, R->d_rows, nb, N, R->d_bits, (u32)ctx->n_cu, st));
+    if (R->last)
+      KMX_HIP(ctx, launch_zquery_window(d_keys, (const u64*)K->offsets, n_seqs, n_bases, K->z, R->d_bits, nb, N, R->d_kmers, R->d_hits, (u32)ctx->n_cu, st));
+  }
+  return seq_queue_tail(R, d_pstart, P + 1);
+}
+
+static int zquery_call(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out, bool host, const char* who)
+{
+  u64 n_bases = 0;
+  int rc = seq_args(ctx, task, out, who);
+  if (rc == KMX_OK) rc = seq_check_bloom(ctx, task, who);      // the query section's limits, then the section's own
+  if (rc == KMX_OK && (task->z > 8 || task->z >= task->kmer_size)) rc = ctx->fail(KMX_E_INVAL, std::string(who) + ": z must be in [0, 8] and below kmer_size");
+  if (rc == KMX_OK) rc = seq_n_bases(ctx, task->offsets, task->n_seqs, host, who, &n_bases);
+  if (rc == KMX_OK && kmx_zquery_bits_bytes(n_bases, task->n_cols) > (1ull << 40))
+    rc = ctx->fail(KMX_E_UNSUPPORTED, std::string(who) + ": a bits table of more than 2^40 bytes (send the queries in batches)");
+  if (rc != KMX_OK) return rc;
+  kmx_zquery_result* R = new kmx_zquery_result();
+  R->init(ctx, "kmx_zquery", *task, n_bases); R->nb = (task->n_cols + 7) / 8;
+  R->pitch = (u32)kmx_zquery_bits_bytes(1, task->n_cols); R->z = task->z; R->last = task->last != 0;
+  kmx_zquery_task dt = *task;
+  std::vector<const uint8_t*> drows(task->nb_parts, nullptr);
+  if (host) rc = seq_upload(R, &dt, drows, who, [&](u32) { return task->window * R->nb; });
+  if (rc == KMX_OK) rc = zquery_queue(ctx, &dt, R);
+  return seq_finish(R, rc, host, out);
+}
+extern "C" int kmx_zquery_dev(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out) { return zquery_call(ctx, task, out, false, "kmx_zquery_dev"); }
+extern "C" int kmx_zquery_host(kmx_ctx* ctx, const kmx_zquery_task* task, kmx_zquery_result** out) { return zquery_call(ctx, task, out, true, "kmx_zquery_host"); }
+
+extern "C" int kmx_zquery_result_wait(kmx_zquery_result* R) { return seq_wait(R); }
+extern "C" uint64_t kmx_zquery_result_n_seqs(const kmx_zquery_result* R) { return R ? R->n_seqs : 0; }
+static int zquery_copy_out(kmx_zquery_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries)
+{
+  const int rc = seq_wait(R);
+  if (rc != KMX_OK) return rc;
+  if (!R->last) return R->ctx->fail(KMX_E_INVAL, "kmx_zquery: n_kmers and hits belong to the last call of a series");
+  return seq_copy_out(R, dst, dst_entries, src, entries, 4);
+}
+extern "C" int kmx_zquery_result_copy_kmers(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_kmers, R->n_seqs) : KMX_E_INVAL; }
+extern "C" int kmx_zquery_result_copy_hits(kmx_zquery_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return R ? zquery_copy_out(R, host_dst, dst_entries, R->d_hits, R->n_seqs * R->n_cols) : KMX_E_INVAL; }
+extern "C" uint32_t* kmx_zquery_result_hits_dev(kmx_zquery_result* R) { return R && R->last && seq_wait(R) == KMX_OK ? R->d_hits : nullptr; }
+extern "C" uint8_t* kmx_zquery_result_bits_dev(kmx_zquery_result* R) { return R && seq_wait(R) == KMX_OK ? R->d_bits : nullptr; }
+extern "C" double kmx_zquery_result_kernel_ms(kmx_zquery_result* R) { return seq_kernel_ms(R); }
+extern "C" uint64_t kmx_zquery_result_algo_bytes(kmx_zquery_result* R)
+{
+  if (!R || seq_wait(R) != KMX_OK) return 0;
+  u64 found = 0;
+  for (u32 p = 0; p < R->n_parts; p++) if (R->in_call[p]) found += R->h_tot[p + 1] - R->h_tot[p];
+  u64 bytes = R->n_bases + found * ((u64)R->nb + R->pitch);
+  if (R->last) {
+    std::vector<u32> nk(R->n_seqs);
+    if (R->n_seqs && kmx_copy_to_host(R->ctx, nk.data(), R->d_kmers, 4 * R->n_seqs) != KMX_OK) return 0;
+    u64 rows = 0;
+    for (u32 n : nk) if (n) rows += (u64)n + R->z;
+    bytes += rows * R->pitch + 4 * R->n_seqs * R->n_cols;
+  }
+  return bytes;
+}
+extern "C" void kmx_zquery_result_free(kmx_zquery_result* R) { seq_free(R); }

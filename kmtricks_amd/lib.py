@@ -767,36 +767,45 @@ class Context:
         finally:
             r.free()
 
+    def _seq_inputs(self, reads, repart, matrices, fit):
+        """the ctypes pieces of a sequence-query call.  reads: a list of sequences (str / bytes) or pack_reads() output; matrices[p]: bytes,
+        a uint8 array or None; fit(p, a) is the family's rule for the flat uint8 body a of partition p: it raises ValueError, or returns
+        the array to send.  -> (bases, offsets, n_seqs, repart, rows, keepalive): pointers into arrays that keepalive holds"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        rep = np.ascontiguousarray(repart, dtype=np.uint16)
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        keepalive, rows = [bb, offs, rep], (C.c_void_p * len(matrices))()
+        for p, mt in enumerate(matrices):
+            if mt is None:
+                continue
+            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+            a = fit(p, a)
+            keepalive.append(a)
+            rows[p] = a.ctypes.data
+        return bb.ctypes.data, offs.ctypes.data, len(offs) - 1, rep.ctypes.data, rows, keepalive
+
+    @staticmethod
+    def _window_rows(window, nb, checked=True):
+        """_seq_inputs' rule for a Bloom matrix: a body is window rows of nb bytes"""
+        def fit(p, a):
+            if checked and len(a) != window * nb:
+                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
+            return a
+        return fit
+
     def query(self, reads, k, m, repart, window, n_cols, matrices, hits_dev=None, keep=False):
         """kmx_query_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
         .cmbf (bytes or a uint8 array of window * ceil(n_cols / 8) bytes) or None (the partition is not part of the call);
         hits_dev None or a device pointer to a uint32 table [queries, n_cols] the call adds to.
         -> QueryOutput (numpy copies), or with keep the QueryResult itself (the table left in HBM; .free() it)"""
-        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rep = np.ascontiguousarray(repart, dtype=np.uint16)
-        nb = (n_cols + 7) // 8
-        keepalive, rows = [], (C.c_void_p * len(matrices))()
-        for p, mt in enumerate(matrices):
-            if mt is None:
-                continue
-            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
-            if len(a) != window * nb:
-                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
-            keepalive.append(a)
-            rows[p] = a.ctypes.data
-        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
-        t = KmxQueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows, hits_dev)
+        bases, offs, n_seqs, rep, rows, keepalive = self._seq_inputs(reads, repart, matrices, self._window_rows(window, (n_cols + 7) // 8))
+        t = KmxQueryTask(bases, offs, n_seqs, k, m, rep, len(matrices), n_cols, window, rows, hits_dev)
         res = _vp()
         self._check(_lib.kmx_query_host(self._h, C.byref(t), C.byref(res)), "kmx_query_host")
         r = QueryResult(self, res, n_cols)
         r.wait()      # (the host buffers above may go once the call has run)
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(r, keep)
 
     def query_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, window, n_cols, rows_dev, hits_dev=None, keep=False):
         """kmx_query_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
@@ -805,13 +814,7 @@ class Context:
         t = KmxQueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, window, rows, hits_dev)
         res = _vp()
         self._check(_lib.kmx_query_dev(self._h, C.byref(t), C.byref(res)), "kmx_query_dev")
-        r = QueryResult(self, res, n_cols)
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(QueryResult(self, res, n_cols), keep)
 
     @staticmethod
     def _zquery_result(r, last, keep, owns_bits):
@@ -832,22 +835,8 @@ class Context:
         the later ones pass that pointer, the one with last=True produces the result.  hits_dev None or a device pointer to a uint32
         table [queries, n_cols] the last call adds to.
         -> QueryOutput (numpy copies) when last, else None; with keep the ZqueryResult itself (.free() it)"""
-        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rep = np.ascontiguousarray(repart, dtype=np.uint16)
-        nb = (n_cols + 7) // 8
-        keepalive, rows = [], (C.c_void_p * len(matrices))()
-        for p, mt in enumerate(matrices):
-            if mt is None:
-                continue
-            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
-            if len(a) != window * nb:
-                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
-            keepalive.append(a)
-            rows[p] = a.ctypes.data
-        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
-        t = KmxZqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows,
-                          z, 1 if last else 0, bits_dev, hits_dev)
+        bases, offs, n_seqs, rep, rows, keepalive = self._seq_inputs(reads, repart, matrices, self._window_rows(window, (n_cols + 7) // 8))
+        t = KmxZqueryTask(bases, offs, n_seqs, k, m, rep, len(matrices), n_cols, window, rows, z, 1 if last else 0, bits_dev, hits_dev)
         res = _vp()
         self._check(_lib.kmx_zquery_host(self._h, C.byref(t), C.byref(res)), "kmx_zquery_host")
         r = ZqueryResult(self, res, n_cols)
@@ -863,6 +852,10 @@ class Context:
         self._check(_lib.kmx_zquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_zquery_dev")
         return self._zquery_result(ZqueryResult(self, res, n_cols), last, keep, bits_dev is None)
 
+    @staticmethod
+    def _kquery_sums(sums):
+        return (1, None) if sums is True else (0, None) if sums is False or sums is None else (1, sums)
+
     def kquery(self, reads, k, m, repart, n_cols, key_words, mode, matrices, n_rows=None, hits_dev=None, sums=False, keep=False):
         """kmx_kquery_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
         .count / .pa (bytes or a uint8 array of whole rows: key words, then n_cols u32 counts or ceil(n_cols / 8) bytes) or None (the
@@ -870,53 +863,34 @@ class Context:
         pointer to a uint32 table [queries, n_cols] the call adds to; sums False, True (the result owns the uint64 table) or a device
         pointer to a uint64 table the call adds to.
         -> KqueryOutput (numpy copies), or with keep the KqueryResult itself (the tables left in HBM; .free() it)"""
-        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rep = np.ascontiguousarray(repart, dtype=np.uint16)
         stride = key_words * 8 + (4 * n_cols if mode == MODE_COUNT else (n_cols + 7) // 8)
-        keepalive, rows, nr = [], (C.c_void_p * len(matrices))(), (C.c_uint64 * len(matrices))()
-        for p, mt in enumerate(matrices):
-            if mt is None:
-                continue
-            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
+        nr = (C.c_uint64 * len(matrices))()
+
+        def fit(p, a):
             if n_rows is None and len(a) % stride:
                 raise ValueError(f"partition {p}: {len(a)} bytes are not whole rows of {stride} bytes")
             nr[p] = len(a) // stride if n_rows is None else n_rows[p]
-            if not len(a):
-                a = np.zeros(1, np.uint8)      # (a partition of no rows is still part of the call)
-            keepalive.append(a)
-            rows[p] = a.ctypes.data
-        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
-        want, sums_dev = (1, None) if sums is True else (0, None) if sums is False or sums is None else (1, sums)
-        t = KmxKqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, key_words, mode, nr, rows,
-                          hits_dev, sums_dev, want)
+            return a if len(a) else np.zeros(1, np.uint8)      # (a partition of no rows is still part of the call)
+
+        bases, offs, n_seqs, rep, rows, keepalive = self._seq_inputs(reads, repart, matrices, fit)
+        want, sums_dev = self._kquery_sums(sums)
+        t = KmxKqueryTask(bases, offs, n_seqs, k, m, rep, len(matrices), n_cols, key_words, mode, nr, rows, hits_dev, sums_dev, want)
         res = _vp()
         self._check(_lib.kmx_kquery_host(self._h, C.byref(t), C.byref(res)), "kmx_kquery_host")
         r = KqueryResult(self, res, n_cols, bool(want))
         r.wait()      # (the host buffers above may go once the call has run)
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(r, keep)
 
     def kquery_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, n_cols, key_words, mode, rows_dev, n_rows, hits_dev=None, sums=False, keep=False):
         """kmx_kquery_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
         repartition table; rows_dev[p] a device pointer to partition p's matrix body or None, n_rows[p] its rows.  -> as kquery"""
         rows = (C.c_void_p * len(rows_dev))(*rows_dev)
         nr = (C.c_uint64 * len(rows_dev))(*[int(x) for x in n_rows])
-        want, sums_dev = (1, None) if sums is True else (0, None) if sums is False or sums is None else (1, sums)
+        want, sums_dev = self._kquery_sums(sums)
         t = KmxKqueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, key_words, mode, nr, rows, hits_dev, sums_dev, want)
         res = _vp()
         self._check(_lib.kmx_kquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_kquery_dev")
-        r = KqueryResult(self, res, n_cols, bool(want))
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(KqueryResult(self, res, n_cols, bool(want)), keep)
 
     def cquery(self, reads, k, m, repart, window, n_cols, matrices, bitw, min_class=1, hits_dev=None, sums_dev=None, keep=False):
         """kmx_cquery_host: reads a list of sequences (str / bytes) or pack_reads() output; matrices[p] the body of partition p's
@@ -924,32 +898,14 @@ class Context:
         call); a hit is a class of at least min_class; hits_dev / sums_dev both None or device pointers to a uint32 and a uint64 table
         [queries, n_cols] the call adds to.
         -> CqueryOutput (numpy copies), or with keep the CqueryResult itself (the tables left in HBM; .free() it)"""
-        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rep = np.ascontiguousarray(repart, dtype=np.uint16)
-        nb = (n_cols * bitw + 7) // 8
-        keepalive, rows = [], (C.c_void_p * len(matrices))()
-        for p, mt in enumerate(matrices):
-            if mt is None:
-                continue
-            a = np.frombuffer(mt, dtype=np.uint8) if isinstance(mt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(mt, dtype=np.uint8).reshape(-1)
-            if 1 <= bitw <= 8 and len(a) != window * nb:      # (a bitw the library refuses is the library's to refuse)
-                raise ValueError(f"partition {p}: {len(a)} bytes are not {window} rows of {nb} bytes")
-            keepalive.append(a)
-            rows[p] = a.ctypes.data
-        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
-        t = KmxCqueryTask(bb.ctypes.data, offs.ctypes.data, len(offs) - 1, k, m, rep.ctypes.data, len(matrices), n_cols, window, rows,
-                          bitw, min_class, hits_dev, sums_dev)
+        fit = self._window_rows(window, (n_cols * bitw + 7) // 8, 1 <= bitw <= 8)      # (a bitw the library refuses is the library's to refuse)
+        bases, offs, n_seqs, rep, rows, keepalive = self._seq_inputs(reads, repart, matrices, fit)
+        t = KmxCqueryTask(bases, offs, n_seqs, k, m, rep, len(matrices), n_cols, window, rows, bitw, min_class, hits_dev, sums_dev)
         res = _vp()
         self._check(_lib.kmx_cquery_host(self._h, C.byref(t), C.byref(res)), "kmx_cquery_host")
         r = CqueryResult(self, res, n_cols)
         r.wait()      # (the host buffers above may go once the call has run)
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(r, keep)
 
     def cquery_dev(self, bases_dev, offsets_dev, n_seqs, k, m, repart_dev, window, n_cols, rows_dev, bitw, min_class=1, hits_dev=None, sums_dev=None, keep=False):
         """kmx_cquery_dev: device pointers (a torch tensor's data_ptr()) to the bases, the uint64 offsets [n_seqs + 1] and the uint16
@@ -958,13 +914,7 @@ class Context:
         t = KmxCqueryTask(bases_dev, offsets_dev, n_seqs, k, m, repart_dev, len(rows_dev), n_cols, window, rows, bitw, min_class, hits_dev, sums_dev)
         res = _vp()
         self._check(_lib.kmx_cquery_dev(self._h, C.byref(t), C.byref(res)), "kmx_cquery_dev")
-        r = CqueryResult(self, res, n_cols)
-        if keep:
-            return r
-        try:
-            return r.output()
-        finally:
-            r.free()
+        return self._finish(CqueryResult(self, res, n_cols), keep)
 
     @staticmethod
     def _dist_mins(mins):
@@ -1335,43 +1285,50 @@ class KqueryOutput:
         self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
 
 
-class KqueryResult:
-    def __init__(self, ctx, h, n_cols, has_sums):
-        self._ctx, self._h, self._n, self._sums = ctx, h, n_cols, has_sums
+class _SeqResult:
+    """what the results of the four sequence-query families share: the calls kmx_<_prefix>_result_<name> of libkmx"""
+    _prefix = None
+
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def _call(self, name, *args, check=False):
+        full = f"kmx_{self._prefix}_result_{name}"
+        rc = getattr(_lib, full)(self._h, *args)
+        if check:
+            self._ctx._check(rc, full)
+        return rc
 
     def wait(self):
-        self._ctx._check(_lib.kmx_kquery_result_wait(self._h), "kmx_kquery_result_wait")
+        self._call("wait", check=True)
 
     def n_seqs(self):
-        return _lib.kmx_kquery_result_n_seqs(self._h)
+        return self._call("n_seqs")
 
     def hits_dev(self):
-        return _lib.kmx_kquery_result_hits_dev(self._h)
-
-    def sums_dev(self):
-        return _lib.kmx_kquery_result_sums_dev(self._h)
+        return self._call("hits_dev")
 
     def kernel_ms(self):
-        return _lib.kmx_kquery_result_kernel_ms(self._h)
+        return self._call("kernel_ms")
 
     def algo_bytes(self):
-        return _lib.kmx_kquery_result_algo_bytes(self._h)
+        return self._call("algo_bytes")
 
-    def output(self):
+    def _copy(self, name, array):
+        """the result's table `name` into array (kmx_..._result_copy_<name>) -> array"""
+        self._call("copy_" + name, array.ctypes.data, array.size, check=True)
+        return array
+
+    def _tables(self, sums=False):
+        """-> n_kmers uint32[queries], hits uint32[queries, n_cols], sums uint64[queries, n_cols] or None: numpy copies"""
         self.wait()
         q = self.n_seqs()
-        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
-        self._ctx._check(_lib.kmx_kquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_kquery_result_copy_kmers")
-        self._ctx._check(_lib.kmx_kquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_kquery_result_copy_hits")
-        sums = None
-        if self._sums:
-            sums = np.zeros((q, self._n), np.uint64)
-            self._ctx._check(_lib.kmx_kquery_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_kquery_result_copy_sums")
-        return KqueryOutput(nk, hits, sums, self.kernel_ms(), self.algo_bytes())
+        return (self._copy("kmers", np.zeros(q, np.uint32)), self._copy("hits", np.zeros((q, self._n), np.uint32)),
+                self._copy("sums", np.zeros((q, self._n), np.uint64)) if sums else None)
 
     def free(self):
         if self._h:
-            _lib.kmx_kquery_result_free(self._h)
+            self._call("free")
             self._h = None
 
     def __del__(self):
@@ -1379,6 +1336,21 @@ class KqueryResult:
             self.free()
         except Exception:
             pass
+
+
+class KqueryResult(_SeqResult):
+    _prefix = "kquery"
+
+    def __init__(self, ctx, h, n_cols, has_sums):
+        super().__init__(ctx, h, n_cols)
+        self._sums = has_sums
+
+    def sums_dev(self):
+        return self._call("sums_dev")
+
+    def output(self):
+        nk, hits, sums = self._tables(self._sums)
+        return KqueryOutput(nk, hits, sums, self.kernel_ms(), self.algo_bytes())
 
 
 class CqueryOutput:
@@ -1390,131 +1362,36 @@ class CqueryOutput:
         self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
 
 
-class CqueryResult:
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_cquery_result_wait(self._h), "kmx_cquery_result_wait")
-
-    def n_seqs(self):
-        return _lib.kmx_cquery_result_n_seqs(self._h)
-
-    def hits_dev(self):
-        return _lib.kmx_cquery_result_hits_dev(self._h)
+class CqueryResult(_SeqResult):
+    _prefix = "cquery"
 
     def sums_dev(self):
-        return _lib.kmx_cquery_result_sums_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_cquery_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_cquery_result_algo_bytes(self._h)
+        return self._call("sums_dev")
 
     def output(self):
-        self.wait()
-        q = self.n_seqs()
-        nk, hits, sums = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32), np.zeros((q, self._n), np.uint64)
-        self._ctx._check(_lib.kmx_cquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_cquery_result_copy_kmers")
-        self._ctx._check(_lib.kmx_cquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_cquery_result_copy_hits")
-        self._ctx._check(_lib.kmx_cquery_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_cquery_result_copy_sums")
+        nk, hits, sums = self._tables(True)
         return CqueryOutput(nk, hits, sums, self.kernel_ms(), self.algo_bytes())
 
-    def free(self):
-        if self._h:
-            _lib.kmx_cquery_result_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class ZqueryResult:
+class ZqueryResult(_SeqResult):
     """a call of a zquery series: bits_dev() the series' table; hits_dev() and output() on the last call only"""
-
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_zquery_result_wait(self._h), "kmx_zquery_result_wait")
-
-    def n_seqs(self):
-        return _lib.kmx_zquery_result_n_seqs(self._h)
-
-    def hits_dev(self):
-        return _lib.kmx_zquery_result_hits_dev(self._h)
+    _prefix = "zquery"
 
     def bits_dev(self):
-        return _lib.kmx_zquery_result_bits_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_zquery_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_zquery_result_algo_bytes(self._h)
+        return self._call("bits_dev")
 
     def output(self):
         """-> QueryOutput: n_kmers the K-positions of every query, hits those whose z + 1 rows all have the sample's bit"""
-        self.wait()
-        q = self.n_seqs()
-        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
-        self._ctx._check(_lib.kmx_zquery_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_zquery_result_copy_kmers")
-        self._ctx._check(_lib.kmx_zquery_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_zquery_result_copy_hits")
+        nk, hits, _ = self._tables()
         return QueryOutput(nk, hits, self.kernel_ms(), self.algo_bytes())
 
-    def free(self):
-        if self._h:
-            _lib.kmx_zquery_result_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class QueryResult:
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_query_result_wait(self._h), "kmx_query_result_wait")
-
-    def n_seqs(self):
-        return _lib.kmx_query_result_n_seqs(self._h)
-
-    def hits_dev(self):
-        return _lib.kmx_query_result_hits_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_query_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_query_result_algo_bytes(self._h)
+class QueryResult(_SeqResult):
+    _prefix = "query"
 
     def output(self):
-        self.wait()
-        q = self.n_seqs()
-        nk, hits = np.zeros(q, np.uint32), np.zeros((q, self._n), np.uint32)
-        self._ctx._check(_lib.kmx_query_result_copy_kmers(self._h, nk.ctypes.data, q), "kmx_query_result_copy_kmers")
-        self._ctx._check(_lib.kmx_query_result_copy_hits(self._h, hits.ctypes.data, hits.size), "kmx_query_result_copy_hits")
+        nk, hits, _ = self._tables()
         return QueryOutput(nk, hits, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_query_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 class FilterOutput:
