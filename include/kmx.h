@@ -34,6 +34,8 @@
  *                               rows that hold both samples, sums of the smaller count -- which the Jaccard and Bray-Curtis distances follow from
  *   kmx_colsums_dev / _host,    no counterpart either (kmdiff's question): the per-sample totals of a run's matrices, and the rows whose
  *   kmx_diff_dev / _host        counts differ between case and control samples by a Poisson likelihood-ratio test, kept in file order
+ *   kmx_select_dev / _host      no counterpart either (MUSET's `kmat_tools filter`): a smaller matrix out of a larger one -- a list of
+ *                               columns in any order, the rows whose recurrence over them lies in a range, counts or presence/absence
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -767,6 +769,88 @@ double    kmx_diff_result_kernel_ms(kmx_diff_result* r);
 /* algorithmic bytes: the body read once + the kept rows written + 40 bytes per kept row */
 uint64_t  kmx_diff_result_algo_bytes(kmx_diff_result* r);
 void      kmx_diff_result_free(kmx_diff_result* r);
+
+/* ----------------------------------------------------------------- select */
+
+/* A smaller matrix out of a larger one (what MUSET's `kmat_tools filter` does on the text of a kmtricks matrix; no counterpart in the
+ * kmtricks tree): some of the columns, in any order, and the rows whose recurrence over those columns lies in a range -- as counts or as
+ * presence/absence bits.
+ * INPUT: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ * `rows` needs no alignment.  The padding bits of an input PA row never reach a result.  Keys are never read, only moved.
+ * PARAMETERS:
+ *   cols       a HOST array of M = n_out distinct input column indices, each < N, in any order: output column j is input column
+ *              cols[j].  NULL is the identity and requires M = N.
+ *   min_abund  a >= 1 (exactly 1 for PA input): a sample holds a row from this count upwards
+ *   min_rec, max_rec
+ *   out_mode   KMX_MODE_COUNT (only from COUNT) or KMX_MODE_PA
+ *   flags      KMX_SELECT_ZERO_BELOW (COUNT output only)
+ * PER ROW:
+ *   present_j = (count[cols[j]] >= a) for COUNT, the bit of column cols[j] for PA
+ *   rec       = the sum of present_j over j < M: the selected columns only
+ * A row is KEPT iff min_rec <= rec <= max_rec.  min_rec > max_rec is valid and keeps nothing; max_rec >= M means no upper bound.
+ * OUTPUT ROW: the key unchanged, then
+ *   COUNT -> COUNT  M u32, v_j = count[cols[j]]; with KMX_SELECT_ZERO_BELOW v_j = 0 where v_j < a
+ *   -> PA           ceil(M / 8) bytes, bit j & 7 of byte j >> 3 = present_j; the padding bits of the last byte are 0
+ * OUTPUTS: the kept rows in the input's order (a valid body of the new row size); one kmx_select_rec per kept row in the same order; the
+ * count of kept rows.
+ * EXAMPLES.  N = 5, a row of counts (0, 3, 10, 1, 7), cols = (4, 2, 1):
+ *   a = 3: present = (1, 1, 1), rec = 3, output counts (7, 10, 3)
+ *   a = 5: present = (1, 1, 0), rec = 2, output counts (7, 10, 3); with KMX_SELECT_ZERO_BELOW (7, 10, 0); as PA the byte 0x03
+ * The row (0, 0, 0, 9, 0) has rec 0: min_rec 1 drops it, min_rec 0 keeps it.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols or n_out = 0; n_out > n_cols; a column index >= N or listed twice;
+ * cols = NULL with M != N; key_words 0 or > 4; a mode or out_mode other than COUNT / PA; PA -> COUNT; min_abund 0; min_abund > 1 with PA
+ * input; KMX_SELECT_ZERO_BELOW with PA output; unknown flag bits.  KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT as the
+ * input's mode (a Bloom row's identity is its position: rows cannot be dropped); n_rows > 2^32 - 256 (the placement tiles are the
+ * filter's: 256 rows); a row of 4 GiB or more.
+ * SCRATCH from the context's pool, per call: two 4-byte words per input row (keep, recurrence), the selection table (N bytes; PA:
+ * ceil(N / 8)) and the column list (4 bytes a column) -- given back when the call has run; a 4-byte counter per 256 rows and the outputs,
+ * sized for every row kept (n_rows * output row bytes + 16, and 8 * n_rows), live until the result is freed; for _host the uploaded rows.
+ * Send a body that does not fit in runs of rows. */
+#define KMX_SELECT_ZERO_BELOW 1u
+
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_out;         /* M: samples of the result */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices (copied by the call), or NULL: the identity */
+  uint32_t        min_abund;     /* a */
+  uint32_t        min_rec;
+  uint32_t        max_rec;       /* >= M: no upper bound */
+  uint32_t        out_mode;      /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        flags;         /* KMX_SELECT_ZERO_BELOW */
+  uint32_t        reserved;      /* 0 */
+} kmx_select_task;               /* 64 bytes */
+
+typedef struct {
+  uint32_t row;          /* index in the input */
+  uint32_t rec;
+} kmx_select_rec;        /* 8 bytes */
+
+typedef struct kmx_select_result kmx_select_result;
+
+/* _dev and _host as for kmx_diff_*: rows a DEVICE pointer (a merge result's, a filter's, a combine's, a diff's or another select's body,
+ * the caller's own memory), the kernels queued on the context's stream and the call back without waiting; or a HOST pointer, uploaded on
+ * a stream of its own, the buffer free for reuse once _result_wait has returned.  cols is a host array in both. */
+int kmx_select_dev(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out);
+int kmx_select_host(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out);
+int       kmx_select_result_wait(kmx_select_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t  kmx_select_result_rows(kmx_select_result* r);                /* kept rows */
+uint64_t  kmx_select_result_row_bytes(const kmx_select_result* r);     /* of an output row */
+uint64_t  kmx_select_result_body_bytes(kmx_select_result* r);          /* rows * row_bytes */
+const void*           kmx_select_result_body_dev(kmx_select_result* r);  /* the kept rows, in HBM until the result is freed */
+int       kmx_select_result_copy_body(kmx_select_result* r, void* host_dst, uint64_t dst_bytes);
+const kmx_select_rec* kmx_select_result_recs_dev(kmx_select_result* r);
+int       kmx_select_result_copy_recs(kmx_select_result* r, kmx_select_rec* host_dst, uint64_t dst_entries);
+double    kmx_select_result_kernel_ms(kmx_select_result* r);           /* needs kmx_set_profiling(ctx, 1); < 0 if unavailable */
+/* algorithmic bytes: the body read once + the kept rows written at their new size + 8 bytes per kept row */
+uint64_t  kmx_select_result_algo_bytes(kmx_select_result* r);
+void      kmx_select_result_free(kmx_select_result* r);
 
 /* ------------------------------------------------------------------ count */
 

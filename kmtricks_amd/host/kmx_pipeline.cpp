@@ -65,7 +65,7 @@ static double since(clk::time_point t) { return std::chrono::duration<double>(cl
 
 static Opt parse_cli(int argc, char** argv)
 {
-  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx filter --in-matrix <dir> --key <fof> --output <dir> [options] | kmx dist --run <dir> [options] | kmx diff --run <dir> --groups <file> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
+  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx filter --in-matrix <dir> --key <fof> --output <dir> [options] | kmx dist --run <dir> [options] | kmx diff --run <dir> --groups <file> [options] | kmx select --run <dir> --output <dir> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
   Opt o;
   // `kmtricks merge` (src/cli.cpp:526-646): --run-dir, --partition-id, --soft-min, --recurrence-min, --share-min, --mode, --clear, --cpr,
   // -t; what the run was made with (k, partitions, Bloom size, minimizer size) is read back from its options.txt below
@@ -1332,6 +1332,7 @@ int kmx_filter_main(int argc, char** argv);     // kmx_filter.cpp: filter
 int kmx_query_main(int argc, char** argv);      // kmx_query.cpp: query
 int kmx_dist_main(int argc, char** argv);       // kmx_dist.cpp: dist
 int kmx_diff_main(int argc, char** argv);       // kmx_diff.cpp: diff
+int kmx_select_main(int argc, char** argv);     // kmx_select.cpp: select
 
 int main(int argc, char** argv)
 {
@@ -1339,6 +1340,7 @@ int main(int argc, char** argv)
   if (argc >= 2 && std::string(argv[1]) == "query") { try { return kmx_query_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "dist") { try { return kmx_dist_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "diff") { try { return kmx_diff_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "select") { try { return kmx_select_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

@@ -94,6 +94,19 @@ DIFF_REC = np.dtype([("sum_ctrl", "<u8"), ("sum_case", "<u8"), ("stat", "<f8"), 
                      ("row", "<u4"), ("over", "<u4")])
 assert DIFF_REC.itemsize == 40
 
+
+class KmxSelectTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_out", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("min_abund", C.c_uint32),
+                ("min_rec", C.c_uint32), ("max_rec", C.c_uint32), ("out_mode", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+# kmx_select_rec: 8 bytes
+SELECT_REC = np.dtype([("row", "<u4"), ("rec", "<u4")])
+assert SELECT_REC.itemsize == 8 and C.sizeof(KmxSelectTask) == 64
+SELECT_ZERO_BELOW = 1
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -348,6 +361,24 @@ DIFF_EXPORTS = ["kmx_colsums_dev", "kmx_colsums_host", "kmx_colsums_result_wait"
                 "kmx_diff_dev", "kmx_diff_host", "kmx_diff_result_wait", "kmx_diff_result_rows", "kmx_diff_result_row_bytes",
                 "kmx_diff_result_body_bytes", "kmx_diff_result_body_dev", "kmx_diff_result_copy_body", "kmx_diff_result_recs_dev",
                 "kmx_diff_result_copy_recs", "kmx_diff_result_kernel_ms", "kmx_diff_result_algo_bytes", "kmx_diff_result_free"]
+
+_lib.kmx_select_dev.argtypes = [_vp, C.POINTER(KmxSelectTask), C.POINTER(_vp)]
+_lib.kmx_select_host.argtypes = [_vp, C.POINTER(KmxSelectTask), C.POINTER(_vp)]
+_lib.kmx_select_result_wait.argtypes = [_vp]
+for _f in ("kmx_select_result_rows", "kmx_select_result_row_bytes", "kmx_select_result_body_bytes", "kmx_select_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_select_result_body_dev", "kmx_select_result_recs_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_select_result_copy_body.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_select_result_copy_recs.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_select_result_kernel_ms.restype = C.c_double
+_lib.kmx_select_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_select_result_free.argtypes = [_vp]
+SELECT_EXPORTS = ["kmx_select_dev", "kmx_select_host", "kmx_select_result_wait", "kmx_select_result_rows", "kmx_select_result_row_bytes",
+                  "kmx_select_result_body_bytes", "kmx_select_result_body_dev", "kmx_select_result_copy_body", "kmx_select_result_recs_dev",
+                  "kmx_select_result_copy_recs", "kmx_select_result_kernel_ms", "kmx_select_result_algo_bytes", "kmx_select_result_free"]
 
 
 def zquery_bits_bytes(n_bases, n_cols):
@@ -1028,6 +1059,37 @@ class Context:
         return self._finish(DiffResult(self, res), keep)
 
     @staticmethod
+    def _select_task(rows, n_rows, n_cols, key_words, mode, cols, out_mode, min_abund, min_rec, max_rec, zero_below):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_out = n_cols if c is None else len(c)
+        t = KmxSelectTask(key_words, mode, n_cols, n_out, rows, n_rows, c.ctypes.data if c is not None and len(c) else None, min_abund, min_rec,
+                          0xFFFFFFFF if max_rec is None else max_rec, mode if out_mode is None else out_mode,
+                          SELECT_ZERO_BELOW if zero_below else 0, 0)
+        return t, c
+
+    def select(self, body, n_rows, n_cols, key_words, mode, cols=None, out_mode=None, min_abund=1, min_rec=0, max_rec=None,
+               zero_below=False, keep=False):
+        """kmx_select_host: body as for colsums; cols: the input columns of the result in its order (None: all, as they stand); out_mode:
+        MODE_COUNT or MODE_PA (None: the input's); a sample holds a row from min_abund upwards; a row is kept when min_rec <= the number
+        of selected samples that hold it <= max_rec (None: no upper bound); zero_below: counts below min_abund leave as 0.
+        -> SelectOutput (numpy copies), or with keep the SelectResult itself (the kept rows and records left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, c = self._select_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, cols, out_mode, min_abund, min_rec, max_rec, zero_below)
+        res = _vp()
+        self._check(_lib.kmx_select_host(self._h, C.byref(t), C.byref(res)), "kmx_select_host")
+        r = SelectResult(self, res)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def select_dev(self, rows_dev, n_rows, n_cols, key_words, mode, cols=None, out_mode=None, min_abund=1, min_rec=0, max_rec=None,
+                   zero_below=False, keep=False):
+        """kmx_select_dev: rows_dev a device pointer to n_rows rows (cols stays a host array).  -> as select"""
+        t, c = self._select_task(rows_dev, n_rows, n_cols, key_words, mode, cols, out_mode, min_abund, min_rec, max_rec, zero_below)
+        res = _vp()
+        self._check(_lib.kmx_select_dev(self._h, C.byref(t), C.byref(res)), "kmx_select_dev")
+        return self._finish(SelectResult(self, res), keep)
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -1267,6 +1329,62 @@ class DiffResult:
     def free(self):
         if self._h:
             _lib.kmx_diff_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class SelectOutput:
+    """body: the kept rows at their new size, in the input's order (bytes); recs: one SELECT_REC (kmx_select_rec, 8 bytes) per kept row
+    in the same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+
+class SelectResult:
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_select_result_wait(self._h), "kmx_select_result_wait")
+
+    def rows(self):
+        return _lib.kmx_select_result_rows(self._h)
+
+    def row_bytes(self):
+        return _lib.kmx_select_result_row_bytes(self._h)
+
+    def body_bytes(self):
+        return _lib.kmx_select_result_body_bytes(self._h)
+
+    def body_dev(self):
+        return _lib.kmx_select_result_body_dev(self._h)
+
+    def recs_dev(self):
+        return _lib.kmx_select_result_recs_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_select_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_select_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        body = np.zeros(self.body_bytes(), np.uint8)
+        self._ctx._check(_lib.kmx_select_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_select_result_copy_body")
+        recs = np.zeros(self.rows(), SELECT_REC)
+        self._ctx._check(_lib.kmx_select_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_select_result_copy_recs")
+        return SelectOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_select_result_free(self._h)
             self._h = None
 
     def __del__(self):
