@@ -453,6 +453,7 @@ struct TaskHost {
   size_t o_skel = 0, o_nskel = 0, o_rbounds = 0;
   u8* d_ov = nullptr;           // the records that are not row keys (key, list, count), the slices' counts, and the directory of their rows
   size_t o_spdir = 0;           // ... offset of (the extension pool's cursor and) that directory in d_ov
+  size_t o_tseed = 0;           // ... and of the tiles' hash words (k_cols_seeds writes every word k_merge_cols reads: never cleared)
   size_t o_ovx = 0; u32 xcap = 0;   // ... the pool the slices' extensions come from
   u64 sparse_rows = 0;          // rows k_cols_sparse added behind the row keys' rows
   u8* d_body = nullptr;         // COUNT/PA: the body assembled in file order on the device (kmx_result_body_dev), when it is not d_out itself
@@ -597,6 +598,13 @@ static int launch_batch(kmx_merge_result* R, bool with_bounds)
     KMX_HIP(ctx, launch_range_bounds(kw, d_subs, nt, R->sub_max_n, R->sub_max_c, ps));
     KMX_HIP(ctx, CO.skel(d_subs, d_subitems, R->n_subitems, ps));
     KMX_HIP(ctx, CO.prep(d_tasks, d_subs, d_cols, nt, ps));
+    {   // the hash word of every tile's row table, once per tile (KMX_COLS_SEED_TRIES: how many words a tile may try before its task
+        // is handed back -- read per batch: the tests switch it)
+      u32 max_slots = 0;
+      for (auto& H : R->tasks) max_slots = std::max(max_slots, H.slots_cap);
+      const char* const tenv = getenv("KMX_COLS_SEED_TRIES");
+      KMX_HIP(ctx, CO.seeds(d_tasks, d_cols, nt, max_slots, tenv && atoi(tenv) > 0 ? (u32)atoi(tenv) : 0u, getenv("KMX_TRACE") != nullptr, ps));
+    }
     KMX_HIP(ctx, hipEventRecord(R->ev_pre, ps));
     // (the task's own range bounds need the upload only: on the main stream, beside the row-key kernels)
     KMX_HIP(ctx, hipStreamWaitEvent(ctx->stream, R->ev_up, 0));
@@ -1040,7 +1048,8 @@ extern "C" int kmx_merge_dev(kmx_ctx* ctx, const kmx_merge_task* tasks, uint32_t
       H.xcap = (u32)std::min<u64>(0x7FFFFF00ULL, CO.ext_entries(H.slots_cap, H.nblk));
       H.o_ovx = align_up((size_t)(CO.scratch_keys(H.slots_cap, H.nblk) * 8 + CO.scratch_counts(H.slots_cap, H.nblk) * 8), 256);
       H.o_spdir = align_up(H.o_ovx + (size_t)H.xcap * (CO.key_words + 1) * 8, 256);
-      H.d_ov = (u8*)ctx->dalloc(H.o_spdir + 256 + (size_t)CO.dir_bytes(H.slots_cap));
+      H.o_tseed = align_up(H.o_spdir + 256 + (size_t)CO.dir_bytes(H.slots_cap), 256);
+      H.d_ov = (u8*)ctx->dalloc(H.o_tseed + (size_t)H.slots_cap * 4);
       if (H.d_ov && hipMemsetAsync(H.d_ov + H.o_spdir, 0, 256 + (size_t)CO.dir_bytes(H.slots_cap), ctx->aux) != hipSuccess) { ctx->dfree(H.d_ov); H.d_ov = nullptr; }
       if (R->cols_ord) {
         // the side store of the row keys' rows (payload only, 8-byte pitch).  Row keys = the keys a merge of S of the lists keeps:
@@ -1140,6 +1149,7 @@ extern "C" int kmx_merge_dev(kmx_ctx* ctx, const kmx_merge_task* tasks, uint32_t
       C.xcap = H.xcap;
       C.spdir = H.d_ov + H.o_spdir + 256;
       C.slots_cap = H.slots_cap; C.nblk = H.nblk; C.nb = H.nb; C.rt = H.rt_cols;
+      C.tseed = reinterpret_cast<u32*>(H.d_ov + H.o_tseed);
       if (R->cols_ord) {      // (the sparse rows' directory is not written then: its room holds the look-back chain and the group map)
         const size_t ng = CO.groups(H.slots_cap);
         C.dense = H.d_dense; C.dpitch = H.dpitch; C.dense_cap = H.dense_cap;
@@ -1657,6 +1667,7 @@ extern "C" void kmx_result_free(kmx_merge_result* R)
   (void)hipSetDevice(ctx->device);
   if (R->ev_done) (void)hipEventSynchronize(R->ev_done);      // (this result's work, not the stream: later batches are queued behind it)
   else (void)hipStreamSynchronize(ctx->stream);
+  if (R->use_cols && getenv("KMX_TRACE")) cols_ops((int)R->tasks[0].kw).seeds_dump();
 #ifdef KMX_PHASE_PROF
   const ColsOps& CO = cols_ops((int)R->tasks[0].kw);
   if (R->is_bft) kmx::bft_phase_prof_dump();

@@ -74,6 +74,7 @@ struct ColsDev {
   uint4* gmap;             // [groups] (range, group in the range, the range's first and last row key) of the task's g-th slice group
   u32* gmax;               // -> max over the batch's tasks of their slice groups (k_cols_sparse's tickets end there)
   u32 ngcap;               // entries of chain / gmap
+  u32* tseed;              // [slots_cap] the hash word of every tile's row table (k_cols_seeds; 0: none found, the task is handed back)
 };
 
 // rows are claimed from a task's arena in chunks of this many bytes (one global atomic + one directory entry per chunk)

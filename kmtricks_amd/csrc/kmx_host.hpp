@@ -40,6 +40,8 @@ struct ColsOps {
   u32 (*skel_cap)();
   hipError_t (*skel)(const TaskDev* subs, const uint2* items, u32 n_items, hipStream_t st);
   hipError_t (*prep)(const TaskDev* tasks, const TaskDev* subs, const ColsDev* cols, u32 n_tasks, hipStream_t st);
+  // behind prep: the hash word of every tile's row table; max_slots = the largest slots_cap of the batch, max_tries 0 = the build's budget
+  hipError_t (*seeds)(const TaskDev* tasks, const ColsDev* cols, u32 n_tasks, u32 max_slots, u32 max_tries, bool trace, hipStream_t st);
   hipError_t (*merge)(int mode, int ext, const TaskDev* tasks, const ColsDev* cols, const uint2* items, u32 n_items, u32* ticket, u32 grid_x, hipStream_t st);
   hipError_t (*sparse)(int mode, const TaskDev* tasks, const ColsDev* cols, const uint2* range_items, u32 n_items, u32 n_tasks, u32* ticket, u32 n_cu, hipStream_t st);
   u64 (*dir_bytes)(u32 slots);
@@ -48,6 +50,7 @@ struct ColsOps {
   hipError_t (*gather)(const TaskDev* tasks, const ColsDev* cols, u32 task, u32 n_groups, const u64* goff, u8* body, hipStream_t st);
   hipError_t (*order)(const TaskDev* tasks, const ColsDev* cols, u32 task, u32 n_groups, const u64* goff, u32* order, hipStream_t st);
   void (*dbg_dump)();
+  void (*seeds_dump)();      // KMX_TRACE: the hash words k_cols_seeds tried per tile, as a histogram
   void (*phase_prof_dump)();
   u32 key_words;
 };

@@ -77,7 +77,6 @@ constexpr int CL_NT = (CL_KPL == 1 && CL_WGS == 1 && KW == 1) ? 2 : 1;  // row t
 constexpr int CL_PT = CL_KPL == 1 ? 2048 : 4096;      // row-key table entries
 constexpr int CL_PTSHIFT = CL_PT == 2048 ? 21 : 20;
 constexpr int CL_HALVES = CL_KPL;        // set-aside slices per tile: one per 56 rows (k_cols_sparse takes a slice group at a time)
-constexpr int CL_SEEDS = 256;            // hashes tried per tile for a collision-free table: 64 cheap ones, then 64-bit multiplicative ones
 constexpr int CL_OVW = 128;              // keys per (slice group, block, wave) of records that are not row keys
 constexpr int CL_XS = 3 * CL_OVW;        // ... and of the extension a wave claims when its slice is full (an outlier sample among its lists)
 constexpr int CL_NW = CL_TPB / 64;
@@ -143,8 +142,10 @@ __device__ __forceinline__ ClEnt ent_load(const ClEnt* tab, u32 h)
 #endif
 __device__ __forceinline__ bool ck_le(CKey a, CKey b) { return !ck_lt(b, a); }
 __device__ __forceinline__ void cl_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// the row keys of a tile sit in a PERFECT hash table: wave 0 tries multipliers until the (<= 56) keys land in
-// distinct entries of the 1024, so a lookup is one LDS read and one compare -- no probing, no branch
+// the row keys of a tile sit in a PERFECT hash table: a hash word under which the tile's (<= CL_RT) keys land in distinct
+// entries of the CL_PT, so a lookup is one LDS read and one compare -- no probing, no branch.  The word is found ONCE per
+// tile, by k_cols_seeds behind k_cols_prep (C.tseed[tile slot]); k_merge_cols' wave 0 only fills the table with it: plain
+// LDS stores, no search between the tile's barriers, and none repeated by each of the task's column blocks.
 // (a hash = 24-bit multiplier | shift << 24: the shift picks which key bits are folded into the 24 that get multiplied,
 //  so two keys that agree in those 24 bits under one hash do not under the next)
 // Keys of real minimizer partitions are structured (the row keys of a tile share their leading nucleotides, neighbours in
@@ -185,29 +186,40 @@ __device__ __forceinline__ u32 cl_mix(CKey key)
 }
 // (Round 5 tried four hashes at once -- a bit map of LDS per hash, a key sets its bit under each and sees whether it was set, the first
 //  hash nobody clashed under wins: k_merge_cols 2.29 -> 2.50 ms.  On real tiles the first or second cheap hash is collision free; four
-//  hashes' worth of work every time is more than the one or two tries below.)
-// wave 0: lane j holds row keys j, j + 64, ...  -> the hash, 0 when no try worked; slot[x] = entry of my key x
-__device__ __forceinline__ u32 cl_build(ClEnt* tab, const CKey (&key)[CL_KPL], const bool (&have)[CL_KPL], u32 lane, u32 (&slot)[CL_KPL])
+//  hashes' worth of work every time is more than the one or two tries of a search in turn.  Round 7 measured the turns --
+//  profiles/r07_cols_table_before.txt -- and took the search out of k_merge_cols altogether: k_cols_seeds.)
+// k_cols_seeds, a wave per tile: lane j holds row keys j, j + 64, ...; bm = the wave's CL_PT bits of LDS.  -> the first hash word
+// of the first max_tries of cl_mult's sequence under which no two keys share an entry, 0 when there is none; tries = how many were tried
+__device__ __forceinline__ u32 cl_find(u32* bm, const CKey (&key)[CL_KPL], const bool (&have)[CL_KPL], u32 lane, u32 max_tries, u32& tries)
 {
-  for (u32 s = 0; s < (u32)CL_SEEDS; s++) {
+  for (u32 s = 0; s < max_tries; s++) {
     const u32 mult = cl_mult(s);
-    u32 h[CL_KPL], old[CL_KPL];
+    for (u32 w = lane; w < (u32)CL_PT / 32u; w += 64u) bm[w] = 0;
+    __builtin_amdgcn_wave_barrier();
     bool clash = false;
 #pragma unroll
     for (int x = 0; x < CL_KPL; x++) {
-      h[x] = cl_thash(key[x], mult);
-      old[x] = have[x] ? atomicCAS(&tab[h[x]].idx, 0u, lane + 64u * x + 1) : 0u;
-      clash |= old[x] != 0;
+      const u32 h = cl_thash(key[x], mult);
+      if (have[x]) clash |= ((atomicOr(&bm[h >> 5], 1u << (h & 31u)) >> (h & 31u)) & 1u) != 0;      // (my bit was set already: somebody else's key, or my other one)
     }
-    if (__ballot(clash) == 0) {
-#pragma unroll
-      for (int x = 0; x < CL_KPL; x++) { if (have[x]) ent_set(tab[h[x]], key[x]); slot[x] = h[x]; }
-      return mult;
-    }
-#pragma unroll
-    for (int x = 0; x < CL_KPL; x++) if (have[x] && old[x] == 0) atomicExch(&tab[h[x]].idx, 0u);      // take my claims back, next hash
+    __builtin_amdgcn_wave_barrier();
+    if (__ballot(clash) == 0) { tries = s + 1; return mult; }
   }
+  tries = max_tries;
   return 0;
+}
+// k_merge_cols, wave 0: my row keys into the table under the tile's hash word (collision free: k_cols_seeds found it so).  An
+// entry is never cleared between the tiles of a work item: an entry an earlier tile left can only be met by a record with
+// that tile's key, and the lists ascend strictly -- every record below a tile's upper key was consumed in that tile.
+__device__ __forceinline__ void cl_fill(ClEnt* tab, const CKey (&key)[CL_KPL], const bool (&have)[CL_KPL], u32 lane, u32 mult)
+{
+#pragma unroll
+  for (int x = 0; x < CL_KPL; x++) {
+    if (have[x]) {
+      ClEnt e; memset(&e, 0, sizeof(e)); ent_set(e, key[x]); e.idx = lane + 64u * x + 1;
+      tab[cl_thash(key[x], mult)] = e;
+    }
+  }
 }
 
 }  // namespace
@@ -408,7 +420,58 @@ void k_cols_prep(const TaskDev* __restrict__ tasks, const TaskDev* __restrict__ 
   }
 }
 
-__device__ const u32 kmx_cols_sentinel[8] = {~0u, ~0u, KW == 1 ? 0u : ~0u, KW == 1 ? 0u : ~0u, 0u, 0u, 0u, 0u};      // the record "past the end of a list": largest key, count 0
+// ---- row keys: the hash word of every tile's row table.  A wave per tile slot (slot = rbounds[range] / rt + range + tile, as the
+//      set-aside slices number them): the tile's row keys from C.skel, cl_mult's hash words in turn until one puts no two keys
+//      into the same entry of a CL_PT-entry table -- a bit map of the wave's own in LDS tells -- and that word into C.tseed[slot].
+//      Once per tile, off k_merge_cols' critical path (where every column block of the tile repeated the search between two
+//      barriers), so the budget is CS_TRIES words, not 256.  A tile that finds none hands its task back before the merge starts. ----
+constexpr int CS_TPB = 256;
+constexpr u32 CS_TRIES = 1024;           // hash words tried per tile (KMX_COLS_SEED_TRIES: fewer, for the tests of the hand-back)
+__device__ u32 kmx_cols_tries[12];       // KMX_TRACE=1: tiles by the number of words tried ([0..8]: 1, 2, 3-4, 5-8, ... 65-128, more), [9] tiles with no row key, [10] the largest number, [11] tiles with none found
+__global__ __launch_bounds__(CS_TPB)
+void k_cols_seeds(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__ cols, u32 max_tries, u32 trace)
+{
+  __shared__ u32 bm[CS_TPB / 64][CL_PT / 32];
+  __shared__ u32 s_fail;
+  const TaskDev& T = tasks[blockIdx.y];
+  const ColsDev& C = cols[blockIdx.y];
+  const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (tid == 0) s_fail = 0;
+  // (one decision per workgroup: the other workgroups of this launch raise the word while this one reads it -- see k_merge_cols)
+  if (__syncthreads_or((__hip_atomic_load(&T.ctrl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (u64)(ERR_FALLBACK | ERR_ROWS_OVERFLOW)) != 0)) return;
+  const u32 slot = blockIdx.x * (u32)(CS_TPB / 64) + wave, c = T.c, rt = C.rt;
+  if (slot < C.slots_cap && slot <= C.rbounds[c] / rt + c) {      // (the tile count is the device's to know: the launch covers every task's room, surplus waves leave here)
+    u32 lo = 0, hi = c;      // the last range whose first slot is <= mine (first slots ascend strictly)
+    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (C.rbounds[mid] / rt + mid <= slot) lo = mid; else hi = mid; }
+    const u32 s_lo = C.rbounds[lo], s_hi = C.rbounds[lo + 1];
+    const u32 q = slot - (s_lo / rt + lo), ntiles = max(1u, (s_hi - s_lo + rt - 1) / rt);
+    if (q < ntiles) {
+      const u32 s0 = s_lo + q * rt;
+      CKey key[CL_KPL]; bool have[CL_KPL];
+#pragma unroll
+      for (int x = 0; x < CL_KPL; x++) {
+        const u32 j = lane + 64u * x;
+        have[x] = j < rt && s0 + j < s_hi;
+        key[x] = have[x] ? reinterpret_cast<const CKey*>(C.skel)[s0 + j] : ck_inf();
+      }
+      u32 tries = 0;
+      const u32 mult = cl_find(bm[wave], key, have, lane, max_tries, tries);
+      if (lane == 0) {
+        C.tseed[slot] = mult;
+        if (mult == 0) { s_fail = 1; atomicAdd(&kmx_cols_dbg[0], 1u); }
+        if (trace) {
+          u32 b = 0; while (b < 8u && (1u << b) < tries) b++;
+          atomicAdd(&kmx_cols_tries[mult == 0 ? 11u : s0 >= s_hi ? 9u : b], 1u);
+          atomicMax(&kmx_cols_tries[10], tries);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0 && s_fail) atomicOr(&T.ctrl[2], (u64)ERR_FALLBACK);      // (once per workgroup; k_merge_cols and k_cols_sparse skip the task)
+}
+
+__device__ const u32 kmx_cols_sentinel[8] ={~0u, ~0u, KW == 1 ? 0u : ~0u, KW == 1 ? 0u : ~0u, 0u, 0u, 0u, 0u};      // the record "past the end of a list": largest key, count 0
 
 #ifdef KMX_PHASE_PROF
 __device__ u64 kmx_cols_prof[8];
@@ -445,7 +508,7 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32* const img = reinterpret_cast<u32*>(smem);                                   // [rt][nb] counts of the tile
   ClEnt* const ptab = reinterpret_cast<ClEnt*>(smem + CL_IMG);                     // [CL_NT][CL_PT] row key -> row
-  u32* const sh = reinterpret_cast<u32*>(smem + CL_IMG + CL_NT * CL_PT * sizeof(ClEnt)); // [0] item [1..3] "another round" flags, used in turn [4],[5] the tables' multipliers
+  u32* const sh = reinterpret_cast<u32*>(smem + CL_IMG + CL_NT * CL_PT * sizeof(ClEnt)); // [0] item [1..3] "another round" flags, used in turn [4] wave 0's own: the next tile's hash word [5] this tile's
   const u32 dummy = (u32)(CL_IMG + CL_NT * CL_PT * sizeof(ClEnt)) / 4 + 16 + (u32)(threadIdx.x & 63);   // image index of a scratch word of my own (deposits that are none)
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -522,11 +585,12 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
     u64 rsum = 0; u32 rn = 0;            // RESC: the rescued records of the row keys' rows (their counts, their number)
     const bool rescue = RESC && cl_uni(T.share_min) != 0;      // (a RESC build with share-min 0: recurrence-min 0 -- nothing is rescued, everything is set aside)
     // first tile: row keys, table, (block 0) the key column of the result
+    // (the tables are empty here: cleared when the kernel starts and behind every work item -- another task may hold the same keys)
+    // (the tiles' hash words: k_cols_seeds' C.tseed; a task with a tile that has none never gets here)
     CKey skn[CL_KPL];
-    u32 myslot[CL_KPL];                  // wave 0: the table entries of my row keys of the tile in hand
     bool failed = false;
 #pragma unroll
-    for (int x = 0; x < CL_KPL; x++) { skn[x] = ck_inf(); myslot[x] = 0; }
+    for (int x = 0; x < CL_KPL; x++) skn[x] = ck_inf();
     if (tid < 64) {
       bool have[CL_KPL];
 #pragma unroll
@@ -538,8 +602,9 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
           if (blk == 0 && !ord) ck_store(reinterpret_cast<u32*>(T.out + (u64)(s_lo + j) * row_bytes), skn[x]);
         }
       }
-      const u32 mult = cl_build(ptab, skn, have, (u32)tid, myslot);
-      if (tid == 0) { sh[4] = mult; if (mult == 0) { failed = true; atomicAdd(&kmx_cols_dbg[0], 1u); } }
+      const u32 m0 = cl_uni(C.tseed[slot0]);
+      cl_fill(ptab, skn, have, (u32)tid, m0);
+      if (tid == 0) sh[5] = m0;      // (the hash word of the tile in hand, for everybody: read at the tile's start, replaced behind the walk's barrier)
     }
     CKey khi_n = ntiles > 1 ? skel[s_lo + rt] : ck_inf();     // upper key of tile 0 (uniform address: scalar load)
     CKey kmid_n = (CL_HALVES > 1 && s_lo + 56 < s_hi) ? skel[s_lo + 56] : ck_inf();      // ... and the key its second slice group starts at
@@ -553,8 +618,11 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
       const bool last = cl_uni(q + 1 == ntiles ? 1u : 0u) != 0;            // takes everything the lists have left in the range
       const CKey khi = ck_uni(khi_n);
       const CKey kmid = ck_uni(kmid_n);
+      const u32 mult = cl_uni(sh[5]);      // this tile's hash word
       if (!last) {
-        // the next tile's row keys are wave 0's business alone: nobody else ever waits for these loads
+        // the next tile's row keys and hash word are wave 0's business alone: nobody else ever waits for these loads
+        // (the word waits in LDS for the tile's way out -- sh[4], wave 0's own: no register is held across the walk for it)
+        if (tid == 0) sh[4] = C.tseed[slot0 + q + 1];
         if (tid < 64) {
 #pragma unroll
           for (int x = 0; x < CL_KPL; x++) { const u32 j = (u32)tid + 64u * x; skn[x] = ck_inf(); if (j < rt && s0 + rt + j < s_hi) skn[x] = skel[s0 + rt + j]; }
@@ -563,7 +631,6 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
         kmid_n = (CL_HALVES > 1 && s0 + rt + 56 < s_hi) ? skel[s0 + rt + 56] : ck_inf();
       }
       const ClEnt* const tab = ptab + (q % CL_NT) * CL_PT;
-      const u32 mult = cl_uni(sh[4 + (q % CL_NT)]);
       // the wave's slices of the tile's slice groups (records below / from the tile's middle row key)
       // (an entry = the key and (list << 32 | count): k_cols_sparse builds the rows of the keys that reach the recurrence from them)
       gu64w* const ovk0 = (gu64w*)(uintptr_t)(C.ovkeys + (((((u64)(slot0 + q) * CL_HALVES) * nblk + blk) * CL_NW + wave) * CL_OVW) * EW);
@@ -716,11 +783,8 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
           if (lane == 0) atomicOr(&T.ctrl[2], (u64)ERR_SLICES); failed = true; atomicAdd(&kmx_cols_dbg[1], 1u); atomicMax(&kmx_cols_dbg[5], max(wov, wov1)); if (last) atomicAdd(&kmx_cols_dbg[6], 1u); if (q == 0) atomicAdd(&kmx_cols_dbg[7], 1u); }
       }
 
-      // ---- tile out: wave 0 turns the row table over, the others stream the image out (and leave it zeroed) ----
+      // ---- tile out: wave 0 puts the next tile's row keys into the row table, the others stream the image out (and leave it zeroed) ----
       if (wave == 0) {
-        ClEnt* const old = ptab + (q % CL_NT) * CL_PT;
-#pragma unroll
-        for (int x = 0; x < CL_KPL; x++) if ((u32)lane + 64u * x < rte) old[myslot[x]].idx = 0;        // (keys may stay: an entry without a row is never a hit)
         if (!last) {
           const u32 sn = s0 + rt;
           bool have[CL_KPL];
@@ -730,8 +794,9 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
             have[x] = j < rt && sn + j < s_hi;
             if (have[x] && blk == 0 && !ord) ck_store(reinterpret_cast<u32*>(T.out + (u64)(sn + j) * row_bytes), skn[x]);
           }
-          const u32 m2 = cl_build(ptab + ((q + 1) % CL_NT) * CL_PT, skn, have, (u32)lane, myslot);
-          if (lane == 0) { sh[4 + ((q + 1) % CL_NT)] = m2; if (m2 == 0) { failed = true; atomicAdd(&kmx_cols_dbg[0], 1u); } }
+          const u32 m2 = cl_uni(sh[4]);
+          cl_fill(ptab + ((q + 1) % CL_NT) * CL_PT, skn, have, (u32)lane, m2);
+          if (lane == 0) sh[5] = m2;
         }
       } else {
         if (NAR) {
@@ -823,6 +888,9 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
       }
     }
     if (failed) atomicOr(&T.ctrl[2], (u64)ERR_FALLBACK);
+    // (the work item's entries go, all of them at once: behind the last tile's barrier nobody reads the tables any more)
+    int t0 = tid; asm volatile("" : "+v"(t0));      // (addresses worked out here: shared with the clearing at the kernel's start they sat in spilled registers across every item)
+    for (int t = t0; t < CL_NT * CL_PT; t += CL_TPB) ptab[t].idx = 0;
     __syncthreads();
   }
 }
@@ -1852,6 +1920,17 @@ void cols_dbg_dump()
   fprintf(stderr, "[kmx merge] k_merge_cols hand-back reasons: no collision-free row table %u, slice overflow %u (wave-tiles; largest %u, in a range's last tile %u, first tile %u), kept key outside the row keys %u, check table full %u, lists too divergent %u (tasks)\n", h[0], h[1], h[5], h[6], h[7], h[2], h[3], h[4]);
   memset(h, 0, sizeof(h)); (void)hipMemcpyToSymbol(HIP_SYMBOL(kmx_cols_dbg), h, sizeof(h));
 }
+// KMX_TRACE=1, when a result of the pair is freed: how many hash words k_cols_seeds tried per tile (counted only under KMX_TRACE)
+void cols_seeds_dump()
+{
+  u32 h[12];
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(kmx_cols_tries), sizeof(h)) != hipSuccess) return;
+  u64 n = 0; for (int i = 0; i < 10; i++) n += h[i];
+  if (n + h[11] == 0) return;
+  fprintf(stderr, "[kmx merge] k_cols_seeds: hash words tried per tile: 1: %u, 2: %u, 3-4: %u, 5-8: %u, 9-16: %u, 17-32: %u, 33-64: %u, 65-128: %u, more: %u; tiles without row keys %u, most tries %u, none found %u\n",
+          h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11]);
+  memset(h, 0, sizeof(h)); (void)hipMemcpyToSymbol(HIP_SYMBOL(kmx_cols_tries), h, sizeof(h));
+}
 #ifdef KMX_PHASE_PROF
 void cols_phase_prof_dump()
 {
@@ -1891,6 +1970,12 @@ hipError_t launch_cols_skel(const TaskDev* subs, const uint2* items, u32 n_items
 hipError_t launch_cols_prep(const TaskDev* tasks, const TaskDev* subs, const ColsDev* cols, u32 n_tasks, hipStream_t st)
 {
   hipLaunchKernelGGL(k_cols_prep, dim3(n_tasks), dim3(CP_TPB), 0, st, tasks, subs, cols);
+  return hipGetLastError();
+}
+hipError_t launch_cols_seeds(const TaskDev* tasks, const ColsDev* cols, u32 n_tasks, u32 max_slots, u32 max_tries, bool trace, hipStream_t st)
+{
+  const u32 per = (u32)(CS_TPB / 64);
+  hipLaunchKernelGGL(k_cols_seeds, dim3((max_slots + per - 1) / per, n_tasks), dim3(CS_TPB), 0, st, tasks, cols, max_tries ? max_tries : CS_TRIES, trace ? 1u : 0u);
   return hipGetLastError();
 }
 template <int MODE, bool EXT, bool RESC, bool ORD, bool NAR>
@@ -1967,8 +2052,8 @@ hipError_t launch_cols_order(const TaskDev* tasks, const ColsDev* cols, u32 task
 }
 
 static const ColsOps g_ops = {cols_lds_bytes, cols_block_lists, cols_wgs_per_cu, cols_tile_rows, cols_scratch_keys, cols_scratch_counts, cols_ext_entries, cols_skel_cap,
-                              launch_cols_skel, launch_cols_prep, launch_merge_cols, launch_cols_sparse, cols_dir_bytes, cols_groups, launch_cols_offsets,
-                              launch_cols_gather, launch_cols_order, cols_dbg_dump,
+                              launch_cols_skel, launch_cols_prep, launch_cols_seeds, launch_merge_cols, launch_cols_sparse, cols_dir_bytes, cols_groups, launch_cols_offsets,
+                              launch_cols_gather, launch_cols_order, cols_dbg_dump, cols_seeds_dump,
 #ifdef KMX_PHASE_PROF
                               cols_phase_prof_dump,
 #else
