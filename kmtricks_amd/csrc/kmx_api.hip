@@ -1237,6 +1237,16 @@ extern "C" int kmx_result_wait(kmx_merge_result* R)
     }
     for (auto& H : R->tasks) H.rows = R->is_bft ? H.t_cols : H.upper - H.lower + 1;
     R->waited = true; R->status = KMX_OK;
+    if (getenv("KMX_TRACE")) {    // (the shape each Bloom task ran at: the tile and range policy cannot be seen from outside otherwise; hash:bft: ranges = work items)
+      // hash:bft: how the launch that produced the result met the rows' recurrences (the whole batch alike, launch_batch)
+      bool any_rec = false; for (auto& H : R->tasks) any_rec = any_rec || H.rec_min > 1 || H.share_min > 0;
+      const char* walk = !R->is_bft ? "" : R->d_rem && !R->bft_two_walks ? ", single walk" : any_rec ? ", two walks" : ", no recurrences";
+      for (size_t t = 0; t < R->tasks.size(); t++) {
+        const TaskHost& H = R->tasks[t];
+        fprintf(stderr, "[kmx merge] bloom task %zu: %u lists, %u bytes a row, %u rows a tile, %llu tiles, %u ranges%s\n", t, H.N, H.row_bytes, H.rt,
+                (unsigned long long)((H.upper - H.lower + H.rt) / H.rt), H.c, walk);
+      }
+    }
     return KMX_OK;
   }
   const ColsOps& CO = cols_ops((int)R->tasks[0].kw);
