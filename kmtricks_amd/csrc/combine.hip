@@ -331,7 +331,7 @@ void k_combine_move(const CombineBlock* __restrict__ blocks, u32 nb, u32 kb, u32
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-static u32 cb_grid(u64 items) { return (u32)std::min<u64>(std::max<u64>(items, 1), CB_MAX_GRID); }
+static u32 cb_grid(u64 items) { return (u32)std::min<u64>(std::max<u64>(items, 1), kmx_grid_cap(CB_MAX_GRID)); }
 
 u32 combine_tiles(u32 n) { return (n + CB_TILE - 1) / CB_TILE; }
 

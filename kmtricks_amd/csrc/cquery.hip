@@ -181,7 +181,7 @@ static int cquery_queue(kmx_ctx* ctx, const kmx_cquery_task* K, kmx_cquery_resul
     KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
     KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
     KMX_HIP(ctx, launch_query_scatter(d_keys, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
-    KMX_HIP(ctx, launch_cquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, nb, K->bitw, N, K->min_class, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
+    KMX_HIP(ctx, launch_cquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, nb, K->bitw, N, K->min_class, R->d_hits, R->d_sums, (u32)kmx_plan_cus(ctx), st));
   }
   return seq_queue_tail(R, d_pstart + P, 1);      // h_tot[0]: the valid k-mers of the call
 }

@@ -237,7 +237,7 @@ static int colsums_queue(kmx_ctx* ctx, const kmx_colsums_task* T, kmx_colsums_re
   if (R->d_sums_own) KMX_HIP(ctx, hipMemsetAsync(R->d_sums_own, 0, 8ull * N, st));
   if (T->n_rows) {
     const u32 units = count ? N : (N + 7) / 8, LU = pow2_at_or_above(units, 256), ub = (units + LU - 1) / LU;
-    u64 tiles = std::max<u64>(1, (u64)std::max(ctx->n_cu, 1) * CS_WGS_PER_CU / ub);
+    u64 tiles = std::max<u64>(1, (u64)std::max(kmx_plan_cus(ctx), 1) * CS_WGS_PER_CU / ub);
     tiles = std::min<u64>(std::min<u64>(tiles, (T->n_rows + 63) / 64), 65535);
     const u64 tile_rows = (T->n_rows + tiles - 1) / tiles;
     tiles = (T->n_rows + tile_rows - 1) / tile_rows;
@@ -398,9 +398,9 @@ static int diff_queue(kmx_ctx* ctx, const kmx_diff_task* T, kmx_diff_result* R)
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has DF_WAVES_PER_SIMD waves a SIMD to hide the loads
     const u32 L = pow2_at_or_above(units, 64);
     u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(ctx->n_cu, 1) * 4 * DF_WAVES_PER_SIMD) RW >>= 1;
+    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(kmx_plan_cus(ctx), 1) * 4 * DF_WAVES_PER_SIMD) RW >>= 1;
     const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, DF_MAX_GRID);
+    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, kmx_grid_cap(DF_MAX_GRID));
     if (count) hipLaunchKernelGGL(k_diff_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, L, RW, (const u8*)R->d_grp,
                                   (u64)T->total_ctrl, (u64)T->total_case, T->threshold, T->min_rec, R->d_keep, R->d_recs_all, R->d_tiles);
     else hipLaunchKernelGGL(k_diff_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, L, RW, (const u8*)R->d_grp,
@@ -410,7 +410,7 @@ static int diff_queue(kmx_ctx* ctx, const kmx_diff_task* T, kmx_diff_result* R)
   KMX_HIP(ctx, launch_filter_scan(R->d_tiles, tiles, st));
   if (n_rows) {
     KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, R->d_keep, R->d_keep, R->d_tiles, R->d_out, st));
-    hipLaunchKernelGGL(k_diff_place, dim3(std::min(tiles, DF_MAX_GRID)), dim3(DF_TILE), 0, st, (const u32*)R->d_keep, (const DiffRec*)R->d_recs_all, n_rows,
+    hipLaunchKernelGGL(k_diff_place, dim3(std::min(tiles, kmx_grid_cap(DF_MAX_GRID))), dim3(DF_TILE), 0, st, (const u32*)R->d_keep, (const DiffRec*)R->d_recs_all, n_rows,
                        (const u32*)R->d_tiles, R->d_recs);
     KMX_HIP(ctx, hipGetLastError());
   }

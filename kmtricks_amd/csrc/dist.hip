@@ -251,7 +251,7 @@ static void dist_release(kmx_dist_result* R)
 static int dist_queue(kmx_ctx* ctx, const kmx_dist_task* T, kmx_dist_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, NB = (N + 63) / 64, skip = 8 * T->key_words, n_cu = (u32)std::max(ctx->n_cu, 1);
+  const u32 N = T->n_cols, NB = (N + 63) / 64, skip = 8 * T->key_words, n_cu = (u32)std::max(kmx_plan_cus(ctx), 1);
   const u64 n_rows = T->n_rows, W = (n_rows + 63) / 64, table = (u64)N * N, pairs = (u64)NB * (NB + 1) / 2;
   const bool count = T->mode == KMX_MODE_COUNT;
   u32 p_runs = 1, m_runs = 1; u64 p_len = DP_CH, m_len = DM_TR;
@@ -278,7 +278,7 @@ static int dist_queue(kmx_ctx* ctx, const kmx_dist_task* T, kmx_dist_result* R)
     const u8* rows = (const u8*)T->rows;
     const u32 ct_n = count ? NB : (NB + 7) / 8;
     const u64 n_tiles = W * ct_n;
-    const u32 grid = (u32)std::min<u64>((n_tiles + 3) / 4, 1u << 20);
+    const u32 grid = (u32)std::min<u64>((n_tiles + 3) / 4, kmx_grid_cap(1u << 20));
     if (count) hipLaunchKernelGGL(k_dist_slab<true>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, R->d_slab);
     else hipLaunchKernelGGL(k_dist_slab<false>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, R->d_slab);
     KMX_HIP(ctx, hipGetLastError());

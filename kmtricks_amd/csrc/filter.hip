@@ -232,7 +232,7 @@ void k_filter_absent_scatter(const u8* __restrict__ key, const u8* __restrict__ 
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-static u32 ft_grid(u64 items) { return (u32)std::min<u64>(std::max<u64>(items, 1), FT_MAX_GRID); }
+static u32 ft_grid(u64 items) { return (u32)std::min<u64>(std::max<u64>(items, 1), kmx_grid_cap(FT_MAX_GRID)); }
 
 u32 filter_tiles(u32 n) { return (n + FT_TILE - 1) / FT_TILE; }
 

@@ -318,11 +318,11 @@ static int kquery_queue(kmx_ctx* ctx, const kmx_kquery_task* K, kmx_kquery_resul
     KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
     KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
     KMX_HIP(ctx, launch_kquery_scatter(d_parts, (const u64*)K->offsets, n_seqs, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
-    KMX_HIP(ctx, launch_kquery_search((int)kw, d_recs, n_bases, d_pstart, P, R->d_rows, d_nrows, stride, d_words, n_bases, d_found, (u32)ctx->n_cu, st));
+    KMX_HIP(ctx, launch_kquery_search((int)kw, d_recs, n_bases, d_pstart, P, R->d_rows, d_nrows, stride, d_words, n_bases, d_found, (u32)kmx_plan_cus(ctx), st));
     if (K->mode == KMX_MODE_PA)
-      KMX_HIP(ctx, launch_query_gather_keyed(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, (N + 7) / 8, N, R->d_hits, (u32)ctx->n_cu, st));
+      KMX_HIP(ctx, launch_query_gather_keyed(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, (N + 7) / 8, N, R->d_hits, (u32)kmx_plan_cus(ctx), st));
     else
-      KMX_HIP(ctx, launch_kquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, N, R->d_hits, R->d_sums, (u32)ctx->n_cu, st));
+      KMX_HIP(ctx, launch_kquery_gather(d_recs, n_bases, d_pstart, P, R->d_rows, stride, skip, N, R->d_hits, R->d_sums, (u32)kmx_plan_cus(ctx), st));
   }
   return seq_queue_tail(R, d_pstart + P, 1, d_found);
 }

@@ -311,9 +311,9 @@ static int select_queue(kmx_ctx* ctx, const kmx_select_task* T, kmx_select_resul
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has SL_WAVES_PER_SIMD waves a SIMD to hide the loads
     const u32 L = sl_pow2_at_or_above(units, 64);
     u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(ctx->n_cu, 1) * 4 * SL_WAVES_PER_SIMD) RW >>= 1;
+    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(kmx_plan_cus(ctx), 1) * 4 * SL_WAVES_PER_SIMD) RW >>= 1;
     const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, SL_MAX_GRID);
+    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, kmx_grid_cap(SL_MAX_GRID));
     if (count) hipLaunchKernelGGL(k_select_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->irb, skip, N, L, RW, (const u8*)R->d_sel,
                                   T->min_abund, T->min_rec, max_rec, R->d_keep, R->d_recv, R->d_tiles);
     else hipLaunchKernelGGL(k_select_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->irb, skip, N, L, RW, (const u8*)R->d_sel,
@@ -327,7 +327,7 @@ static int select_queue(kmx_ctx* ctx, const kmx_select_task* T, kmx_select_resul
       // gathered loads of a tile with every row kept: the key's units, then one a count (-> COUNT) or eight a payload byte (-> PA)
       const u64 loads = (u64)SL_TILE * (out_count ? 2ull * kw + M : 8ull * kw + 8ull * (((u64)M + 7) / 8));
       const u32 S = (u32)std::min<u64>(std::max<u64>((loads + SL_LOADS_PER_WG - 1) / SL_LOADS_PER_WG, 1), 1024);
-      const u32 grid = (u32)std::min<u64>((u64)tiles * S, SL_MAX_GRID);
+      const u32 grid = (u32)std::min<u64>((u64)tiles * S, kmx_grid_cap(SL_MAX_GRID));
       const u32 ob = (u32)(((u64)M + 7) / 8);
       if (out_count) hipLaunchKernelGGL(k_select_move_cc, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->irb, N, 2 * kw, M, d_cols,
                                         zb ? T->min_abund : 0u, (const u32*)R->d_keep, (const u32*)R->d_tiles, S, (u32*)R->d_out);
@@ -337,7 +337,7 @@ static int select_queue(kmx_ctx* ctx, const kmx_select_task* T, kmx_select_resul
                               T->min_abund, (const u32*)R->d_keep, (const u32*)R->d_tiles, S, R->d_out);
       KMX_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_select_place, dim3(std::min(tiles, SL_MAX_GRID)), dim3(SL_TILE), 0, st, (const u32*)R->d_keep, (const u32*)R->d_recv, n_rows,
+    hipLaunchKernelGGL(k_select_place, dim3(std::min(tiles, kmx_grid_cap(SL_MAX_GRID))), dim3(SL_TILE), 0, st, (const u32*)R->d_keep, (const u32*)R->d_recv, n_rows,
                        (const u32*)R->d_tiles, R->d_recs);
     KMX_HIP(ctx, hipGetLastError());
   }

@@ -258,9 +258,9 @@ static int zquery_queue(kmx_ctx* ctx, const kmx_zquery_task* K, kmx_zquery_resul
     KMX_HIP(ctx, launch_filter_scan(d_cell, (u32)(cells - 1), st));
     KMX_HIP(ctx, launch_query_parts(d_cell, P, n_chunks, d_pstart, st));
     KMX_HIP(ctx, launch_zquery_scatter(d_keys, n_bases, n_tiles, n_chunks, tpc, d_cell, d_recs, st));
-    KMX_HIP(ctx, launch_zquery_rows(d_recs, n_bases, d_pstart, P, R->d_rows, nb, N, R->d_bits, (u32)ctx->n_cu, st));
+    KMX_HIP(ctx, launch_zquery_rows(d_recs, n_bases, d_pstart, P, R->d_rows, nb, N, R->d_bits, (u32)kmx_plan_cus(ctx), st));
     if (R->last)
-      KMX_HIP(ctx, launch_zquery_window(d_keys, (const u64*)K->offsets, n_seqs, n_bases, K->z, R->d_bits, nb, N, R->d_kmers, R->d_hits, (u32)ctx->n_cu, st));
+      KMX_HIP(ctx, launch_zquery_window(d_keys, (const u64*)K->offsets, n_seqs, n_bases, K->z, R->d_bits, nb, N, R->d_kmers, R->d_hits, (u32)kmx_plan_cus(ctx), st));
   }
   return seq_queue_tail(R, d_pstart, P + 1);
 }

@@ -71,6 +71,35 @@ def combine_expected(blocks, kw, mode, drop_last=False):
     return b"".join(out), len(order)
 
 
+def combine_expected_np(blocks, kw, mode, drop_last=False):
+    """the same body by another road, for blocks too long for the dictionary: numpy over whole columns -- the union is np.unique over
+    the keys' words, most significant first; a block's payload goes to its rows of the union at once.  tests/test_combine_cpu.py holds
+    the two against each other.  -> (body bytes, rows)"""
+    keys = [np.asarray(b[0], np.uint64).reshape(-1, kw) for b in blocks]
+    total = sum(b[2] for b in blocks)
+    if not sum(len(k) for k in keys):
+        return b"", 0
+    union, inv = np.unique(np.concatenate(keys)[:, ::-1], axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    rows = len(union)
+    if drop_last and rows and int((inv == rows - 1).sum()) == 1:
+        rows -= 1
+    wide = np.zeros((len(union), total), np.uint32 if mode == MODE_COUNT else np.uint8)      # a count, or a bit, per column
+    at, pos = 0, 0
+    for b, k in zip(blocks, keys):
+        n_cols, cb = b[2], (b[3] if len(b) > 3 else 4)
+        if len(k):
+            pl = np.ascontiguousarray(np.asarray(b[1], np.uint8).reshape(len(k), payload_bytes(n_cols, mode, cb)))
+            vals = pl.view(COUNT_DTYPE[cb]).astype(np.uint32) if mode == MODE_COUNT else np.unpackbits(pl, axis=1, bitorder="little")[:, :n_cols]
+            wide[inv[at:at + len(k)], pos:pos + n_cols] = vals
+        at += len(k)
+        pos += n_cols
+    pay = wide.astype("<u4").view(np.uint8).reshape(len(union), 4 * total) if mode == MODE_COUNT else \
+        np.packbits(wide, axis=1, bitorder="little").reshape(len(union), (total + 7) // 8)
+    low_first = np.ascontiguousarray(union[:, ::-1]).astype("<u8").view(np.uint8).reshape(len(union), 8 * kw)
+    return np.concatenate([low_first, pay], axis=1)[:rows].tobytes(), rows
+
+
 def sort_keys(keys):
     """distinct keys uint64[n, kw] in ascending order, most significant word first"""
     keys = np.unique(np.asarray(keys, np.uint64).reshape(len(keys), -1), axis=0)
@@ -109,3 +138,27 @@ def synth_case(seed, rows, n_cols, kw, mode, share=0.5, shape="uniform", count_b
             payload = rng.integers(0, 256, (n, (n_cols[i] + 7) // 8), dtype=np.uint8)
         out.append((keys, np.ascontiguousarray(payload), n_cols[i], count_bytes[i]))
     return out
+
+
+def _payload(rng, n, n_cols, mode):
+    if mode == MODE_COUNT:
+        cols = rng.integers(0, 300, (n, n_cols), dtype=np.uint32)
+        cols[rng.random(cols.shape) < 0.2] = 0xFFFFFFFF
+        return np.ascontiguousarray(cols.view(np.uint8).reshape(n, 4 * n_cols))
+    return rng.integers(0, 256, (n, (n_cols + 7) // 8), dtype=np.uint8)
+
+
+def span_case(seed, kw, mode, n_b, n_a=200, cols=(3, 5)):
+    """two blocks for the edge of k_combine_rank's staged span: block A has n_a rows (one rank tile), its smallest key below and its
+    largest above every key of block B, so that the span of A's tile in B is all n_b rows of B; half of A's other keys are keys of B
+    too (share 0.5).  -> [A, B] as synth_case gives blocks"""
+    rng = np.random.default_rng(seed)
+    own = n_a - (n_a - 2) // 2      # A's keys that B lacks, its two ends among them
+    pool = sort_keys(rng.integers(0, 2 ** 64, (n_b + own + 64, kw), dtype=np.uint64, endpoint=False))[:n_b + own]
+    assert len(pool) == n_b + own
+    inner = rng.permutation(np.arange(1, len(pool) - 1))
+    a_own = np.concatenate([[0, len(pool) - 1], inner[:own - 2]])
+    b_idx = np.sort(inner[own - 2:])
+    a_idx = np.sort(np.concatenate([a_own, rng.choice(b_idx, n_a - own, replace=False)]))
+    assert len(a_idx) == n_a and len(b_idx) == n_b and a_idx[0] < b_idx[0] and a_idx[-1] > b_idx[-1]
+    return [(pool[a_idx], _payload(rng, n_a, cols[0], mode), cols[0], 4), (pool[b_idx], _payload(rng, n_b, cols[1], mode), cols[1], 4)]

@@ -207,6 +207,9 @@ def totals_of(sums, group):
 
 # ---- what the GPU test sends: one list, walked by both test files --------------------------------------------------------------------
 P05 = 0.05
+WIDE_COUNT_COLS = ((1025, 2025), (1100, 2100))      # (N, seed)
+RW_ROWS = (131, 300, 700, 1500, 2048 + 77)
+RW_SEEDS = {(m, rows): 3000 + 10 * i + j for j, m in enumerate(("count", "pa")) for i, rows in enumerate(RW_ROWS)}
 
 
 class Case:
@@ -257,14 +260,15 @@ class Case:
 def gpu_cases():
     cases = []
 
-    def add(name, mode, N, kw, rows, group, totals=None, thresholds=("p05",), min_rec=0, make=None, **mk):
-        sd = len(cases) + 1000
+    def add(name, mode, N, kw, rows, group, totals=None, thresholds=("p05",), min_rec=0, make=None, seed=None, **mk):
+        sd = len(cases) + 1000 if seed is None else seed
         g = np.asarray(group, np.uint8)
         cases.append(Case(name, mode, N, kw, rows, g, make or (lambda: make_body(sd, rows, N, kw, mode, group=g, **mk)), totals, thresholds, min_rec))
 
     for mode in (MODE_COUNT, MODE_PA):
         m = "count" if mode == MODE_COUNT else "pa"
         # columns: both sides of the byte, of a wave's worth of units (64 counts; 64 bytes = 512 bits) and of the 16 units a lane holds
+        # (that last edge, 1024 count columns, is WIDE_COUNT_COLS at the end of the list)
         for N in (2, 7, 8, 9, 63, 64, 65, 100, 128, 129, 1000):
             rows = 131 if N == 1000 else 150
             add(f"cols-{m}-{N}", mode, N, 1, rows, random_groups(N, N) if N > 2 else [CTRL, CASE], thresholds=(0.0, "p05", math.inf),
@@ -294,6 +298,22 @@ def gpu_cases():
                 make=lambda mode=mode: np.full(70 * row_bytes(1, 1000, mode), 0xFF, np.uint8))
         # kept shares: near 0.1 %, 50 % and all, over several tiles
         add(f"shares-{m}", mode, 24, 1, 4000, random_groups(77, 24), thresholds=(("top", 0.001), ("top", 0.5), 0.0), fill=0.3, effect=0.002)
+    # (appended behind the cases above, whose seeds follow their place in the list; the seeds below are chosen so that no row lies in
+    # the band of its threshold)
+    # count columns on both sides of the 16 units a lane of k_diff_score keeps the groups of in a register (64 lanes x 16 = 1024
+    # columns): beyond them the group comes from memory, and ignored columns lie there
+    for N, sd in WIDE_COUNT_COLS:
+        g = random_groups(N, N)
+        g[1024] = IGN      # (N = 1025: the one column out there)
+        assert N == 1025 or (g[1025:] == CTRL).any() and (g[1025:] == CASE).any() and (g[1025:] == IGN).any()
+        add(f"cols-count-{N}", MODE_COUNT, N, 1, 70, g, thresholds=(0.0, "p05", math.inf), seed=sd, fill=0.4, maxed=0.02, effect=0.1)
+    # long rows (a wave a row) in every number that gives k_diff_score another chunk of rows when the host plans for one CU
+    # (tests/test_launch_shapes_gpu.py): 4, 8, 16, 32 and 64 rows a wave, the last chunk partial, nine placement tiles at the most
+    for mode, N in ((MODE_COUNT, 70), (MODE_PA, 520)):
+        m = "count" if mode == MODE_COUNT else "pa"
+        for i, rows in enumerate(RW_ROWS):
+            add(f"rw-{m}-{rows}", mode, N, 1 + (i + mode) % 4, rows, random_groups(rows + N, N), thresholds=(0.0, "p05"),
+                seed=RW_SEEDS[(m, rows)], fill=0.5, effect=0.05)
     return cases
 
 

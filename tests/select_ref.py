@@ -138,6 +138,7 @@ COLUMN_SHAPES = [(1, "identity", 1), (7, "reversed", 7), (8, "perm", 7), (8, "ev
                  (63, "perm", 9), (63, "none", 63), (64, "reversed", 64), (64, "none", 64), (65, "perm", 63), (65, "identity", 65),
                  (130, "perm", 64), (130, "every-other", 65), (520, "perm", 65), (520, "every-other", 260), (520, "none", 520),
                  (520, "one", 1)]
+WIDE_COUNT_SHAPES = [(2049, "every-other", 1025), (2049, "perm", 1000), (2100, "every-other", 1050), (2100, "perm", 1000)]
 ROWS = [0, 1, 63, 64, 65, 255, 256, 257, 4200]
 FILLS = [0.0, 0.02, 0.5, 1.0]
 ABUNDS = [1, 2, U32]
@@ -179,6 +180,24 @@ def gpu_cases():
                 dict(out_mode=out_mode, min_abund=a, min_rec=3, max_rec=None, zero_below=False)]
         make = (lambda sd=sd, mode=mode: make_body(sd, 1000, 9, 2, mode, fill=0.5, pad_ones=True, maxed=0.05, lo=1, hi=4))
         cases.append(Case(f"{PAIR_NAMES[(mode, out_mode)]}-subset", mode, out_mode, 9, 2, 1000, make_cols("perm", 9, 8, sd), runs, make))
+    # (appended behind the cases above: the running index goes on, no earlier seed moves)
+    # count columns on both sides of the 32 units a lane of k_select_score keeps the selection of in a register (64 lanes x 32 = 2048
+    # columns): beyond them it comes from memory; the lists take some of the columns out there and leave some
+    for N, kind, M in WIDE_COUNT_SHAPES:
+        for mode, out_mode in MODE_PAIRS[:2]:
+            rows, kw, fill = 150, 1 + i % 4, 0.5
+            sd = 7000 + i
+            cols = make_cols(kind, 2048 if (N, kind) == (2049, "perm") else N, M, sd)      # (N = 2049: "perm" leaves the one column out there)
+            assert len(cols) == M
+            runs = []
+            for ri, (lo, hi) in enumerate(rec_ranges(M)[:4]):
+                a = ABUNDS[(i + ri) % 2]
+                runs.append(dict(out_mode=out_mode, min_abund=a, min_rec=lo, max_rec=hi, zero_below=out_mode == MODE_COUNT and (i + ri) % 2 == 1))
+            # (half the selected columns hold a row on average: about half the rows are kept)
+            runs.append(dict(out_mode=out_mode, min_abund=1, min_rec=M // 2, max_rec=M, zero_below=False))
+            make = (lambda sd=sd, rows=rows, N=N, kw=kw, fill=fill: make_body(sd, rows, N, kw, MODE_COUNT, fill=fill, pad_ones=True, maxed=0.05, lo=1, hi=4))
+            cases.append(Case(f"{PAIR_NAMES[(mode, out_mode)]}-{N}-{kind}-{M}-r{rows}-k{kw}-f{fill}", mode, out_mode, N, kw, rows, cols, runs, make))
+            i += 1
     return cases
 
 

@@ -105,6 +105,37 @@ def test_two_word_keys_where_only_the_high_word_differs():
     assert [k for k, _ in count_rows(cr.combine_expected([c], 2, cr.MODE_COUNT)[0], 2, 1)] == [(2 ** 64 - 1) | (1 << 64), 2 << 64]
 
 
+def test_the_two_roads_agree():
+    """the numpy road (for the blocks of the GPU test that are too long for the dictionary) against the dictionary: every key width and
+    key shape, both modes, count widths 1, 2 and 4, empty blocks, shares 0 ... 1, drop_last with one holder and with two"""
+    from synth import SHAPES
+    for kw in (1, 2, 3, 4):
+        for si, shape in enumerate(SHAPES):
+            for mode in (cr.MODE_COUNT, cr.MODE_PA):
+                blocks = cr.synth_case(10 * kw + si, [300, 0, 170, 40], [7, 2, 9, 1], kw, mode, share=(0.0, 0.5, 1.0)[(kw + si) % 3], shape=shape,
+                                       count_bytes=[4, 4, 1, 2], extreme=True)
+                for drop in (False, True):
+                    assert cr.combine_expected_np(blocks, kw, mode, drop) == cr.combine_expected(blocks, kw, mode, drop), (kw, shape, mode, drop)
+    for mode in (cr.MODE_COUNT, cr.MODE_PA):
+        empty = cr.synth_case(1, [0, 0], [3, 9], 2, mode)
+        assert cr.combine_expected_np(empty, 2, mode, True) == cr.combine_expected(empty, 2, mode, True) == (b"", 0)
+        top = (K(1, 9), np.full((2, cr.payload_bytes(3, mode)), 0x5A, np.uint8), 3, 4)
+        for other in (K(2, 9), K(2, 8)):      # the greatest key held by two blocks, and by one
+            blocks = [top, (other, np.full((2, cr.payload_bytes(2, mode)), 0xC3, np.uint8), 2, 4)]
+            for drop in (False, True):
+                assert cr.combine_expected_np(blocks, 1, mode, drop) == cr.combine_expected(blocks, 1, mode, drop)
+
+
+def test_span_case_is_what_it_says():
+    """block A's ends enclose every key of block B; A shares half its other keys with B; both ascend strictly"""
+    for kw in (1, 2, 3, 4):
+        for n_b in (2048 // kw, 2048 // kw + 1):
+            a, b = cr.span_case(kw, kw, cr.MODE_COUNT, n_b)
+            va, vb = [cr._value(k) for k in a[0]], [cr._value(k) for k in b[0]]
+            assert len(va) == 200 and len(vb) == n_b and va == sorted(set(va)) and vb == sorted(set(vb))
+            assert va[0] < vb[0] and va[-1] > vb[-1] and len(set(va) & set(vb)) == 99
+
+
 # ---- the host path of the driver against the restatement ------------------------------------------------------------------------
 def make_runs(tmp_path, kind, P=3, seed=0):
     """three runs of 3, 11 and 6 columns over P partitions -> (fof path, blocks[run][partition], total columns)"""

@@ -145,6 +145,53 @@ def test_dirty_pa_padding(ctx):
     assert not (last >> 4).any()      # 20 columns: the upper half of the third byte is padding
 
 
+@pytest.mark.parametrize("mode", [cr.MODE_COUNT, cr.MODE_PA])
+@pytest.mark.parametrize("kw", [1, 2, 3, 4])
+def test_span_at_the_edge_of_the_staged_keys(ctx, kw, mode):
+    """k_combine_rank stages a tile's span of another block's keys in LDS when it holds at most CAP = 2048 / kw keys: block A's one
+    tile spans all of block B, of exactly CAP rows (staged) and of CAP + 1 (searched in global memory), in both block orders"""
+    cap = 2048 // kw      # CB_LDS_W / KW (kmtricks_amd/csrc/combine.hip)
+    for n_b in (cap, cap + 1):
+        a, b = cr.span_case(100 * kw + n_b % 7 + mode, kw, mode, n_b)
+        assert cr._value(a[0][0]) < cr._value(b[0][0]) and cr._value(a[0][-1]) > cr._value(b[0][-1]) and len(b[0]) == n_b
+        for blocks in ([a, b], [b, a]):
+            out = check(ctx, blocks, kw, mode, what=f"span={n_b} kw={kw} mode={mode} first={blocks[0][2]}")
+            assert out.rows == 200 + n_b - 99
+
+
+@pytest.mark.parametrize("mode", [cr.MODE_COUNT, cr.MODE_PA])
+def test_scan_carry(ctx, mode):
+    """a block of more than 1024 rank tiles (262144 rows): k_combine_scan takes its tile counts in two trips of 1024 and carries the
+    sum over; against the numpy road of the restatement (the dictionary is for a few thousand rows)"""
+    rows = [262144 + 300, 1000]
+    assert (rows[0] + 255) // 256 > 1024
+    blocks = cr.synth_case(262 + mode, rows, [1, 3], 1, mode, share=0.5, extreme=True)
+    for order in (blocks, blocks[::-1]):
+        exp, n = cr.combine_expected_np(order, 1, mode)
+        out = ctx.combine([(cr.block_body(b[0], b[1]), b[2], b[3]) for b in order], 1, mode)
+        assert out.rows == n == rows[0] + 500
+        same(out.body, exp, f"scan carry mode={mode} first={order[0][2]}")
+
+
+def move_rows_log(orb):
+    """rows of a workgroup of k_combine_move, as launch_combine_move works them out: about 128 KB of them"""
+    sr_log = 8
+    while sr_log > 0 and (orb << sr_log) > 131072:
+        sr_log -= 1
+    return sr_log
+
+
+def test_output_rows_of_64_kb_and_more(ctx):
+    """count rows so wide that a workgroup of k_combine_move takes two output rows at a time, and one (a row above 128 KB)"""
+    seen = set()
+    for cols in ([20000, 13000], [9000, 9000], [8000, 8000]):
+        blocks = cr.synth_case(sum(cols) % 97, [40, 40], cols, 1, cr.MODE_COUNT, share=0.5, extreme=True)
+        seen.add(move_rows_log(8 + 4 * sum(cols)))
+        for order in (blocks, blocks[::-1]):
+            check(ctx, order, 1, cr.MODE_COUNT, what=f"cols={[b[2] for b in order]}")
+    assert seen == {0, 1} and move_rows_log(8 + 4 * 33000) == 0 and move_rows_log(8 + 4 * 16000) == 1
+
+
 # ---- device residency -----------------------------------------------------------------------------------------------------------
 def test_combine_dev_on_torch_tensors(ctx):
     torch = pytest.importorskip("torch")

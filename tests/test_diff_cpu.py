@@ -126,6 +126,20 @@ def test_no_row_of_the_gpu_inputs_lies_in_the_band():
         assert all(x["r0"] == x["r1"] == 0 and x["c0"] == x["c1"] == 0 for x in fr.case(f"ignored-{m}").rows)
     big = fr.case("ones-count-own")
     assert big.rows[0]["c0"] == int((big.group == 0).sum()) * 0xFFFFFFFF > 2 ** 40
+    # the cases at the end of the list: count columns beyond the 1024 whose groups a lane keeps in a register, ignored ones among
+    # them and columns that count; the long rows of the chunk sweep, whose p = 0.05 keep sets are proper subsets
+    for N, _ in fr.WIDE_COUNT_COLS:
+        c = fr.case(f"cols-count-{N}")
+        assert N > 1024 and c.group[1024] == fr.IGN and c.thresholds[0] == 0.0 and math.isinf(c.thresholds[2])
+        pay = dr.split_payload(c.body, N, 1, COUNT)
+        assert pay[:, 1024:].any(axis=1).sum() >= 20      # rows that hold a count out there: a group read wrong shows in their sums
+    assert set(fr.case("cols-count-1100").group[1025:].tolist()) == {0, 1, 2}
+    for m, N in (("count", 70), ("pa", 520)):
+        for rows in fr.RW_ROWS:
+            c = fr.case(f"rw-{m}-{rows}")
+            n = sum(fr.keep_expected(c.rows, c.thresholds[1])[0])
+            assert c.n_cols == N and c.n_rows == rows and 0 < n < rows, (c.name, n)
+        assert {fr.case(f"rw-{m}-{rows}").key_words for rows in fr.RW_ROWS} == {1, 2, 3, 4}
 
 
 def test_header_and_binding_name_the_same_symbols():

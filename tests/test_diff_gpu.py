@@ -179,6 +179,29 @@ def test_colsums(ctx, mode):
             r.free()
 
 
+@pytest.mark.parametrize("N", [2049, 4100])
+def test_colsums_of_wide_pa_rows(ctx, N):
+    """presence/absence rows of more than 256 payload bytes: k_colsums<PA> takes them in two and three blocks of 256 bytes (grid x);
+    every padding bit set; one call, and calls over cuts that accumulate into a caller's table"""
+    import torch
+    rows, kw = 150, 1 + N % 4
+    rb = dr.row_bytes(kw, N, PA)
+    assert (N + 7) // 8 > 256
+    body = fr.make_body(N, rows, N, kw, PA, fill=0.4, pad_ones=True)
+    assert (body.reshape(rows, rb)[:, -1] >> (N % 8)).min() == (0xFF >> (N % 8))
+    exp = fr.colsums_np(body, N, kw, PA)
+    assert exp[-1] > 0 and exp[2048] > 0 and len(set(exp.tolist())) > 10
+    assert np.array_equal(ctx.colsums(body, rows, N, kw, PA), exp)
+    table = torch.zeros(N, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    cuts = [0, 1, 50, 101, rows]
+    for series in (1, 2):
+        for a, b in reversed(list(zip(cuts[:-1], cuts[1:]))):
+            ctx.colsums(body[a * rb:b * rb], b - a, N, kw, PA, sums_dev=table.data_ptr())
+        torch.cuda.synchronize()
+        assert np.array_equal(table.cpu().numpy().view(np.uint64), series * exp), series
+
+
 def test_limits_are_refused(ctx):
     from kmtricks_amd import lib
     c = fr.case("cols-count-9")

@@ -116,6 +116,17 @@ def test_headline_rows(ctx):
     check(ctx, fr.synth_case(21, 20000, 1000, 1, fr.MODE_COUNT, 0.5), 1000, 1, fr.MODE_COUNT, what="20000 x 1000")
 
 
+def test_rows_above_64_kb(ctx):
+    """16 500 count columns: a row of 66 008 bytes, two of which are more than the 128 KB a workgroup of k_filter_move takes -- it
+    moves one row (sr = 1), the tile's 256 ranks one by one"""
+    n_cols = 16500
+    irb, sr = 8 + 4 * n_cols, 256
+    while sr > 1 and sr * irb > 131072:      # launch_filter_move (kmtricks_amd/csrc/filter.hip)
+        sr >>= 1
+    assert sr == 1 and irb > 65536
+    check(ctx, fr.synth_case(165, 100, n_cols, 1, fr.MODE_COUNT, 0.5, extreme=True), n_cols, 1, fr.MODE_COUNT, what="100 x 16500")
+
+
 @pytest.mark.parametrize("want", ["k", "m", "v", "km", "kv", "mv", "kmv"])
 def test_every_subset_of_outputs(ctx, want):
     for mode in (fr.MODE_COUNT, fr.MODE_PA):

@@ -92,7 +92,18 @@ def test_the_sweep_covers_what_it_says():
                 shares[pair].add("none" if f == 0 else "all" if f == 1 else "subset" if 0.1 <= f <= 0.9 else "other")
         if c.mode == COUNT and c.n_rows:
             seen["maxed"].add(bool((dr.split_payload(c.body, c.n_cols, c.key_words, c.mode) == sr.U32).any()))
-    assert seen["N"] == {1, 7, 8, 9, 63, 64, 65, 130, 520}
+    assert seen["N"] == {1, 7, 8, 9, 63, 64, 65, 130, 520, 2049, 2100}
+    # count columns beyond the 2048 whose selection a lane keeps in a register: for both output modes, lists that take such a column and
+    # lists that leave one, and a run that keeps a proper subset of the rows
+    for N, kind, M in sr.WIDE_COUNT_SHAPES:
+        for pair in sr.MODE_PAIRS[:2]:
+            c = next(x for x in cases if x.n_cols == N and x.n_out == M and (x.mode, x.out_mode) == pair and f"-{kind}-" in x.name)
+            far = set(range(2048, N))
+            assert far & set(c.cols.tolist()) or N == 2049, c.name
+            assert 0.1 <= len(c.expected[-1][1]) / c.n_rows <= 0.9, c.name
+    took = {N: [bool(set(range(2048, N)) & set(c.cols.tolist())) for c in cases if c.n_cols == N] for N in (2049, 2100)}
+    left = {N: [bool(set(range(2048, N)) - set(c.cols.tolist())) for c in cases if c.n_cols == N] for N in (2049, 2100)}
+    assert all(any(took[N]) and any(left[N]) for N in (2049, 2100)), (took, left)
     assert seen["M"] >= {1, 7, 8, 9, 63, 64, 65, 520}
     assert seen["rows"] >= {0, 1, 63, 64, 65, 255, 256, 257, 4200}
     assert seen["kw"] == {1, 2, 3, 4} and seen["a"] == {1, 2, sr.U32} and seen["zb"] == {False, True} and True in seen["maxed"]
