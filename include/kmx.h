@@ -36,6 +36,8 @@
  *   kmx_diff_dev / _host        counts differ between case and control samples by a Poisson likelihood-ratio test, kept in file order
  *   kmx_select_dev / _host      no counterpart either (MUSET's `kmat_tools filter`): a smaller matrix out of a larger one -- a list of
  *                               columns in any order, the rows whose recurrence over them lies in a range, counts or presence/absence
+ *   kmx_pan_dev / _host         no counterpart either (pangrowth, Panacus `hist`): how many rows of a matrix 0, 1, ... M of a list of
+ *                               samples hold, where each row is first met and first missed along the list, and per sample by recurrence
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -851,6 +853,94 @@ double    kmx_select_result_kernel_ms(kmx_select_result* r);           /* needs 
 /* algorithmic bytes: the body read once + the kept rows written at their new size + 8 bytes per kept row */
 uint64_t  kmx_select_result_algo_bytes(kmx_select_result* r);
 void      kmx_select_result_free(kmx_select_result* r);
+
+/* -------------------------------------------------------------------- pan */
+
+/* The recurrence spectrum of a matrix (what pangrowth and Panacus `hist` / `histgrowth` / `ordered-histgrowth` compute; no counterpart in
+ * the kmtricks tree): how many rows are held by 0, 1, ... M of a list of samples, at which sample of the list a row is first met and
+ * first missed, and per sample how many rows of each recurrence it holds.  The pangenome growth and core curves follow from the first
+ * table in closed form, on the host.
+ * INPUT, as for kmx_select_*: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ * `rows` needs no alignment.  The padding bits of a PA row never reach a result.  Keys are never read.
+ * PARAMETERS:
+ *   cols       select's convention: a HOST array of M = n_use distinct input column indices, each < N, in any order; NULL is the
+ *              identity and requires M = N.  The list's ORDER is the order in which samples are "added" for the ordered curves:
+ *              ordinal j is input column cols[j].
+ *   min_abund  a >= 1 (exactly 1 for PA): a sample holds a row from this count upwards
+ *   flags      KMX_PAN_SHARED
+ * PER ROW:
+ *   present_j = (count[cols[j]] >= a) for COUNT, the bit of column cols[j] for PA
+ *   rec       = the sum of present_j over j < M
+ *   first     = min{ j : present_j }, M if there is none
+ *   gap       = min{ j : !present_j }, M if there is none
+ * OUTPUTS: u64 DEVICE tables.  The call ADDS into a table of the caller's, or into a zeroed one the result owns when the pointer is
+ * NULL.  Partitions and runs of rows accumulate in any order; n_rows = 0 adds nothing.
+ *   spectrum[3][M + 1]   [0][r] the rows with rec = r; [1][j] the rows with first = j; [2][j] the rows with gap = j
+ *   shared[M + 1][N]     (KMX_PAN_SHARED only) shared[r][c] the rows with rec = r in which INPUT column c is a listed column and
+ *                        present.  Unlisted columns and row r = 0 stay untouched.  (Indexed by input column so that a wave's adds are
+ *                        contiguous; a driver permutes for printing.)
+ * EXAMPLE.  N = 4, cols NULL, a = 1, four rows:
+ *   (1,0,2,0)  rec 2, first 0, gap 1
+ *   (0,0,0,5)  rec 1, first 3, gap 0
+ *   (3,3,3,3)  rec 4, first 0, gap 4
+ *   (0,0,0,0)  rec 0, first 4, gap 0
+ *   spectrum[0] = (1,1,1,0,1), spectrum[1] = (2,0,0,1,1), spectrum[2] = (2,1,0,0,1)
+ *   shared[1] = (0,0,0,1), shared[2] = (1,0,1,0), shared[4] = (1,1,1,1), every other row of shared is zero
+ * With a = 3 the first row has rec 0.  With cols = (3,0) the second row has rec 1, first 0, gap 1.
+ * IDENTITIES of one call's increments: the sum of spectrum[0] is n_rows; spectrum[1][M] = spectrum[0][0]; spectrum[2][M] =
+ * spectrum[0][M]; the sum of shared[r] over c is r * spectrum[0][r]; the sum of shared[.][c] over r is the number of rows that hold c
+ * (with a = 1 inter[c][c] of kmx_dist_*, the presence tally of kmx_colsums_* on PA rows).
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols or n_use = 0; n_use > n_cols; a column index >= N or listed twice;
+ * cols = NULL with M != N; key_words 0 or > 4; a mode other than COUNT / PA; min_abund 0; min_abund > 1 with PA; unknown flag bits; a
+ * shared table without KMX_PAN_SHARED.  KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT (a Bloom row is a hash bit: its
+ * recurrence is not a k-mer's); n_rows > 2^32 - 256; a row of 4 GiB or more; KMX_PAN_SHARED with (M + 1) * N * 8 >= 8 GiB.
+ * SCRATCH from the context's pool, per call, given back when the call has run: the ordinal table (4 bytes per input column, rounded up
+ * to 8 columns), a call-local spectrum (24 * (M + 1) bytes); with KMX_PAN_SHARED 4 * (M + 1) bytes of class cursors and 12 bytes per
+ * input row (its recurrence, and its (row, rec) place in recurrence order); for _host the uploaded rows.  The tables the result owns
+ * (24 * (M + 1) bytes; with KMX_PAN_SHARED 8 * (M + 1) * N) live until the result is freed.  Send a body that does not fit in runs of
+ * rows. */
+#define KMX_PAN_SHARED 1u
+
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_use;         /* M: samples of the list */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices in the order they are added (copied by the call), or NULL: the identity */
+  uint32_t        min_abund;     /* a */
+  uint32_t        flags;         /* KMX_PAN_SHARED */
+  uint64_t*       spectrum;      /* NULL, or a device table of 3 * (M + 1) u64 to accumulate into */
+  uint64_t*       shared;        /* NULL, or (KMX_PAN_SHARED) a device table of (M + 1) * N u64 to accumulate into */
+} kmx_pan_task;                  /* 64 bytes */
+
+typedef struct kmx_pan_result kmx_pan_result;
+
+/* _dev and _host as for kmx_select_*: rows a DEVICE pointer (a merge result's, a filter's, a combine's, a select's body, the caller's own
+ * memory), the kernels queued on the context's stream and the call back without waiting; or a HOST pointer, uploaded on a stream of its
+ * own, the buffer free for reuse once _result_wait has returned.  cols is a host array in both; spectrum and shared are device tables in
+ * both and stay the caller's. */
+int kmx_pan_dev(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out);
+int kmx_pan_host(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out);
+int       kmx_pan_result_wait(kmx_pan_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t* kmx_pan_result_spectrum_dev(kmx_pan_result* r);      /* the table as it stands: the result's own or the task's */
+uint64_t* kmx_pan_result_shared_dev(kmx_pan_result* r);        /* NULL without KMX_PAN_SHARED */
+int       kmx_pan_result_copy_spectrum(kmx_pan_result* r, uint64_t* host_dst, uint64_t dst_entries);   /* 3 * (M + 1) entries */
+int       kmx_pan_result_copy_shared(kmx_pan_result* r, uint64_t* host_dst, uint64_t dst_entries);     /* (M + 1) * N; KMX_E_INVAL without KMX_PAN_SHARED */
+/* duration in ms of the call's kernels, the clearing of the tables the result owns included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_pan_result_kernel_ms(kmx_pan_result* r);
+/* the same interval in its parts: clearing + k_pan_score + k_pan_fold, k_pan_order, k_pan_shared (the last two -1 without
+ * KMX_PAN_SHARED); any pointer may be NULL */
+int       kmx_pan_result_kernel_parts_ms(kmx_pan_result* r, double* score_ms, double* order_ms, double* shared_ms);
+/* algorithmic bytes: the body read once (n_rows * row bytes) + the spectrum (24 * (M + 1)); with KMX_PAN_SHARED the body read once more,
+ * 24 bytes per row (its recurrence and its place in the order, each written and read once) and the shared table (8 * (M + 1) * N)
+ *  */
+uint64_t  kmx_pan_result_algo_bytes(kmx_pan_result* r);
+void      kmx_pan_result_free(kmx_pan_result* r);
 
 /* ------------------------------------------------------------------ count */
 

@@ -1333,6 +1333,7 @@ int kmx_query_main(int argc, char** argv);      // kmx_query.cpp: query
 int kmx_dist_main(int argc, char** argv);       // kmx_dist.cpp: dist
 int kmx_diff_main(int argc, char** argv);       // kmx_diff.cpp: diff
 int kmx_select_main(int argc, char** argv);     // kmx_select.cpp: select
+int kmx_pan_main(int argc, char** argv);        // kmx_pan.cpp: pan
 
 int main(int argc, char** argv)
 {
@@ -1341,6 +1342,7 @@ int main(int argc, char** argv)
   if (argc >= 2 && std::string(argv[1]) == "dist") { try { return kmx_dist_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "diff") { try { return kmx_diff_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "select") { try { return kmx_select_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "pan") { try { return kmx_pan_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

@@ -107,6 +107,16 @@ SELECT_REC = np.dtype([("row", "<u4"), ("rec", "<u4")])
 assert SELECT_REC.itemsize == 8 and C.sizeof(KmxSelectTask) == 64
 SELECT_ZERO_BELOW = 1
 
+
+class KmxPanTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("min_abund", C.c_uint32),
+                ("flags", C.c_uint32), ("spectrum", C.c_void_p), ("shared", C.c_void_p)]
+
+
+assert C.sizeof(KmxPanTask) == 64
+PAN_SHARED = 1
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -379,6 +389,23 @@ _lib.kmx_select_result_free.argtypes = [_vp]
 SELECT_EXPORTS = ["kmx_select_dev", "kmx_select_host", "kmx_select_result_wait", "kmx_select_result_rows", "kmx_select_result_row_bytes",
                   "kmx_select_result_body_bytes", "kmx_select_result_body_dev", "kmx_select_result_copy_body", "kmx_select_result_recs_dev",
                   "kmx_select_result_copy_recs", "kmx_select_result_kernel_ms", "kmx_select_result_algo_bytes", "kmx_select_result_free"]
+_lib.kmx_pan_dev.argtypes = [_vp, C.POINTER(KmxPanTask), C.POINTER(_vp)]
+_lib.kmx_pan_host.argtypes = [_vp, C.POINTER(KmxPanTask), C.POINTER(_vp)]
+_lib.kmx_pan_result_wait.argtypes = [_vp]
+_lib.kmx_pan_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_pan_result_algo_bytes.argtypes = [_vp]
+for _f in ("kmx_pan_result_copy_spectrum", "kmx_pan_result_copy_shared"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_pan_result_spectrum_dev", "kmx_pan_result_shared_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_pan_result_kernel_ms.restype = C.c_double
+_lib.kmx_pan_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_pan_result_kernel_parts_ms.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+_lib.kmx_pan_result_free.argtypes = [_vp]
+PAN_EXPORTS = ["kmx_pan_dev", "kmx_pan_host", "kmx_pan_result_wait", "kmx_pan_result_spectrum_dev", "kmx_pan_result_shared_dev",
+               "kmx_pan_result_copy_spectrum", "kmx_pan_result_copy_shared", "kmx_pan_result_kernel_ms", "kmx_pan_result_kernel_parts_ms",
+               "kmx_pan_result_algo_bytes", "kmx_pan_result_free"]
 
 
 def zquery_bits_bytes(n_bases, n_cols):
@@ -1090,6 +1117,35 @@ class Context:
         return self._finish(SelectResult(self, res), keep)
 
     @staticmethod
+    def _pan_task(rows, n_rows, n_cols, key_words, mode, cols, min_abund, shared, spectrum_dev, shared_dev):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = n_cols if c is None else len(c)
+        want = bool(shared) or shared_dev is not None
+        t = KmxPanTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None, min_abund,
+                       PAN_SHARED if want else 0, spectrum_dev, shared_dev)
+        return t, c, n_use, want      # (c is kept alive by the caller until the call has copied it)
+
+    def pan(self, body, n_rows, n_cols, key_words, mode, cols=None, min_abund=1, shared=False, spectrum_dev=None, shared_dev=None, keep=False):
+        """kmx_pan_host: body as for select; cols: the input columns of the list in the order they are added (None: all, as they stand);
+        shared: the per-sample table by recurrence is computed too; spectrum_dev / shared_dev: None (the result owns a zeroed table) or a
+        device pointer to a uint64 table [3, M + 1] / [M + 1, n_cols] the call adds to (shared_dev implies shared).
+        -> PanOutput (numpy copies), or with keep the PanResult itself (the tables left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, c, n_use, want = self._pan_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, cols, min_abund, shared, spectrum_dev, shared_dev)
+        res = _vp()
+        self._check(_lib.kmx_pan_host(self._h, C.byref(t), C.byref(res)), "kmx_pan_host")
+        r = PanResult(self, res, n_cols, n_use, want)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def pan_dev(self, rows_dev, n_rows, n_cols, key_words, mode, cols=None, min_abund=1, shared=False, spectrum_dev=None, shared_dev=None, keep=False):
+        """kmx_pan_dev: rows_dev a device pointer to n_rows rows (cols stays a host array).  -> as pan"""
+        t, c, n_use, want = self._pan_task(rows_dev, n_rows, n_cols, key_words, mode, cols, min_abund, shared, spectrum_dev, shared_dev)
+        res = _vp()
+        self._check(_lib.kmx_pan_dev(self._h, C.byref(t), C.byref(res)), "kmx_pan_dev")
+        return self._finish(PanResult(self, res, n_cols, n_use, want), keep)
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -1329,6 +1385,62 @@ class DiffResult:
     def free(self):
         if self._h:
             _lib.kmx_diff_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PanOutput:
+    """spectrum uint64[3, M + 1]: rows by recurrence, by first ordinal, by first missing ordinal (the table the call added to, when one
+    was given); shared uint64[M + 1, n_cols] (None unless asked for): rows of recurrence r that input column c holds; kernel_ms < 0
+    without set_profiling"""
+
+    def __init__(self, spectrum, shared, kernel_ms, algo_bytes):
+        self.spectrum, self.shared, self.kernel_ms, self.algo_bytes = spectrum, shared, kernel_ms, algo_bytes
+
+
+class PanResult:
+    def __init__(self, ctx, h, n_cols, n_use, has_shared):
+        self._ctx, self._h, self._n, self._m, self._shared = ctx, h, n_cols, n_use, has_shared
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_pan_result_wait(self._h), "kmx_pan_result_wait")
+
+    def spectrum_dev(self):
+        return _lib.kmx_pan_result_spectrum_dev(self._h)
+
+    def shared_dev(self):
+        return _lib.kmx_pan_result_shared_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_pan_result_kernel_ms(self._h)
+
+    def kernel_parts_ms(self):
+        """(clearing + k_pan_score + k_pan_fold, k_pan_order, k_pan_shared) in ms; -1 where unavailable"""
+        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
+        self._ctx._check(_lib.kmx_pan_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_pan_result_kernel_parts_ms")
+        return a.value, b.value, c.value
+
+    def algo_bytes(self):
+        return _lib.kmx_pan_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        spectrum = np.zeros((3, self._m + 1), np.uint64)
+        self._ctx._check(_lib.kmx_pan_result_copy_spectrum(self._h, spectrum.ctypes.data, spectrum.size), "kmx_pan_result_copy_spectrum")
+        shared = None
+        if self._shared:
+            shared = np.zeros((self._m + 1, self._n), np.uint64)
+            self._ctx._check(_lib.kmx_pan_result_copy_shared(self._h, shared.ctypes.data, shared.size), "kmx_pan_result_copy_shared")
+        return PanOutput(spectrum, shared, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_pan_result_free(self._h)
             self._h = None
 
     def __del__(self):
