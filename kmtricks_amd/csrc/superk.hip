@@ -1024,6 +1024,9 @@ static int superk_impl(kmx_ctx* ctx, const char* bases, const uint64_t* offsets,
       const int kw = (int)((k + 31) / 32);
       const SkfLayout L = kmx_fast_layout(creq->hash_mode ? 1 : kw);
       const u32 tb_max = (u32)(kb / L.target) + P + 1, nc_max = (u32)(kb / L.chunk) + P + 1, nb_max = (u32)((kb + SKF_DK - 1) / SKF_DK) + 1;
+      // (KMX_TRACE=1: the grids the host planned from the sizes it knows -- the split's from the reads, the count's bounds from the bases; scan_mw = k_cs_scan_mw's workgroups)
+      if (getenv("KMX_TRACE")) fprintf(stderr, "[kmx count_reads_plan] reads %llu chunks %u rows %u wpg %u Gc %u rpg %u pbits %u tb_max %u nc_max %u nb_max %u scan_mw %u\n", (unsigned long long)n_seqs,
+                                       n_chunks, R, wpg, Gc, rpg, pbits, tb_max, nc_max, nb_max, (tb_max + 1 + 4095) / 4096);
       // ONE block: the part that is cleared -- [k_sk_scan's flags][the bucket scans' flags][the sample sort's bucket counters] ... [control 32 B]
       // [minimizers that occur, u64][lost buckets, u32 at + 48][pad to 64], a multiple of 256 bytes (the runtime clears an unaligned tail with a
       // launch of its own) -- and, right behind the control block, what the host reads at the call's end IN ONE COPY with it: [pp (P + 1) u64]
