@@ -38,6 +38,8 @@
  *                               columns in any order, the rows whose recurrence over them lies in a range, counts or presence/absence
  *   kmx_pan_dev / _host         no counterpart either (pangrowth, Panacus `hist`): how many rows of a matrix 0, 1, ... M of a list of
  *                               samples hold, where each row is first met and first missed along the list, and per sample by recurrence
+ *   kmx_colors_dev / _host      no counterpart either (the colour classes of Mantis, Bifrost, Fulgor, GGCAT; the bars of an UpSet plot): the
+ *                               distinct sets of samples that occur as a row's presence pattern, the rows of each, every row's class
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -68,7 +70,8 @@ enum {
   KMX_E_INVAL    = -2,   /* bad argument */
   KMX_E_NOMEM    = -3,   /* host or device allocation failed */
   KMX_E_HIP      = -4,   /* HIP runtime error during a call */
-  KMX_E_UNSUPPORTED = -5 /* configuration outside what this build handles (message says which) */
+  KMX_E_UNSUPPORTED = -5,/* configuration outside what this build handles (message says which) */
+  KMX_E_INTERNAL = -6    /* a bound inside the library was reached on the device (kmx_colors_*: the table's probe bound); never expected */
 };
 
 /* matrix row encodings; names follow kmtricks' --mode <kmer|hash>:<count|pa|bf|bfc>:bin */
@@ -941,6 +944,88 @@ int       kmx_pan_result_kernel_parts_ms(kmx_pan_result* r, double* score_ms, do
  *  */
 uint64_t  kmx_pan_result_algo_bytes(kmx_pan_result* r);
 void      kmx_pan_result_free(kmx_pan_result* r);
+
+/* ----------------------------------------------------------------- colors */
+
+/* The distinct sample sets of a matrix's rows (the colour classes of a coloured de Bruijn graph -- Mantis, Bifrost, Fulgor and GGCAT store
+ * k-mer -> class id plus a class table --, the exclusive regions of the N-way Venn diagram that an UpSet plot draws; no counterpart in
+ * the kmtricks tree): which exact sets of samples occur as a row's presence pattern, how many rows each set has, and every row's set.
+ * INPUT, as for kmx_pan_*: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ * `rows` needs no alignment.  The padding bits of a PA row never reach a result.  Keys are never read.
+ * PARAMETERS:
+ *   cols       pan's convention: a HOST array of M = n_use distinct input column indices, each < N, in the caller's order; NULL is the
+ *              identity and requires M = N.  Ordinal j is input column cols[j].
+ *   min_abund  a >= 1 (exactly 1 for PA): a sample holds a row from this count upwards
+ *   flags      none is defined: 0
+ * PER ROW:
+ *   present_j = (count[cols[j]] >= a) for COUNT, the bit of column cols[j] for PA
+ *   pattern   = the M-bit vector (present_0 ... present_{M-1}) packed as a PA payload of M columns in u64 words: ordinal j = bit j & 63
+ *               of word j >> 6; W = ceil(M / 64) words; the unused high bits of the last word are zero
+ * CLASSES: two rows are of one class exactly when their patterns are equal -- every word is compared, never a hash alone.  The classes
+ * are numbered 0 ... C - 1 in the order of their first row: class c's first row comes before class c + 1's.  The all-zero pattern is a
+ * class like any other.
+ * OUTPUTS, device memory the result owns (the _copy_ accessors bring them to the host; all wait for the call themselves):
+ *   n_classes       C
+ *   ids[n_rows]     u32, the class of every row
+ *   first[C]        u32, the class's first row
+ *   size[C]         u32, its rows
+ *   patterns[C][W]  u64
+ * EXAMPLE.  N = 4, cols NULL, a = 1, six rows (1,0,2,0) (0,0,0,5) (3,0,1,0) (0,0,0,0) (0,0,0,1) (7,0,9,0):
+ *   C = 3, patterns = (5, 8, 0), first = (0, 1, 3), size = (3, 2, 1), ids = (0,1,0,2,1,0)
+ *   a = 2:            C = 5, patterns = (4, 8, 1, 0, 5), size = (1,1,1,2,1), ids = (0,1,2,3,3,4)
+ *   cols = (2, 0):    C = 2, patterns = (3, 0), first = (0, 1), size = (3, 3), ids = (0,1,0,1,1,0)
+ * IDENTITIES: the sum of size is n_rows; ids[first[c]] = c; first is strictly ascending; the row first[c] has pattern patterns[c]; the
+ * sizes summed by popcount(pattern) are spectrum[0] of kmx_pan_* on the same task.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols or n_use = 0; n_use > n_cols; a column index >= N or listed twice;
+ * cols = NULL with M != N; key_words 0 or > 4; a mode other than COUNT / PA; min_abund 0; min_abund > 1 with PA; flag bits.
+ * KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT (a Bloom row is a hash bit: its sample set is not a k-mer's);
+ * n_rows > 2^32 - 256 (0xFFFFFFFF is the table's "empty"); a row of 4 GiB or more; scratch and result together beyond the device's
+ * memory.  n_rows = 0 is a valid call with C = 0.  (KMX_E_NOMEM: the pool could not give what the device has in principle.)
+ * SCRATCH from the context's pool, per call, given back when the call has run: PER ROW 8 * W + 24 bytes (the packed pattern, its 64-bit
+ * signature, the row's representative, and per representative the class's first row, its size and the first row's rank) plus the
+ * table, 4 bytes a slot, T = the power of two >= 2 * n_rows slots: 8 to 16 bytes a row -- 8 * W + 40 bytes a row at the most; 4 bytes a
+ * listed column; 4 bytes per 256 rows; for _host the uploaded rows.  The RESULT keeps 8 * W + 12 bytes per input row until it is freed
+ * (ids, and first / size / patterns sized for C = n_rows: C is known on the device only).  Send a body that does not fit in runs of
+ * rows and merge the class tables (as `kmx colors` does).
+ * KMX_E_INTERNAL from _wait and every accessor: a row found no slot within T probes (never expected: the table is at most half full). */
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_use;         /* M: samples of the list */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices in the caller's order (copied by the call), or NULL: the identity */
+  uint32_t        min_abund;     /* a */
+  uint32_t        flags;         /* 0 */
+} kmx_colors_task;               /* 48 bytes */
+
+typedef struct kmx_colors_result kmx_colors_result;
+
+/* _dev and _host as for kmx_pan_*: rows a DEVICE pointer, the kernels queued on the context's stream and the call back without waiting;
+ * or a HOST pointer, uploaded on a stream of its own, the buffer free for reuse once _result_wait has returned.  cols is a host array
+ * in both. */
+int kmx_colors_dev(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out);
+int kmx_colors_host(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out);
+int       kmx_colors_result_wait(kmx_colors_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t  kmx_colors_result_n_classes(kmx_colors_result* r);           /* C; 0 after an error */
+const uint32_t* kmx_colors_result_ids_dev(kmx_colors_result* r);       /* n_rows u32 on the device; NULL after an error */
+int       kmx_colors_result_copy_ids(kmx_colors_result* r, uint32_t* host_dst, uint64_t dst_entries);        /* n_rows entries */
+int       kmx_colors_result_copy_first(kmx_colors_result* r, uint32_t* host_dst, uint64_t dst_entries);      /* C */
+int       kmx_colors_result_copy_sizes(kmx_colors_result* r, uint32_t* host_dst, uint64_t dst_entries);      /* C */
+int       kmx_colors_result_copy_patterns(kmx_colors_result* r, uint64_t* host_dst, uint64_t dst_entries);   /* C * W */
+/* duration in ms of the call's kernels, the clearing of the table included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_colors_result_kernel_ms(kmx_colors_result* r);
+/* the same interval in its parts: k_col_pack; clearing + k_col_claim; k_col_flag + scan + k_col_number + k_col_ids + k_col_gather; any
+ * pointer may be NULL */
+int       kmx_colors_result_kernel_parts_ms(kmx_colors_result* r, double* pack_ms, double* claim_ms, double* number_ms);
+/* algorithmic bytes: the body read once (n_rows * row bytes) + the packed patterns and signatures written once and read once
+ * (2 * n_rows * (8 * W + 8)) + ids (4 * n_rows) + the class table (C * (8 + 8 * W)) */
+uint64_t  kmx_colors_result_algo_bytes(kmx_colors_result* r);
+void      kmx_colors_result_free(kmx_colors_result* r);
 
 /* ------------------------------------------------------------------ count */
 

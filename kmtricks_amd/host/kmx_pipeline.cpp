@@ -65,7 +65,7 @@ static double since(clk::time_point t) { return std::chrono::duration<double>(cl
 
 static Opt parse_cli(int argc, char** argv)
 {
-  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx filter --in-matrix <dir> --key <fof> --output <dir> [options] | kmx dist --run <dir> [options] | kmx diff --run <dir> --groups <file> [options] | kmx select --run <dir> --output <dir> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
+  if (argc < 2 || (std::string(argv[1]) != "pipeline" && std::string(argv[1]) != "merge")) die("usage: kmx pipeline --file <fof> --run-dir <dir> [options] | kmx merge --run-dir <dir> [options] | kmx filter --in-matrix <dir> --key <fof> --output <dir> [options] | kmx dist --run <dir> [options] | kmx diff --run <dir> --groups <file> [options] | kmx select --run <dir> --output <dir> [options] | kmx colors --run <dir> [options] | kmx dump --input <file> [-o out] | kmx aggregate --run-dir <dir> --matrix kmer|hash ...  (see INTEGRATION.md)");
   Opt o;
   // `kmtricks merge` (src/cli.cpp:526-646): --run-dir, --partition-id, --soft-min, --recurrence-min, --share-min, --mode, --clear, --cpr,
   // -t; what the run was made with (k, partitions, Bloom size, minimizer size) is read back from its options.txt below
@@ -1334,6 +1334,7 @@ int kmx_dist_main(int argc, char** argv);       // kmx_dist.cpp: dist
 int kmx_diff_main(int argc, char** argv);       // kmx_diff.cpp: diff
 int kmx_select_main(int argc, char** argv);     // kmx_select.cpp: select
 int kmx_pan_main(int argc, char** argv);        // kmx_pan.cpp: pan
+int kmx_colors_main(int argc, char** argv);     // kmx_colors.cpp: colors
 
 int main(int argc, char** argv)
 {
@@ -1343,6 +1344,7 @@ int main(int argc, char** argv)
   if (argc >= 2 && std::string(argv[1]) == "diff") { try { return kmx_diff_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "select") { try { return kmx_select_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "pan") { try { return kmx_pan_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "colors") { try { return kmx_colors_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

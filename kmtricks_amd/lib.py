@@ -117,6 +117,16 @@ class KmxPanTask(C.Structure):
 assert C.sizeof(KmxPanTask) == 64
 PAN_SHARED = 1
 
+
+class KmxColorsTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("min_abund", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+assert C.sizeof(KmxColorsTask) == 48
+E_INTERNAL = -6
+
 _vp = C.c_void_p
 _lib.kmx_version.restype = C.c_int
 _lib.kmx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -403,6 +413,23 @@ _lib.kmx_pan_result_kernel_ms.restype = C.c_double
 _lib.kmx_pan_result_kernel_ms.argtypes = [_vp]
 _lib.kmx_pan_result_kernel_parts_ms.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
 _lib.kmx_pan_result_free.argtypes = [_vp]
+_lib.kmx_colors_dev.argtypes = [_vp, C.POINTER(KmxColorsTask), C.POINTER(_vp)]
+_lib.kmx_colors_host.argtypes = [_vp, C.POINTER(KmxColorsTask), C.POINTER(_vp)]
+_lib.kmx_colors_result_wait.argtypes = [_vp]
+for _f in ("kmx_colors_result_n_classes", "kmx_colors_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_colors_result_ids_dev.restype = _vp
+_lib.kmx_colors_result_ids_dev.argtypes = [_vp]
+for _f in ("kmx_colors_result_copy_ids", "kmx_colors_result_copy_first", "kmx_colors_result_copy_sizes", "kmx_colors_result_copy_patterns"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_colors_result_kernel_ms.restype = C.c_double
+_lib.kmx_colors_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_colors_result_kernel_parts_ms.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+_lib.kmx_colors_result_free.argtypes = [_vp]
+COLORS_EXPORTS = ["kmx_colors_dev", "kmx_colors_host", "kmx_colors_result_wait", "kmx_colors_result_n_classes", "kmx_colors_result_ids_dev",
+                  "kmx_colors_result_copy_ids", "kmx_colors_result_copy_first", "kmx_colors_result_copy_sizes", "kmx_colors_result_copy_patterns",
+                  "kmx_colors_result_kernel_ms", "kmx_colors_result_kernel_parts_ms", "kmx_colors_result_algo_bytes", "kmx_colors_result_free"]
 PAN_EXPORTS = ["kmx_pan_dev", "kmx_pan_host", "kmx_pan_result_wait", "kmx_pan_result_spectrum_dev", "kmx_pan_result_shared_dev",
                "kmx_pan_result_copy_spectrum", "kmx_pan_result_copy_shared", "kmx_pan_result_kernel_ms", "kmx_pan_result_kernel_parts_ms",
                "kmx_pan_result_algo_bytes", "kmx_pan_result_free"]
@@ -1146,6 +1173,32 @@ class Context:
         return self._finish(PanResult(self, res, n_cols, n_use, want), keep)
 
     @staticmethod
+    def _colors_task(rows, n_rows, n_cols, key_words, mode, cols, min_abund):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = n_cols if c is None else len(c)
+        t = KmxColorsTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None, min_abund, 0)
+        return t, c, n_use      # (c is kept alive by the caller until the call has copied it)
+
+    def colors(self, body, n_rows, n_cols, key_words, mode, cols=None, min_abund=1, keep=False):
+        """kmx_colors_host: body as for pan; cols: the input columns of the list in the caller's order (None: all, as they stand); a
+        sample holds a row from min_abund upwards.
+        -> ColorsOutput (numpy copies), or with keep the ColorsResult itself (ids and the class table left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, c, n_use = self._colors_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, cols, min_abund)
+        res = _vp()
+        self._check(_lib.kmx_colors_host(self._h, C.byref(t), C.byref(res)), "kmx_colors_host")
+        r = ColorsResult(self, res, n_rows, n_use)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def colors_dev(self, rows_dev, n_rows, n_cols, key_words, mode, cols=None, min_abund=1, keep=False):
+        """kmx_colors_dev: rows_dev a device pointer to n_rows rows (cols stays a host array).  -> as colors"""
+        t, c, n_use = self._colors_task(rows_dev, n_rows, n_cols, key_words, mode, cols, min_abund)
+        res = _vp()
+        self._check(_lib.kmx_colors_dev(self._h, C.byref(t), C.byref(res)), "kmx_colors_dev")
+        return self._finish(ColorsResult(self, res, n_rows, n_use), keep)
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -1441,6 +1494,63 @@ class PanResult:
     def free(self):
         if self._h:
             _lib.kmx_pan_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ColorsOutput:
+    """n_classes C; ids uint32[n_rows]: the class of every row; first uint32[C]: a class's first row; sizes uint32[C]: its rows;
+    patterns uint64[C, W]: ordinal j of the list = bit j & 63 of word j >> 6; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_classes, ids, first, sizes, patterns, kernel_ms, algo_bytes):
+        self.n_classes, self.ids, self.first, self.sizes, self.patterns = n_classes, ids, first, sizes, patterns
+        self.kernel_ms, self.algo_bytes = kernel_ms, algo_bytes
+
+
+class ColorsResult:
+    def __init__(self, ctx, h, n_rows, n_use):
+        self._ctx, self._h, self._rows, self._w = ctx, h, n_rows, (n_use + 63) // 64
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_colors_result_wait(self._h), "kmx_colors_result_wait")
+
+    def n_classes(self):
+        return _lib.kmx_colors_result_n_classes(self._h)
+
+    def ids_dev(self):
+        return _lib.kmx_colors_result_ids_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_colors_result_kernel_ms(self._h)
+
+    def kernel_parts_ms(self):
+        """(k_col_pack, clearing + k_col_claim, the numbering kernels) in ms; -1 where unavailable"""
+        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
+        self._ctx._check(_lib.kmx_colors_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_colors_result_kernel_parts_ms")
+        return a.value, b.value, c.value
+
+    def algo_bytes(self):
+        return _lib.kmx_colors_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        n = self.n_classes()
+        ids, first, sizes = np.zeros(self._rows, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        patterns = np.zeros((n, self._w), np.uint64)
+        self._ctx._check(_lib.kmx_colors_result_copy_ids(self._h, ids.ctypes.data, ids.size), "kmx_colors_result_copy_ids")
+        self._ctx._check(_lib.kmx_colors_result_copy_first(self._h, first.ctypes.data, first.size), "kmx_colors_result_copy_first")
+        self._ctx._check(_lib.kmx_colors_result_copy_sizes(self._h, sizes.ctypes.data, sizes.size), "kmx_colors_result_copy_sizes")
+        self._ctx._check(_lib.kmx_colors_result_copy_patterns(self._h, patterns.ctypes.data, patterns.size), "kmx_colors_result_copy_patterns")
+        return ColorsOutput(n, ids, first, sizes, patterns, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_colors_result_free(self._h)
             self._h = None
 
     def __del__(self):
