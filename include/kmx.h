@@ -40,6 +40,8 @@
  *                               samples hold, where each row is first met and first missed along the list, and per sample by recurrence
  *   kmx_colors_dev / _host      no counterpart either (the colour classes of Mantis, Bifrost, Fulgor, GGCAT; the bars of an UpSet plot): the
  *                               distinct sets of samples that occur as a row's presence pattern, the rows of each, every row's class
+ *   kmx_gram_dev / _host        no counterpart either (EIGENSTRAT / smartpca; the kinship matrix of a k-mer GWAS): the sample-by-sample
+ *                               table of shared rows, each row weighted by its recurrence class -- what the samples' PCs follow from
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -1026,6 +1028,86 @@ int       kmx_colors_result_kernel_parts_ms(kmx_colors_result* r, double* pack_m
  * (2 * n_rows * (8 * W + 8)) + ids (4 * n_rows) + the class table (C * (8 + 8 * W)) */
 uint64_t  kmx_colors_result_algo_bytes(kmx_colors_result* r);
 void      kmx_colors_result_free(kmx_colors_result* r);
+
+/* ------------------------------------------------------------------- gram */
+
+/* The recurrence-weighted co-presence table of a matrix's samples (the integer part of the EIGENSTRAT / smartpca Gram matrix, the
+ * kinship matrix of a k-mer GWAS; no counterpart in the kmtricks tree): T[i][j] = the sum over the rows that hold samples i and j of a
+ * weight that depends on the row's recurrence alone.  With p = rec / M and the weight 1 / (p (1 - p)) in fixed point, the centred and
+ * scaled Gram matrix of the samples follows from T and the tables of kmx_pan_* on the host (`kmx pca`).
+ * INPUT, as for kmx_pan_*: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ * `rows` needs no alignment.  The padding bits of a PA row never reach a result.  Keys are never read.
+ * PARAMETERS:
+ *   cols       pan's convention: a HOST array of M = n_use distinct input column indices, each < N, in any order; NULL is the identity
+ *              and requires M = N.  (The order of the list has no bearing on the table: it is indexed by input column.)
+ *   min_abund  a >= 1 (exactly 1 for PA): a sample holds a row from this count upwards
+ *   weights    a HOST array of M + 1 u32: the weight of recurrence class 0 ... M (copied by the call)
+ *   flags      none is defined: 0
+ * PER ROW:
+ *   present_c = (count[c] >= a) for COUNT, the bit of column c for PA, for every LISTED input column c
+ *   rec       = the number of listed columns present
+ * OUTPUT: table[N][N], u64, row-major, DEVICE memory, indexed by INPUT column.  For every pair of listed input columns i, j that are
+ * both present in a row the call ADDS weights[rec] to table[i][j]: both triangles are written, and the diagonal cell table[i][i] gets
+ * weights[rec] for every row that holds listed column i.  Cells with an unlisted i or j are never touched; rows of a class of weight 0
+ * add nothing.  The call adds into a table of the caller's, or into a zeroed one the result owns when the pointer is NULL.  Sums are
+ * modulo 2^64: keeping the sum of weights[rec_r] over all the rows added into one table below 2^64 is the caller's business (`kmx pca`
+ * chooses its fixed point from the spectrum for that).  Partitions and runs of rows accumulate in any order; n_rows = 0 adds nothing.
+ * EXAMPLE.  N = 3, cols NULL, a = 1, weights = (0, 6, 3, 0), five rows:
+ *   (1,0,0)  rec 1, weight 6: T00 += 6
+ *   (1,1,0)  rec 2, weight 3: T00, T01, T10, T11 += 3
+ *   (1,1,1)  rec 3, weight 0: nothing
+ *   (0,0,0)  rec 0, weight 0: nothing
+ *   (0,1,1)  rec 2, weight 3: T11, T12, T21, T22 += 3
+ *   table = ((9,3,0),(3,6,3),(0,3,3))
+ * IDENTITIES of one call's increments: (a) table[i][i] = the sum over R of weights[R] * shared[R][i] of kmx_pan_* on the same task;
+ * (b) with weights = (0,1,1,...,1) and a = 1 the table is inter of kmx_dist_* on the listed columns; (c) the sum of table[i][j] over
+ * the listed j = the sum over R of R * weights[R] * shared[R][i].
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols or n_use = 0; n_use > n_cols; a column index >= N or listed twice;
+ * cols = NULL with M != N; key_words 0 or > 4; a mode other than COUNT / PA; min_abund 0; min_abund > 1 with PA; flag bits; weights
+ * NULL.  KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT; n_rows > 2^32 - 256; a row of 4 GiB or more; N > 32768 (a table
+ * would be 8 GiB and more: the limit of kmx_dist_*).
+ * SCRATCH from the context's pool, per call, given back when the call has run; W = n_rows / 64 + min(M + 1, n_rows) bounds the 64-row
+ * words of the recurrence order (every class of a weight other than 0 starts on a word): the bit slab, 8 * 64 * ceil(N / 64) * W bytes;
+ * the order and the words' weights, 260 * W bytes; 4 bytes per input row (its recurrence); 16 * (M + 1) bytes of class counts, cursors
+ * and weights; a byte per input column or payload byte; for _host the uploaded rows.  The table the result owns (8 * N * N bytes) lives
+ * until the result is freed.  Send a body that does not fit in runs of rows. */
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_use;         /* M: samples of the list */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices (copied by the call), or NULL: the identity */
+  const uint32_t* weights;       /* HOST: M + 1 class weights (copied by the call) */
+  uint32_t        min_abund;     /* a */
+  uint32_t        flags;         /* 0 */
+  uint64_t*       table;         /* NULL, or a device table of N * N u64 to accumulate into */
+} kmx_gram_task;                 /* 64 bytes */
+
+typedef struct kmx_gram_result kmx_gram_result;
+
+/* _dev and _host as for kmx_pan_*: rows a DEVICE pointer, the kernels queued on the context's stream and the call back without waiting;
+ * or a HOST pointer, uploaded on a stream of its own, the buffer free for reuse once _result_wait has returned.  cols and weights are
+ * host arrays in both; table is a device table in both and stays the caller's. */
+int kmx_gram_dev(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out);
+int kmx_gram_host(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out);
+int       kmx_gram_result_wait(kmx_gram_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t* kmx_gram_result_table_dev(kmx_gram_result* r);       /* the table as it stands: the result's own or the task's */
+int       kmx_gram_result_copy_table(kmx_gram_result* r, uint64_t* host_dst, uint64_t dst_entries);     /* N * N entries */
+/* duration in ms of the call's kernels, the clearing of the table the result owns included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_gram_result_kernel_ms(kmx_gram_result* r);
+/* the same interval in its parts: clearing + k_gram_score + k_gram_fold, k_gram_order, k_gram_slab, k_gram_pairs; any pointer may be
+ * NULL */
+int       kmx_gram_result_kernel_parts_ms(kmx_gram_result* r, double* score_ms, double* order_ms, double* slab_ms, double* pairs_ms);
+/* algorithmic bytes: the body read twice (2 * n_rows * row bytes) + 16 bytes per row (its recurrence and its place in the order, each
+ * written and read once) + the slab written and read once (2 * 8 * 64 * ceil(N / 64) * Wu, Wu the words the order takes: the sum over
+ * the classes of a weight other than 0 of ceil(rows of the class / 64)) + the table (8 * N * N) */
+uint64_t  kmx_gram_result_algo_bytes(kmx_gram_result* r);
+void      kmx_gram_result_free(kmx_gram_result* r);
 
 /* ------------------------------------------------------------------ count */
 

@@ -125,6 +125,15 @@ class KmxColorsTask(C.Structure):
 
 
 assert C.sizeof(KmxColorsTask) == 48
+
+
+class KmxGramTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("weights", C.c_void_p),
+                ("min_abund", C.c_uint32), ("flags", C.c_uint32), ("table", C.c_void_p)]
+
+
+assert C.sizeof(KmxGramTask) == 64
 E_INTERNAL = -6
 
 _vp = C.c_void_p
@@ -430,6 +439,20 @@ _lib.kmx_colors_result_free.argtypes = [_vp]
 COLORS_EXPORTS = ["kmx_colors_dev", "kmx_colors_host", "kmx_colors_result_wait", "kmx_colors_result_n_classes", "kmx_colors_result_ids_dev",
                   "kmx_colors_result_copy_ids", "kmx_colors_result_copy_first", "kmx_colors_result_copy_sizes", "kmx_colors_result_copy_patterns",
                   "kmx_colors_result_kernel_ms", "kmx_colors_result_kernel_parts_ms", "kmx_colors_result_algo_bytes", "kmx_colors_result_free"]
+_lib.kmx_gram_dev.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
+_lib.kmx_gram_host.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
+_lib.kmx_gram_result_wait.argtypes = [_vp]
+_lib.kmx_gram_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_gram_result_algo_bytes.argtypes = [_vp]
+_lib.kmx_gram_result_copy_table.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_gram_result_table_dev.restype = _vp
+_lib.kmx_gram_result_table_dev.argtypes = [_vp]
+_lib.kmx_gram_result_kernel_ms.restype = C.c_double
+_lib.kmx_gram_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_gram_result_kernel_parts_ms.argtypes = [_vp] + [C.POINTER(C.c_double)] * 4
+_lib.kmx_gram_result_free.argtypes = [_vp]
+GRAM_EXPORTS = ["kmx_gram_dev", "kmx_gram_host", "kmx_gram_result_wait", "kmx_gram_result_table_dev", "kmx_gram_result_copy_table",
+                "kmx_gram_result_kernel_ms", "kmx_gram_result_kernel_parts_ms", "kmx_gram_result_algo_bytes", "kmx_gram_result_free"]
 PAN_EXPORTS = ["kmx_pan_dev", "kmx_pan_host", "kmx_pan_result_wait", "kmx_pan_result_spectrum_dev", "kmx_pan_result_shared_dev",
                "kmx_pan_result_copy_spectrum", "kmx_pan_result_copy_shared", "kmx_pan_result_kernel_ms", "kmx_pan_result_kernel_parts_ms",
                "kmx_pan_result_algo_bytes", "kmx_pan_result_free"]
@@ -1199,6 +1222,37 @@ class Context:
         return self._finish(ColorsResult(self, res, n_rows, n_use), keep)
 
     @staticmethod
+    def _gram_task(rows, n_rows, n_cols, key_words, mode, weights, cols, min_abund, table_dev):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = n_cols if c is None else len(c)
+        w = np.ascontiguousarray(weights, dtype=np.uint32).reshape(-1)
+        if len(w) != n_use + 1:
+            raise ValueError(f"{len(w)} class weights for {n_use} listed columns: M + 1 are needed")
+        t = KmxGramTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None, w.ctypes.data,
+                        min_abund, 0, table_dev)
+        return t, (c, w)      # (the arrays are kept alive by the caller until the call has copied them)
+
+    def gram(self, body, n_rows, n_cols, key_words, mode, weights, cols=None, min_abund=1, table_dev=None, keep=False):
+        """kmx_gram_host: body as for pan; weights: M + 1 uint32, the weight of a row by the number of listed samples that hold it; cols:
+        the listed input columns (None: all); table_dev: None (the result owns a zeroed table) or a device pointer to a uint64 table
+        [n_cols, n_cols] the call adds to.
+        -> GramOutput (numpy copies), or with keep the GramResult itself (the table left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, alive = self._gram_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, weights, cols, min_abund, table_dev)
+        res = _vp()
+        self._check(_lib.kmx_gram_host(self._h, C.byref(t), C.byref(res)), "kmx_gram_host")
+        r = GramResult(self, res, n_cols)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def gram_dev(self, rows_dev, n_rows, n_cols, key_words, mode, weights, cols=None, min_abund=1, table_dev=None, keep=False):
+        """kmx_gram_dev: rows_dev a device pointer to n_rows rows (weights and cols stay host arrays).  -> as gram"""
+        t, alive = self._gram_task(rows_dev, n_rows, n_cols, key_words, mode, weights, cols, min_abund, table_dev)
+        res = _vp()
+        self._check(_lib.kmx_gram_dev(self._h, C.byref(t), C.byref(res)), "kmx_gram_dev")
+        return self._finish(GramResult(self, res, n_cols), keep)
+
+    @staticmethod
     def _block_row_bytes(key_words, mode, n_cols, count_bytes):
         return key_words * 8 + (n_cols * count_bytes if mode == MODE_COUNT else (n_cols + 7) // 8)
 
@@ -1494,6 +1548,54 @@ class PanResult:
     def free(self):
         if self._h:
             _lib.kmx_pan_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class GramOutput:
+    """table uint64[n_cols, n_cols]: the class weights summed over the rows that hold both samples (the table the call added to, when
+    one was given); kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, table, kernel_ms, algo_bytes):
+        self.table, self.kernel_ms, self.algo_bytes = table, kernel_ms, algo_bytes
+
+
+class GramResult:
+    def __init__(self, ctx, h, n_cols):
+        self._ctx, self._h, self._n = ctx, h, n_cols
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_gram_result_wait(self._h), "kmx_gram_result_wait")
+
+    def table_dev(self):
+        return _lib.kmx_gram_result_table_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_gram_result_kernel_ms(self._h)
+
+    def kernel_parts_ms(self):
+        """(clearing + k_gram_score + k_gram_fold, k_gram_order, k_gram_slab, k_gram_pairs) in ms; -1 where unavailable"""
+        p = [C.c_double(-1) for _ in range(4)]
+        self._ctx._check(_lib.kmx_gram_result_kernel_parts_ms(self._h, *[C.byref(x) for x in p]), "kmx_gram_result_kernel_parts_ms")
+        return tuple(x.value for x in p)
+
+    def algo_bytes(self):
+        return _lib.kmx_gram_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        table = np.zeros((self._n, self._n), np.uint64)
+        self._ctx._check(_lib.kmx_gram_result_copy_table(self._h, table.ctypes.data, table.size), "kmx_gram_result_copy_table")
+        return GramOutput(table, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_gram_result_free(self._h)
             self._h = None
 
     def __del__(self):
