@@ -42,6 +42,8 @@
  *                               distinct sets of samples that occur as a row's presence pattern, the rows of each, every row's class
  *   kmx_gram_dev / _host        no counterpart either (EIGENSTRAT / smartpca; the kinship matrix of a k-mer GWAS): the sample-by-sample
  *                               table of shared rows, each row weighted by its recurrence class -- what the samples' PCs follow from
+ *   kmx_assoc_dev / _host       no counterpart either (kmdiff's and EIGENSTRAT's corrected test, a k-mer GWAS): the rows whose presence
+ *                               pattern is associated with a phenotype once covariates (the PCs) are projected out, kept in file order
  *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -1108,6 +1110,110 @@ int       kmx_gram_result_kernel_parts_ms(kmx_gram_result* r, double* score_ms, 
  * the classes of a weight other than 0 of ceil(rows of the class / 64)) + the table (8 * N * N) */
 uint64_t  kmx_gram_result_algo_bytes(kmx_gram_result* r);
 void      kmx_gram_result_free(kmx_gram_result* r);
+
+/* ------------------------------------------------------------------ assoc */
+
+/* The structure-corrected association test of a matrix's rows (what kmdiff, EIGENSTRAT and a k-mer GWAS run once the samples' principal
+ * components are known; no counterpart in the kmtricks tree): a phenotype -- case/control or quantitative -- is regressed on each row's
+ * presence pattern with the covariates in the model.  The covariates are projected out of both sides: with Q an orthonormal basis of the
+ * covariates (intercept included), y~ the phenotype's residual and x a row's 0/1 pattern, the score statistic is
+ * (M - q) (x.y~)^2 / (|y~|^2 (|x|^2 - |Q'x|^2)).  The caller gives y~ and Q's columns in fixed point, so the per-row sums are exact
+ * integers and the statistic uses + - * / on doubles alone (`kmx assoc`).
+ * INPUT, as for kmx_pan_* / kmx_gram_*: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples:
+ *   key_words 1 ... 4, KMX_MODE_COUNT  a row is 8 * key_words key bytes, then N u32 counts
+ *   key_words 1 ... 4, KMX_MODE_PA     a row is the key, then ceil(N / 8) bytes, column i = bit i & 7 of byte i >> 3
+ * `rows` needs no alignment.  The padding bits of a PA row never reach a result.  Keys are never read, only moved.
+ * PARAMETERS:
+ *   cols       pan's convention: a HOST array of M = n_use distinct input column indices, each < N, in any order; NULL is the identity
+ *              and requires M = N
+ *   min_abund  a >= 1 (exactly 1 for PA): a sample holds a row from this count upwards
+ *   n_vec      V, 1 ... 32
+ *   vecs       a HOST array of M * V int32_t, vecs[m * V + j] the value of vector j for the m-th listed sample (copied by the call).
+ *              Vector 0 is the phenotype with the covariates projected out; vectors 1 ... V - 1 are an orthonormal basis of the
+ *              covariates, intercept included.  The call does not check that meaning: the definition below is over the integers as given.
+ *   frac_bits  F, 0 ... 62; sc = 2^-F
+ *   gain       double, finite, > 0
+ *   vmin       double, >= 0
+ *   threshold  double, not NaN, >= 0; +inf keeps nothing
+ *   min_rec, max_rec   u32
+ *   flags      none is defined: 0
+ * PER ROW:
+ *   present_c = (count[c] >= a) for COUNT, the bit of column c for PA, for every LISTED input column c
+ *   rec       = the number of listed columns present
+ *   s_j (i64) = the sum over the present listed samples m of vecs[m][j]
+ * and then in IEEE double with no fused multiply-add, the operations and their order exactly these:
+ *   u    = (double)s_0 * sc
+ *   h    = 0; for j = 1 ... V-1 in ascending order: a = (double)s_j * sc; h = h + a * a
+ *   v    = (double)rec - h
+ *   if v > vmin:  beta = u / v;  stat = (gain * (u * u)) / v
+ *   else:         beta = 0;      stat = 0
+ * A row is KEPT iff min_rec <= rec <= max_rec and stat >= threshold.
+ * OUTPUTS, the shape of kmx_diff_*: the kept rows whole, in the input's order (a valid body of the same row size); one kmx_assoc_rec per
+ * kept row in the same order; the count of kept rows.
+ * EXAMPLE.  N = M = 4, cols NULL, a = 1, V = 2, F = 2, gain = 3, vmin = 0.25, vecs rows (-2, 2), (-2, 2), (2, 2), (2, 2) -- the
+ * phenotype (0, 0, 1, 1) centred, and the intercept 1/2 each:
+ *   row (0,0,1,1)  rec 2, s0 =  4, u = 1,   s1 = 4, h = 1,    v = 1            stat = 3, beta = 1
+ *   row (1,1,1,1)  rec 4, s0 =  0, u = 0,   s1 = 8, h = 4,    v = 0 <= vmin    stat = 0, beta = 0
+ *   row (1,0,1,0)  rec 2, s0 =  0, u = 0,   s1 = 4, h = 1,    v = 1            stat = 0, beta = 0
+ *   row (0,0,0,1)  rec 1, s0 =  2, u = 0.5, s1 = 2, h = 0.25, v = 0.75         stat = 1, beta = the double nearest 2/3
+ * With threshold 1.0 rows 0 and 3 are kept, in that order.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols or n_use = 0; n_use > n_cols; a column index >= N or listed twice;
+ * cols = NULL with M != N; key_words 0 or > 4; a mode other than COUNT / PA; min_abund 0; min_abund > 1 with PA; V = 0 or V > 32; vecs
+ * NULL; F > 62; a vector whose sum of |entries| is 2^53 or more ((double)s_j must be exact); gain not finite or <= 0; vmin negative or
+ * NaN; a NaN or negative threshold; flag bits.  KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT; n_rows > 2^32 - 256 (the
+ * placement tiles are the filter's: 256 rows); a row of 4 GiB or more.  n_rows = 0 yields nothing.
+ * SCRATCH from the context's pool, per call: a 4-byte keep word and a 32-byte record slot per input row, a 4-byte counter per 256 rows,
+ * 40 bytes of the call's scalars, the vector table (4 bytes x N rounded up to 8 x V rounded up to one of 1, 2, 4, 8, 12, 16, 24, 32) and a byte per input column or
+ * payload byte -- all given back when the call has run; the outputs are sized for every row kept (n_rows * row bytes + 16, and 32 *
+ * n_rows) and live until the result is freed; for the _host calls the uploaded rows.  Send a body that does not fit in runs of rows. */
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_use;         /* M: samples of the list */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices (copied by the call), or NULL: the identity */
+  const int32_t*  vecs;          /* HOST: M * V entries, vecs[m * V + j] (copied by the call) */
+  uint32_t        n_vec;         /* V: 1 ... 32 */
+  uint32_t        frac_bits;     /* F: 0 ... 62 */
+  uint32_t        min_abund;     /* a */
+  uint32_t        flags;         /* 0 */
+  double          gain;
+  double          vmin;
+  double          threshold;     /* a kept row has stat >= threshold */
+  uint32_t        min_rec;       /* ... and min_rec <= rec <= max_rec */
+  uint32_t        max_rec;
+} kmx_assoc_task;                /* 96 bytes */
+
+typedef struct {
+  double   stat;
+  double   beta;
+  int64_t  s0;
+  uint32_t rec;
+  uint32_t row;          /* index in the input */
+} kmx_assoc_rec;         /* 32 bytes */
+
+typedef struct kmx_assoc_result kmx_assoc_result;
+
+/* _dev and _host as for kmx_diff_*: rows a DEVICE pointer, the kernels queued on the context's stream and the call back without waiting;
+ * or a HOST pointer, uploaded on a stream of its own, the buffer free for reuse once _result_wait has returned.  cols and vecs are host
+ * arrays in both. */
+int kmx_assoc_dev(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out);
+int kmx_assoc_host(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out);
+int       kmx_assoc_result_wait(kmx_assoc_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t  kmx_assoc_result_rows(kmx_assoc_result* r);                /* kept rows */
+uint64_t  kmx_assoc_result_row_bytes(const kmx_assoc_result* r);
+uint64_t  kmx_assoc_result_body_bytes(kmx_assoc_result* r);          /* rows * row_bytes */
+const void*          kmx_assoc_result_body_dev(kmx_assoc_result* r); /* the kept rows, in HBM until the result is freed */
+int       kmx_assoc_result_copy_body(kmx_assoc_result* r, void* host_dst, uint64_t dst_bytes);
+const kmx_assoc_rec* kmx_assoc_result_recs_dev(kmx_assoc_result* r);
+int       kmx_assoc_result_copy_recs(kmx_assoc_result* r, kmx_assoc_rec* host_dst, uint64_t dst_entries);
+double    kmx_assoc_result_kernel_ms(kmx_assoc_result* r);           /* needs kmx_set_profiling(ctx, 1); < 0 if unavailable */
+/* algorithmic bytes: the body read once + the kept rows written + 32 bytes per kept row + the vectors (4 * N * V) */
+uint64_t  kmx_assoc_result_algo_bytes(kmx_assoc_result* r);
+void      kmx_assoc_result_free(kmx_assoc_result* r);
 
 /* ------------------------------------------------------------------ count */
 

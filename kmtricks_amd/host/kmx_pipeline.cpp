@@ -1336,6 +1336,7 @@ int kmx_select_main(int argc, char** argv);     // kmx_select.cpp: select
 int kmx_pan_main(int argc, char** argv);        // kmx_pan.cpp: pan
 int kmx_colors_main(int argc, char** argv);     // kmx_colors.cpp: colors
 int kmx_pca_main(int argc, char** argv);        // kmx_pca.cpp: pca
+int kmx_assoc_main(int argc, char** argv);      // kmx_assoc.cpp: assoc
 
 int main(int argc, char** argv)
 {
@@ -1347,6 +1348,7 @@ int main(int argc, char** argv)
   if (argc >= 2 && std::string(argv[1]) == "pan") { try { return kmx_pan_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "colors") { try { return kmx_colors_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "pca") { try { return kmx_pca_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "assoc") { try { return kmx_assoc_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

@@ -95,6 +95,19 @@ DIFF_REC = np.dtype([("sum_ctrl", "<u8"), ("sum_case", "<u8"), ("stat", "<f8"), 
 assert DIFF_REC.itemsize == 40
 
 
+class KmxAssocTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("vecs", C.c_void_p),
+                ("n_vec", C.c_uint32), ("frac_bits", C.c_uint32), ("min_abund", C.c_uint32), ("flags", C.c_uint32),
+                ("gain", C.c_double), ("vmin", C.c_double), ("threshold", C.c_double), ("min_rec", C.c_uint32), ("max_rec", C.c_uint32)]
+
+
+assert C.sizeof(KmxAssocTask) == 96
+# kmx_assoc_rec: 32 bytes
+ASSOC_REC = np.dtype([("stat", "<f8"), ("beta", "<f8"), ("s0", "<i8"), ("rec", "<u4"), ("row", "<u4")])
+assert ASSOC_REC.itemsize == 32
+
+
 class KmxSelectTask(C.Structure):
     _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_out", C.c_uint32),
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("min_abund", C.c_uint32),
@@ -390,6 +403,24 @@ DIFF_EXPORTS = ["kmx_colsums_dev", "kmx_colsums_host", "kmx_colsums_result_wait"
                 "kmx_diff_dev", "kmx_diff_host", "kmx_diff_result_wait", "kmx_diff_result_rows", "kmx_diff_result_row_bytes",
                 "kmx_diff_result_body_bytes", "kmx_diff_result_body_dev", "kmx_diff_result_copy_body", "kmx_diff_result_recs_dev",
                 "kmx_diff_result_copy_recs", "kmx_diff_result_kernel_ms", "kmx_diff_result_algo_bytes", "kmx_diff_result_free"]
+
+_lib.kmx_assoc_dev.argtypes = [_vp, C.POINTER(KmxAssocTask), C.POINTER(_vp)]
+_lib.kmx_assoc_host.argtypes = [_vp, C.POINTER(KmxAssocTask), C.POINTER(_vp)]
+_lib.kmx_assoc_result_wait.argtypes = [_vp]
+for _f in ("kmx_assoc_result_rows", "kmx_assoc_result_row_bytes", "kmx_assoc_result_body_bytes", "kmx_assoc_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+for _f in ("kmx_assoc_result_body_dev", "kmx_assoc_result_recs_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_assoc_result_copy_body.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_assoc_result_copy_recs.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_assoc_result_kernel_ms.restype = C.c_double
+_lib.kmx_assoc_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_assoc_result_free.argtypes = [_vp]
+ASSOC_EXPORTS = ["kmx_assoc_dev", "kmx_assoc_host", "kmx_assoc_result_wait", "kmx_assoc_result_rows", "kmx_assoc_result_row_bytes",
+                 "kmx_assoc_result_body_bytes", "kmx_assoc_result_body_dev", "kmx_assoc_result_copy_body", "kmx_assoc_result_recs_dev",
+                 "kmx_assoc_result_copy_recs", "kmx_assoc_result_kernel_ms", "kmx_assoc_result_algo_bytes", "kmx_assoc_result_free"]
 
 _lib.kmx_select_dev.argtypes = [_vp, C.POINTER(KmxSelectTask), C.POINTER(_vp)]
 _lib.kmx_select_host.argtypes = [_vp, C.POINTER(KmxSelectTask), C.POINTER(_vp)]
@@ -1136,6 +1167,44 @@ class Context:
         return self._finish(DiffResult(self, res), keep)
 
     @staticmethod
+    def _assoc_task(rows, n_rows, n_cols, key_words, mode, vecs, frac_bits, gain, vmin, threshold, cols, min_abund, min_rec, max_rec):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = n_cols if c is None else len(c)
+        v = None
+        n_vec = 0
+        if vecs is not None:
+            v = np.ascontiguousarray(vecs, dtype=np.int32)
+            if v.ndim != 2 or v.shape[0] != n_use:
+                raise ValueError(f"vecs of shape {v.shape} for {n_use} listed columns: expected (M, V)")
+            n_vec = v.shape[1]
+        t = KmxAssocTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None,
+                         v.ctypes.data if v is not None and v.size else None, n_vec, frac_bits, min_abund, 0, gain, vmin, threshold, min_rec, max_rec)
+        return t, (c, v)
+
+    def assoc(self, body, n_rows, n_cols, key_words, mode, vecs, frac_bits, gain, vmin, threshold, cols=None, min_abund=1, min_rec=0,
+              max_rec=2**32 - 1, keep=False):
+        """kmx_assoc_host: body as for diff; vecs: int32[M, V], row m the values of the V vectors for the m-th listed sample (vector 0
+        the residual phenotype, 1 ... V - 1 an orthonormal basis of the covariates), in fixed point with frac_bits fraction bits; a row
+        is kept when its recurrence over the listed columns lies in [min_rec, max_rec] and its statistic is at least threshold.
+        -> AssocOutput (numpy copies), or with keep the AssocResult itself (the kept rows and records left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, hold = self._assoc_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, vecs, frac_bits, gain, vmin, threshold, cols,
+                                   min_abund, min_rec, max_rec)
+        res = _vp()
+        self._check(_lib.kmx_assoc_host(self._h, C.byref(t), C.byref(res)), "kmx_assoc_host")
+        r = AssocResult(self, res)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def assoc_dev(self, rows_dev, n_rows, n_cols, key_words, mode, vecs, frac_bits, gain, vmin, threshold, cols=None, min_abund=1, min_rec=0,
+                  max_rec=2**32 - 1, keep=False):
+        """kmx_assoc_dev: rows_dev a device pointer to n_rows rows (vecs and cols stay host arrays).  -> as assoc"""
+        t, hold = self._assoc_task(rows_dev, n_rows, n_cols, key_words, mode, vecs, frac_bits, gain, vmin, threshold, cols, min_abund, min_rec, max_rec)
+        res = _vp()
+        self._check(_lib.kmx_assoc_dev(self._h, C.byref(t), C.byref(res)), "kmx_assoc_dev")
+        return self._finish(AssocResult(self, res), keep)
+
+    @staticmethod
     def _select_task(rows, n_rows, n_cols, key_words, mode, cols, out_mode, min_abund, min_rec, max_rec, zero_below):
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
         n_out = n_cols if c is None else len(c)
@@ -1492,6 +1561,62 @@ class DiffResult:
     def free(self):
         if self._h:
             _lib.kmx_diff_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class AssocOutput:
+    """body: the kept rows, whole and in the input's order (bytes); recs: one ASSOC_REC (kmx_assoc_rec, 32 bytes) per kept row in the
+    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+
+class AssocResult:
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_assoc_result_wait(self._h), "kmx_assoc_result_wait")
+
+    def rows(self):
+        return _lib.kmx_assoc_result_rows(self._h)
+
+    def row_bytes(self):
+        return _lib.kmx_assoc_result_row_bytes(self._h)
+
+    def body_bytes(self):
+        return _lib.kmx_assoc_result_body_bytes(self._h)
+
+    def body_dev(self):
+        return _lib.kmx_assoc_result_body_dev(self._h)
+
+    def recs_dev(self):
+        return _lib.kmx_assoc_result_recs_dev(self._h)
+
+    def kernel_ms(self):
+        return _lib.kmx_assoc_result_kernel_ms(self._h)
+
+    def algo_bytes(self):
+        return _lib.kmx_assoc_result_algo_bytes(self._h)
+
+    def output(self):
+        self.wait()
+        body = np.zeros(self.body_bytes(), np.uint8)
+        self._ctx._check(_lib.kmx_assoc_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_assoc_result_copy_body")
+        recs = np.zeros(self.rows(), ASSOC_REC)
+        self._ctx._check(_lib.kmx_assoc_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_assoc_result_copy_recs")
+        return AssocOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
+
+    def free(self):
+        if self._h:
+            _lib.kmx_assoc_result_free(self._h)
             self._h = None
 
     def __del__(self):
