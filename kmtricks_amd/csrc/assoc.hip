@@ -21,7 +21,7 @@
 // r * row_bytes + skip + b with r < n_rows and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads; nothing is
 // loaded in wider pieces than the piece that is tested (a byte for PA, a count's dword for COUNT) and nothing is rounded to an aligned
 // address.  The launch knobs of this file are its own: KMX_ASSOC_CUS and KMX_ASSOC_GRID.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,7 +39,6 @@ constexpr u32 AS_LOADS_PA = 4;            // ... PA: every row is eight ballots
 constexpr u32 AS_LOADS = 8;               // rows whose loads a lane has in flight before the first ballot
 
 typedef long long i64;
-struct __attribute__((packed, aligned(1))) ADword { u32 v; };      // a dword at any address: one global_load_dword
 
 struct AssocPrm { double sc, gain, vmin, thr; u32 min_rec, max_rec; };      // the scalars of a call, in device memory
 struct AssocRec { double stat, beta; i64 s0; u32 rec, row; };      // kmx_assoc_rec
@@ -94,7 +93,7 @@ void k_assoc_score(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 s
 #pragma unroll
           for (u32 k = 0; k < AS_LOADS; k++) {
             x[k] = 0;      // (below a: a >= 1)
-            if (m && r0 + k < nr) x[k] = reinterpret_cast<const ADword*>(p + (u64)(r0 + k) * row_bytes)->v;
+            if (m && r0 + k < nr) x[k] = reinterpret_cast<const UDword*>(p + (u64)(r0 + k) * row_bytes)->v;
           }
 #pragma unroll
           for (u32 k = 0; k < AS_LOADS; k++) {      // (every lane of the wave goes round)
@@ -200,105 +199,66 @@ static u32 as_vp(u32 V)
   for (u32 s : steps) if (V <= s) return s;
   return 32;
 }
-// KMX_ASSOC_CUS=c: the CU count the launches plan for, 1 <= c <= the device's (it may only lower the count)
-static u32 as_cus(int n_cu)
-{
-  const long c = kmx_env_int("KMX_ASSOC_CUS"), n = std::max(n_cu, 1);
-  return (u32)(c >= 1 && c <= n ? c : n);
-}
-// KMX_ASSOC_GRID=g: the cap on the workgroups of a launch (every kernel here strides over its work), 1 <= g <= the built-in cap
-static u32 as_grid(u64 dflt)
-{
-  const long g = kmx_env_int("KMX_ASSOC_GRID");
-  return (u32)(g >= 1 && (u64)g <= dflt ? (u64)g : dflt);
-}
+static u32 as_cus(const kmx_ctx* ctx) { return (u32)std::max(kmx_env_cus("KMX_ASSOC_CUS", ctx), 1); }
+static u32 as_grid(u64 dflt) { return kmx_env_grid("KMX_ASSOC_GRID", dflt); }
 
 }  // namespace kmx
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_assoc_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_cols = 0, n_vec = 0;
-  u64 row_bytes = 0;
-  u32 *d_keep = nullptr, *d_tiles = nullptr;
-  AssocRec *d_recs_all = nullptr, *d_recs = nullptr;
-  u8 *d_par = nullptr, *d_out = nullptr;
-  u8* h_par = nullptr;                  // page-locked: the call's scalars, the biased vector table, the list a byte a unit, on their way up
-  u32* h_tot = nullptr;                 // page-locked: kept rows
-  void* d_in = nullptr;                 // kmx_assoc_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_assoc_result : MatResult {
+  u32 n_vec = 0;
+  AssocRec* d_recs = nullptr;
+  u8* d_out = nullptr;
 };
 
 static int assoc_check(kmx_ctx* ctx, const kmx_assoc_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
+  const MatCheck c{ctx, who};
   const u32 N = T->n_cols, M = T->n_use, V = T->n_vec;
-  if (N == 0 || M == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column, and so has the list");
-  if (T->mode == KMX_MODE_BF || T->mode == KMX_MODE_BFC || T->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported: a Bloom row is a hash bit, its presence pattern is not a k-mer's (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->key_words < 1 || T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (T->min_abund == 0) return ctx->fail(KMX_E_INVAL, w + ": min_abund must be at least 1");
-  if (T->min_abund > 1 && T->mode == KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": min_abund above 1 needs counts");
-  if (T->flags) return ctx->fail(KMX_E_INVAL, w + ": unknown flag bits");
-  if (V == 0 || V > 32) return ctx->fail(KMX_E_INVAL, w + ": n_vec must be 1 ... 32");
-  if (!T->vecs) return ctx->fail(KMX_E_INVAL, w + ": null vecs");
-  if (T->frac_bits > 62) return ctx->fail(KMX_E_INVAL, w + ": frac_bits must be 0 ... 62");
-  if (!std::isfinite(T->gain) || !(T->gain > 0.0)) return ctx->fail(KMX_E_INVAL, w + ": the gain is a finite number above 0");
-  if (std::isnan(T->vmin) || T->vmin < 0.0) return ctx->fail(KMX_E_INVAL, w + ": vmin is a number at or above 0");
-  if (std::isnan(T->threshold) || T->threshold < 0.0) return ctx->fail(KMX_E_INVAL, w + ": the threshold is a number at or above 0");
-  if (M > N) return ctx->fail(KMX_E_INVAL, w + ": more listed columns than input columns");
-  if (!T->cols && M != N) return ctx->fail(KMX_E_INVAL, w + ": cols = NULL is the identity and needs n_use = n_cols");
-  *row_bytes = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * N : ((u64)N + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (T->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  if (T->cols) {
-    std::vector<u32> s(T->cols, T->cols + M);
-    std::sort(s.begin(), s.end());
-    if (s.back() >= N) return ctx->fail(KMX_E_INVAL, w + ": a column index at or above n_cols");
-    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return ctx->fail(KMX_E_INVAL, w + ": a column is listed twice");
-  }
+  int rc;
+  if ((rc = c.n_cols(N, M, "list")) || (rc = c.no_bloom(T->mode, ": a Bloom row is a hash bit, its presence pattern is not a k-mer's")) || (rc = c.mode(T->mode)) ||
+      (rc = c.key_words(T->key_words)) || (rc = c.min_abund(T->min_abund, T->mode)) || (rc = c.flags(T->flags, 0))) return rc;
+  if (V == 0 || V > 32) return c.no(KMX_E_INVAL, ": n_vec must be 1 ... 32");
+  if (!T->vecs) return c.no(KMX_E_INVAL, ": null vecs");
+  if (T->frac_bits > 62) return c.no(KMX_E_INVAL, ": frac_bits must be 0 ... 62");
+  if (!std::isfinite(T->gain) || !(T->gain > 0.0)) return c.no(KMX_E_INVAL, ": the gain is a finite number above 0");
+  if (std::isnan(T->vmin) || T->vmin < 0.0) return c.no(KMX_E_INVAL, ": vmin is a number at or above 0");
+  if (std::isnan(T->threshold) || T->threshold < 0.0) return c.no(KMX_E_INVAL, ": the threshold is a number at or above 0");
+  if ((rc = c.list_fits(M, N, "listed")) || (rc = c.identity(T->cols, M, N, "n_use"))) return rc;
+  *row_bytes = MatCheck::row_bytes(T->key_words, T->mode, N);
+  if ((rc = c.row_fits(*row_bytes)) || (rc = c.n_rows(T->n_rows)) || (rc = c.rows(T->n_rows, T->rows)) || (rc = c.col_list(T->cols, M, N))) return rc;
   // (double)s_j must be exact whichever samples are present: the sum of a vector's magnitudes stays below 2^53
   for (u32 j = 0; j < V; j++) {
     u64 sum = 0;      // (M < 2^32 entries below 2^31 + 1: no wrap)
     for (u64 m = 0; m < M; m++) { const i64 e = T->vecs[m * V + j]; sum += (u64)(e < 0 ? -e : e); }
-    if (sum >= (1ull << 53)) return ctx->fail(KMX_E_INVAL, w + ": the magnitudes of vector " + std::to_string(j) + " sum to 2^53 or more: its sums would not be exact in a double");
+    if (sum >= (1ull << 53)) return c.no(KMX_E_INVAL, ": the magnitudes of vector " + std::to_string(j) + " sum to 2^53 or more: its sums would not be exact in a double");
   }
   return KMX_OK;
 }
 
-static void assoc_release(kmx_assoc_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keep, R->d_tiles, R->d_recs_all, R->d_recs, R->d_par, R->d_out, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_par); c->hfree(R->h_tot);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
+// what a score launch takes besides its grid
+struct AssocArgs { const u8* rows; u32 n_rows; u64 row_bytes; u32 skip, n_cols; const u8* lst; const u32* vt; u32 min_abund; const AssocPrm* prm; u32* keep; AssocRec* recs_all; u32* tiles; };
 
 template <bool COUNT, int VP>
-static void assoc_launch_score(u32 grid, hipStream_t st, const kmx_assoc_task* T, const kmx_assoc_result* R, u32 skip, const u8* d_lst, const u32* d_vt, const AssocPrm* prm)
+static void assoc_launch_score(u32 grid, hipStream_t st, const AssocArgs& a)
 {
-  hipLaunchKernelGGL((k_assoc_score<COUNT, VP>), dim3(grid), dim3(64), 0, st, (const u8*)T->rows, R->n_rows, R->row_bytes, skip, T->n_cols, d_lst, d_vt,
-                     T->min_abund, prm, R->d_keep, R->d_recs_all, R->d_tiles);
+  hipLaunchKernelGGL((k_assoc_score<COUNT, VP>), dim3(grid), dim3(64), 0, st, a.rows, a.n_rows, a.row_bytes, a.skip, a.n_cols, a.lst, a.vt,
+                     a.min_abund, a.prm, a.keep, a.recs_all, a.tiles);
 }
 template <bool COUNT>
-static void assoc_launch_vp(u32 VP, u32 grid, hipStream_t st, const kmx_assoc_task* T, const kmx_assoc_result* R, u32 skip, const u8* d_lst, const u32* d_vt, const AssocPrm* prm)
+static void assoc_launch_vp(u32 VP, u32 grid, hipStream_t st, const AssocArgs& a)
 {
   switch (VP) {
-    case 1: assoc_launch_score<COUNT, 1>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 2: assoc_launch_score<COUNT, 2>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 4: assoc_launch_score<COUNT, 4>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 8: assoc_launch_score<COUNT, 8>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 12: assoc_launch_score<COUNT, 12>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 16: assoc_launch_score<COUNT, 16>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    case 24: assoc_launch_score<COUNT, 24>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
-    default: assoc_launch_score<COUNT, 32>(grid, st, T, R, skip, d_lst, d_vt, prm); break;
+    case 1: assoc_launch_score<COUNT, 1>(grid, st, a); break;
+    case 2: assoc_launch_score<COUNT, 2>(grid, st, a); break;
+    case 4: assoc_launch_score<COUNT, 4>(grid, st, a); break;
+    case 8: assoc_launch_score<COUNT, 8>(grid, st, a); break;
+    case 12: assoc_launch_score<COUNT, 12>(grid, st, a); break;
+    case 16: assoc_launch_score<COUNT, 16>(grid, st, a); break;
+    case 24: assoc_launch_score<COUNT, 24>(grid, st, a); break;
+    default: assoc_launch_score<COUNT, 32>(grid, st, a); break;
   }
 }
 
@@ -306,16 +266,17 @@ static void assoc_launch_vp(u32 VP, u32 grid, hipStream_t st, const kmx_assoc_ta
 static int assoc_queue(kmx_ctx* ctx, const kmx_assoc_task* T, kmx_assoc_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, M = T->n_use, V = T->n_vec, VP = as_vp(V), skip = 8 * T->key_words, n_rows = R->n_rows, tiles = filter_tiles(n_rows);
+  const u32 N = T->n_cols, M = T->n_use, V = R->n_vec = T->n_vec, VP = as_vp(V), skip = 8 * T->key_words, n_rows = (u32)R->n_rows, tiles = filter_tiles(n_rows);
   const bool count = T->mode == KMX_MODE_COUNT;
   const u32 units = count ? N : (u32)(((u64)N + 7) / 8);
   const u64 NR = ((u64)N + 7) / 8 * 8;      // the table's rows: PA walks whole payload bytes
   const u64 vt_bytes = 4 * NR * VP, par_bytes = sizeof(AssocPrm) + vt_bytes + units;      // the scalars, the table, the list
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_par = (u8*)ctx->halloc(par_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_assoc: host allocation failed");
+  u8* h_par;      // page-locked: the call's scalars, the biased vector table, the list a byte a unit, on their way up
+  if (!(R->h_tot = (u32*)R->pin(64)) || !(h_par = (u8*)R->pin(par_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_assoc: host allocation failed");
   R->h_tot[0] = 0;
-  AssocPrm* h_prm = reinterpret_cast<AssocPrm*>(R->h_par);
-  u32* h_vt = reinterpret_cast<u32*>(R->h_par + sizeof(AssocPrm));
-  u8* h_lst = R->h_par + sizeof(AssocPrm) + vt_bytes;
+  AssocPrm* h_prm = reinterpret_cast<AssocPrm*>(h_par);
+  u32* h_vt = reinterpret_cast<u32*>(h_par + sizeof(AssocPrm));
+  u8* h_lst = h_par + sizeof(AssocPrm) + vt_bytes;
   h_prm->sc = std::ldexp(1.0, -(int)T->frac_bits); h_prm->gain = T->gain; h_prm->vmin = T->vmin; h_prm->thr = T->threshold;
   h_prm->min_rec = T->min_rec; h_prm->max_rec = T->max_rec;
   for (u64 i = 0; i < NR * VP; i++) h_vt[i] = 0x80000000u;      // the value 0
@@ -325,132 +286,56 @@ static int assoc_queue(kmx_ctx* ctx, const kmx_assoc_task* T, kmx_assoc_result* 
     for (u32 j = 0; j < V; j++) h_vt[(u64)c * VP + j] = (u32)T->vecs[(u64)m * V + j] ^ 0x80000000u;
     if (count) h_lst[c] = 1; else h_lst[c >> 3] |= (u8)(1u << (c & 7));
   }
-  R->d_keep = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_tiles = (u32*)ctx->dalloc(4ull * ((u64)tiles + 1));
-  R->d_recs_all = (AssocRec*)ctx->dalloc(sizeof(AssocRec) * (u64)n_rows);
-  R->d_recs = (AssocRec*)ctx->dalloc(sizeof(AssocRec) * (u64)n_rows);      // every row kept
-  R->d_out = (u8*)ctx->dalloc((u64)n_rows * R->row_bytes + 16);
-  R->d_par = (u8*)ctx->dalloc(par_bytes);
-  if (!R->d_keep || !R->d_tiles || !R->d_recs_all || !R->d_recs || !R->d_out || !R->d_par)
-    return ctx->fail(KMX_E_NOMEM, "kmx_assoc: device allocation failed (send the body in runs of rows)");
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_par, R->h_par, par_bytes, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_tiles, 0, 4ull * ((u64)tiles + 1), st));
+  u32* d_keep = (u32*)R->tmp(4ull * n_rows);
+  u32* d_tiles = (u32*)R->keep(4ull * ((u64)tiles + 1));
+  AssocRec* d_recs_all = (AssocRec*)R->tmp(sizeof(AssocRec) * (u64)n_rows);
+  R->d_recs = (AssocRec*)R->keep(sizeof(AssocRec) * (u64)n_rows);      // every row kept
+  R->d_out = (u8*)R->keep((u64)n_rows * R->row_bytes + 16);
+  u8* d_par = (u8*)R->tmp(par_bytes);
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_assoc: device allocation failed (send the body in runs of rows)");
+  KMX_HIP(ctx, hipMemcpyAsync(d_par, h_par, par_bytes, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_tiles, 0, 4ull * ((u64)tiles + 1), st));
   const u32 cap = as_grid(AS_MAX_GRID);
   if (n_rows) {
     const u64 groups = ((u64)n_rows + AS_GROUP - 1) / AS_GROUP;
-    const u32 grid = (u32)std::min<u64>(groups, std::min<u64>((u64)as_cus(ctx->n_cu) * AS_WGS_PER_CU, cap));
-    const AssocPrm* prm = reinterpret_cast<const AssocPrm*>(R->d_par);
-    const u32* d_vt = reinterpret_cast<const u32*>(R->d_par + sizeof(AssocPrm));
-    const u8* d_lst = R->d_par + sizeof(AssocPrm) + vt_bytes;
-    if (count) assoc_launch_vp<true>(VP, grid, st, T, R, skip, d_lst, d_vt, prm);
-    else assoc_launch_vp<false>(VP, grid, st, T, R, skip, d_lst, d_vt, prm);
+    const u32 grid = (u32)std::min<u64>(groups, std::min<u64>((u64)as_cus(ctx) * AS_WGS_PER_CU, cap));
+    const AssocArgs a{(const u8*)T->rows, n_rows, R->row_bytes, skip, N, d_par + sizeof(AssocPrm) + vt_bytes, reinterpret_cast<const u32*>(d_par + sizeof(AssocPrm)),
+                      T->min_abund, reinterpret_cast<const AssocPrm*>(d_par), d_keep, d_recs_all, d_tiles};
+    if (count) assoc_launch_vp<true>(VP, grid, st, a);
+    else assoc_launch_vp<false>(VP, grid, st, a);
     KMX_HIP(ctx, hipGetLastError());
   }
-  KMX_HIP(ctx, launch_filter_scan(R->d_tiles, tiles, st));
+  KMX_HIP(ctx, launch_filter_scan(d_tiles, tiles, st));
   if (n_rows) {
-    KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, R->d_keep, R->d_keep, R->d_tiles, R->d_out, st));
-    hipLaunchKernelGGL(k_assoc_place, dim3(std::min(tiles, cap)), dim3(AS_TILE), 0, st, (const u32*)R->d_keep, (const AssocRec*)R->d_recs_all, n_rows,
-                       (const u32*)R->d_tiles, R->d_recs);
+    KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, d_keep, d_keep, d_tiles, R->d_out, st));
+    hipLaunchKernelGGL(k_assoc_place, dim3(std::min(tiles, cap)), dim3(AS_TILE), 0, st, (const u32*)d_keep, (const AssocRec*)d_recs_all, n_rows,
+                       (const u32*)d_tiles, R->d_recs);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_tiles + tiles, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R, d_tiles + tiles);
 }
 
-static int assoc_call(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = assoc_check(ctx, task, who, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_assoc_result* R = new kmx_assoc_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->row_bytes = row_bytes; R->n_cols = task->n_cols; R->n_vec = task->n_vec;
-  kmx_assoc_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); assoc_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = assoc_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_assoc_dev(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_assoc_dev", "kmx_assoc", assoc_check, assoc_queue); }
+extern "C" int kmx_assoc_host(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_assoc_host", "kmx_assoc", assoc_check, assoc_queue); }
 
-extern "C" int kmx_assoc_dev(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out) { return assoc_call(ctx, task, out, false, "kmx_assoc_dev"); }
-extern "C" int kmx_assoc_host(kmx_ctx* ctx, const kmx_assoc_task* task, kmx_assoc_result** out) { return assoc_call(ctx, task, out, true, "kmx_assoc_host"); }
-
-extern "C" int kmx_assoc_result_wait(kmx_assoc_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_assoc: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; the kept rows and their records stay
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_keep); R->d_keep = nullptr;
-  c->dfree(R->d_recs_all); R->d_recs_all = nullptr;
-  c->dfree(R->d_par); R->d_par = nullptr;
-  c->dfree(R->d_in); R->d_in = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_assoc_result_rows(kmx_assoc_result* R) { return R && kmx_assoc_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" int kmx_assoc_result_wait(kmx_assoc_result* R) { return mat_wait(R); }
+extern "C" uint64_t kmx_assoc_result_rows(kmx_assoc_result* R) { return mat_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
 extern "C" uint64_t kmx_assoc_result_row_bytes(const kmx_assoc_result* R) { return R ? R->row_bytes : 0; }
 extern "C" uint64_t kmx_assoc_result_body_bytes(kmx_assoc_result* R) { return R ? kmx_assoc_result_rows(R) * R->row_bytes : 0; }
-extern "C" const void* kmx_assoc_result_body_dev(kmx_assoc_result* R) { return R && kmx_assoc_result_wait(R) == KMX_OK ? R->d_out : nullptr; }
-extern "C" const kmx_assoc_rec* kmx_assoc_result_recs_dev(kmx_assoc_result* R) { return R && kmx_assoc_result_wait(R) == KMX_OK ? (const kmx_assoc_rec*)R->d_recs : nullptr; }
-static int assoc_copy_out(kmx_assoc_result* R, void* dst, uint64_t dst_bytes, const void* src, u64 bytes)
-{
-  if (dst_bytes < bytes) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!bytes) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, bytes);
-}
+extern "C" const void* kmx_assoc_result_body_dev(kmx_assoc_result* R) { return mat_wait(R) == KMX_OK ? R->d_out : nullptr; }
+extern "C" const kmx_assoc_rec* kmx_assoc_result_recs_dev(kmx_assoc_result* R) { return mat_wait(R) == KMX_OK ? (const kmx_assoc_rec*)R->d_recs : nullptr; }
 extern "C" int kmx_assoc_result_copy_body(kmx_assoc_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_assoc_result_wait(R);
-  return rc != KMX_OK ? rc : assoc_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_assoc_result_body_bytes(R));
-}
+{ return R ? mat_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_assoc_result_body_bytes(R), 1) : KMX_E_INVAL; }
 extern "C" int kmx_assoc_result_copy_recs(kmx_assoc_result* R, kmx_assoc_rec* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_assoc_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < R->h_tot[0]) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  return assoc_copy_out(R, host_dst, ~0ull, R->d_recs, sizeof(AssocRec) * (u64)R->h_tot[0]);
-}
-extern "C" double kmx_assoc_result_kernel_ms(kmx_assoc_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_assoc_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_recs, kmx_assoc_result_rows(R), sizeof(AssocRec)) : KMX_E_INVAL; }
+extern "C" double kmx_assoc_result_kernel_ms(kmx_assoc_result* R) { return mat_kernel_ms(R); }
 extern "C" uint64_t kmx_assoc_result_algo_bytes(kmx_assoc_result* R)
 {
-  if (!R || kmx_assoc_result_wait(R) != KMX_OK) return 0;
-  return (u64)R->n_rows * R->row_bytes + (u64)R->h_tot[0] * (R->row_bytes + sizeof(AssocRec)) + 4ull * R->n_cols * R->n_vec;
+  if (mat_wait(R) != KMX_OK) return 0;
+  return R->n_rows * R->row_bytes + (u64)R->h_tot[0] * (R->row_bytes + sizeof(AssocRec)) + 4ull * R->n_cols * R->n_vec;
 }
-extern "C" void kmx_assoc_result_free(kmx_assoc_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  assoc_release(R);
-}
+extern "C" void kmx_assoc_result_free(kmx_assoc_result* R) { mat_free(R); }

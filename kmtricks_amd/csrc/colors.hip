@@ -24,7 +24,7 @@
 // and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads (c < N); nothing is rounded to an aligned address.
 // Every row index taken from the table, rep, minrow or first is tested < n_rows before it becomes an address.  The launch knobs of
 // this file are its own: KMX_COLORS_CUS, KMX_COLORS_GRID and KMX_COLORS_HASH_BITS.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -39,7 +39,6 @@ constexpr u32 CL_WAVES_PER_SIMD = 8;      // chunks of long lists are made small
 constexpr u32 CL_AHEAD = 4;              // k_col_pack: loads a lane has on their way before the ballots that need them
 constexpr u64 CL_SEED = 0x9E3779B97F4A7C15ull;
 
-struct __attribute__((packed, aligned(1))) CDword { u32 v; };      // a dword at any address: one global_load_dword
 static_assert(sizeof(kmx_colors_task) == 48, "kmx_colors_task is 48 bytes");
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
@@ -53,7 +52,7 @@ __device__ __forceinline__ u64 cl_shfl64(u64 v, int src)
 
 // what a lane loads for column c < N: its count, or the payload byte that holds its bit; and whether that makes the column present
 // (a value of 0 is "absent" in both modes: a >= 1)
-template <bool COUNT> __device__ __forceinline__ u32 cl_unit(const u8* q, u32 c) { return COUNT ? reinterpret_cast<const CDword*>(q + 4ull * c)->v : (u32)q[c >> 3]; }
+template <bool COUNT> __device__ __forceinline__ u32 cl_unit(const u8* q, u32 c) { return COUNT ? reinterpret_cast<const UDword*>(q + 4ull * c)->v : (u32)q[c >> 3]; }
 template <bool COUNT> __device__ __forceinline__ bool cl_present(u32 v, u32 c, u32 a) { return COUNT ? v >= a : (bool)((v >> (c & 7u)) & 1u); }
 
 // colt: the input column of every ordinal, M entries.  L: lanes of a row (a power of two <= 64, >= M when below 64); RW: rows of a wave's
@@ -230,19 +229,8 @@ void k_col_gather(const u64* __restrict__ pat, const u32* __restrict__ first, co
 }
 // ---- end of the kernels -------------------------------------------------------------------------------------------------------------
 
-static u32 cl_pow2_at_or_above(u64 x, u32 cap) { u32 p = 1; while (p < cap && p < x) p <<= 1; return p; }
-// KMX_COLORS_CUS=c: the CU count the launches plan for, 1 <= c <= the device's (it may only lower the count)
-static u32 cl_cus(const kmx_ctx* ctx)
-{
-  const long c = kmx_env_int("KMX_COLORS_CUS"), n = std::max(ctx->n_cu, 1);
-  return (u32)(c >= 1 && c <= n ? c : n);
-}
-// KMX_COLORS_GRID=g: the cap on the workgroups of a launch whose kernel strides over its work, 1 <= g <= the built-in cap
-static u32 cl_grid(u64 dflt)
-{
-  const long g = kmx_env_int("KMX_COLORS_GRID");
-  return (u32)(g >= 1 && (u64)g <= dflt ? (u64)g : dflt);
-}
+static u32 cl_cus(const kmx_ctx* ctx) { return (u32)std::max(kmx_env_cus("KMX_COLORS_CUS", ctx), 1); }
+static u32 cl_grid(u64 dflt) { return kmx_env_grid("KMX_COLORS_GRID", dflt); }
 // KMX_COLORS_HASH_BITS=b, 0 <= b <= 63: the low b bits of every signature stay, all the others are set
 static u64 cl_keep()
 {
@@ -263,198 +251,119 @@ static u64 cl_result_bytes(u64 n_rows, u64 M) { return n_rows * (12 + 8 * ((M + 
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_colors_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_cols = 0, n_use = 0, W = 0;
-  u64 row_bytes = 0;
-  u64 *d_pat = nullptr, *d_sig = nullptr, *d_patterns = nullptr;
-  u32 *d_colt = nullptr, *d_table = nullptr, *d_minrow = nullptr, *d_cnt = nullptr, *d_rep = nullptr, *d_rank = nullptr, *d_tiles = nullptr, *d_status = nullptr;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_colors_result : MatResult {      // h_tot: C and the status word on their way down
+  u32 n_use = 0, W = 0;
+  u64* d_patterns = nullptr;
   u32 *d_ids = nullptr, *d_first = nullptr, *d_size = nullptr;
-  u32* h_colt = nullptr;                // page-locked: the column table on its way up
-  u32* h_back = nullptr;                // page-locked: C and the status word on their way down
-  void* d_in = nullptr;                 // kmx_colors_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev[4] = {};      // ev: start, behind the pack, behind the claim, end
-  bool waited = false; int status = KMX_OK;
 };
 
 static int colors_check(kmx_ctx* ctx, const kmx_colors_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
+  const MatCheck c{ctx, who};
   const u32 N = T->n_cols, M = T->n_use;
-  if (N == 0 || M == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column, and so has the list");
-  if (T->mode == KMX_MODE_BF || T->mode == KMX_MODE_BFC || T->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported: a Bloom row is a hash bit, its sample set is not a k-mer's (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->key_words < 1 || T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (T->min_abund == 0) return ctx->fail(KMX_E_INVAL, w + ": min_abund must be at least 1");
-  if (T->min_abund > 1 && T->mode == KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": min_abund above 1 needs counts");
-  if (T->flags) return ctx->fail(KMX_E_INVAL, w + ": unknown flag bits");
-  if (M > N) return ctx->fail(KMX_E_INVAL, w + ": more listed columns than input columns");
-  if (!T->cols && M != N) return ctx->fail(KMX_E_INVAL, w + ": cols = NULL is the identity and needs n_use = n_cols");
-  *row_bytes = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * N : ((u64)N + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (T->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if (T->cols) {
-    std::vector<u32> s(T->cols, T->cols + M);
-    std::sort(s.begin(), s.end());
-    if (s.back() >= N) return ctx->fail(KMX_E_INVAL, w + ": a column index at or above n_cols");
-    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return ctx->fail(KMX_E_INVAL, w + ": a column is listed twice");
-  }
+  int rc;
+  if ((rc = c.n_cols(N, M, "list")) || (rc = c.no_bloom(T->mode, ": a Bloom row is a hash bit, its sample set is not a k-mer's")) || (rc = c.mode(T->mode)) ||
+      (rc = c.key_words(T->key_words)) || (rc = c.min_abund(T->min_abund, T->mode)) || (rc = c.flags(T->flags, 0)) || (rc = c.list_fits(M, N, "listed")) ||
+      (rc = c.identity(T->cols, M, N, "n_use"))) return rc;
+  *row_bytes = MatCheck::row_bytes(T->key_words, T->mode, N);
+  if ((rc = c.row_fits(*row_bytes)) || (rc = c.n_rows(T->n_rows)) || (rc = c.col_list(T->cols, M, N))) return rc;
   // the pool cannot give more than the device has
   size_t fr = 0, tot = 0;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) return ctx->fail(KMX_E_HIP, w + ": the device's memory size is not known");
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) return c.no(KMX_E_HIP, ": the device's memory size is not known");
   if (cl_scratch_bytes(T->n_rows, M) + cl_result_bytes(T->n_rows, M) > (u64)tot)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": scratch and result beyond the device's memory (send the body in runs of rows)");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  return KMX_OK;
-}
-
-static void colors_release(kmx_colors_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_pat, R->d_sig, R->d_patterns, R->d_colt, R->d_table, R->d_minrow, R->d_cnt, R->d_rep, R->d_rank, R->d_tiles, R->d_status,
-                    R->d_ids, R->d_first, R->d_size, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_colt); c->hfree(R->h_back);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev[0], R->ev[1], R->ev[2], R->ev[3]}) if (e) (void)hipEventDestroy(e);
-  delete R;
+    return c.no(KMX_E_UNSUPPORTED, ": scratch and result beyond the device's memory (send the body in runs of rows)");
+  return c.rows(T->n_rows, T->rows);
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
 static int colors_queue(kmx_ctx* ctx, const kmx_colors_task* T, kmx_colors_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, M = T->n_use, skip = 8 * T->key_words, n_rows = R->n_rows, W = R->W;
+  const u32 N = T->n_cols, M = R->n_use = T->n_use, skip = 8 * T->key_words, n_rows = (u32)R->n_rows, W = R->W = (u32)(((u64)M + 63) / 64);
   const bool count = T->mode == KMX_MODE_COUNT;
   const u64 n = n_rows, slots = cl_table_slots(n), tiles = cl_tiles(n);
-  if (!(R->h_colt = (u32*)ctx->halloc(4ull * M)) || !(R->h_back = (u32*)ctx->halloc(8))) return ctx->fail(KMX_E_NOMEM, "kmx_colors: host allocation failed");
-  for (u32 j = 0; j < M; j++) R->h_colt[j] = T->cols ? T->cols[j] : j;
-  R->h_back[0] = 0; R->h_back[1] = 0;
-  R->d_colt = (u32*)ctx->dalloc(4ull * M);
-  R->d_tiles = (u32*)ctx->dalloc(4 * (tiles + 1));
-  R->d_status = (u32*)ctx->dalloc(4);
-  bool ok = R->d_colt && R->d_tiles && R->d_status;
+  u32* h_colt;      // page-locked: the column table on its way up
+  if (!(h_colt = (u32*)R->pin(4ull * M)) || !(R->h_tot = (u32*)R->pin(8))) return ctx->fail(KMX_E_NOMEM, "kmx_colors: host allocation failed");
+  for (u32 j = 0; j < M; j++) h_colt[j] = T->cols ? T->cols[j] : j;
+  R->h_tot[0] = 0; R->h_tot[1] = 0;
+  u32* d_colt = (u32*)R->tmp(4ull * M);
+  u32* d_tiles = (u32*)R->tmp(4 * (tiles + 1));
+  u32* d_status = (u32*)R->tmp(4);
+  u64 *d_pat = nullptr, *d_sig = nullptr;
+  u32 *d_table = nullptr, *d_minrow = nullptr, *d_cnt = nullptr, *d_rep = nullptr, *d_rank = nullptr;
   if (n_rows) {
-    R->d_pat = (u64*)ctx->dalloc(8 * n * W); R->d_sig = (u64*)ctx->dalloc(8 * n); R->d_table = (u32*)ctx->dalloc(4 * slots);
-    R->d_minrow = (u32*)ctx->dalloc(4 * n); R->d_cnt = (u32*)ctx->dalloc(4 * n); R->d_rep = (u32*)ctx->dalloc(4 * n); R->d_rank = (u32*)ctx->dalloc(4 * n);
-    R->d_ids = (u32*)ctx->dalloc(4 * n); R->d_first = (u32*)ctx->dalloc(4 * n); R->d_size = (u32*)ctx->dalloc(4 * n); R->d_patterns = (u64*)ctx->dalloc(8 * n * W);
-    ok = ok && R->d_pat && R->d_sig && R->d_table && R->d_minrow && R->d_cnt && R->d_rep && R->d_rank && R->d_ids && R->d_first && R->d_size && R->d_patterns;
+    d_pat = (u64*)R->tmp(8 * n * W); d_sig = (u64*)R->tmp(8 * n); d_table = (u32*)R->tmp(4 * slots);
+    d_minrow = (u32*)R->tmp(4 * n); d_cnt = (u32*)R->tmp(4 * n); d_rep = (u32*)R->tmp(4 * n); d_rank = (u32*)R->tmp(4 * n);
+    R->d_ids = (u32*)R->keep(4 * n); R->d_first = (u32*)R->keep(4 * n); R->d_size = (u32*)R->keep(4 * n); R->d_patterns = (u64*)R->keep(8 * n * W);
   }
-  if (!ok) return ctx->fail(KMX_E_NOMEM, "kmx_colors: device allocation failed (send the body in runs of rows)");
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_colt, R->h_colt, 4ull * M, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    for (int i = 0; i < 4; i++) KMX_HIP(ctx, hipEventCreate(&R->ev[i]));
-    KMX_HIP(ctx, hipEventRecord(R->ev[0], st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_tiles, 0, 4 * (tiles + 1), st));
-  KMX_HIP(ctx, hipMemsetAsync(R->d_status, 0, 4, st));
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_colors: device allocation failed (send the body in runs of rows)");
+  KMX_HIP(ctx, hipMemcpyAsync(d_colt, h_colt, 4ull * M, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R, 4);      // ev: start, behind the pack, behind the claim, end
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_tiles, 0, 4 * (tiles + 1), st));
+  KMX_HIP(ctx, hipMemsetAsync(d_status, 0, 4, st));
   const u32 cus = cl_cus(ctx);
   const u32 tile_grid = (u32)std::min<u64>(std::max<u64>(tiles, 1), cl_grid(CL_MAX_GRID));
   if (n_rows) {
     // lists of 64 ordinals and more get a wave a row; their chunks shrink until the chip has CL_WAVES_PER_SIMD waves a SIMD to hide the loads
-    const u32 L = cl_pow2_at_or_above(M, 64);
-    u32 RW = 64;
-    if (L == 64) while (RW > 4 && n / RW < (u64)cus * 4 * CL_WAVES_PER_SIMD) RW >>= 1;
-    const u64 chunks = (n + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, cl_grid(std::min<u64>((u64)cus * CL_WGS_PER_CU, CL_MAX_GRID)));
+    const RowPlan p = mat_row_plan(M, n, cus, CL_WAVES_PER_SIMD);
+    const u32 grid = (u32)std::min<u64>((p.chunks + 3) / 4, cl_grid(std::min<u64>((u64)cus * CL_WGS_PER_CU, CL_MAX_GRID)));
     const u64 keep = cl_keep();
-    if (count) hipLaunchKernelGGL(k_col_pack<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW,
-                                  (const u32*)R->d_colt, T->min_abund, keep, R->d_pat, R->d_sig);
-    else hipLaunchKernelGGL(k_col_pack<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW,
-                            (const u32*)R->d_colt, T->min_abund, keep, R->d_pat, R->d_sig);
+    if (count) hipLaunchKernelGGL(k_col_pack<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW,
+                                  (const u32*)d_colt, T->min_abund, keep, d_pat, d_sig);
+    else hipLaunchKernelGGL(k_col_pack<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW,
+                            (const u32*)d_colt, T->min_abund, keep, d_pat, d_sig);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[1], st));
   if (n_rows) {
-    KMX_HIP(ctx, hipMemsetAsync(R->d_table, 0xFF, 4 * slots, st));
-    KMX_HIP(ctx, hipMemsetAsync(R->d_minrow, 0xFF, 4 * n, st));
-    KMX_HIP(ctx, hipMemsetAsync(R->d_cnt, 0, 4 * n, st));
-    hipLaunchKernelGGL(k_col_claim, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u64*)R->d_pat, (const u64*)R->d_sig, n_rows, W, R->d_table, slots - 1,
-                       R->d_minrow, R->d_cnt, R->d_rep, R->d_status);
+    KMX_HIP(ctx, hipMemsetAsync(d_table, 0xFF, 4 * slots, st));
+    KMX_HIP(ctx, hipMemsetAsync(d_minrow, 0xFF, 4 * n, st));
+    KMX_HIP(ctx, hipMemsetAsync(d_cnt, 0, 4 * n, st));
+    hipLaunchKernelGGL(k_col_claim, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u64*)d_pat, (const u64*)d_sig, n_rows, W, d_table, slots - 1,
+                       d_minrow, d_cnt, d_rep, d_status);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[2], st));
   if (n_rows) {
-    hipLaunchKernelGGL(k_col_flag, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)R->d_rep, (const u32*)R->d_minrow, n_rows, R->d_tiles);
+    hipLaunchKernelGGL(k_col_flag, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)d_rep, (const u32*)d_minrow, n_rows, d_tiles);
     KMX_HIP(ctx, hipGetLastError());
-    KMX_HIP(ctx, launch_filter_scan(R->d_tiles, (u32)tiles, st));
-    hipLaunchKernelGGL(k_col_number, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)R->d_rep, (const u32*)R->d_minrow, (const u32*)R->d_cnt, n_rows,
-                       (const u32*)R->d_tiles, R->d_rank, R->d_first, R->d_size);
+    KMX_HIP(ctx, launch_filter_scan(d_tiles, (u32)tiles, st));
+    hipLaunchKernelGGL(k_col_number, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)d_rep, (const u32*)d_minrow, (const u32*)d_cnt, n_rows,
+                       (const u32*)d_tiles, d_rank, R->d_first, R->d_size);
     KMX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_col_ids, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)R->d_rep, (const u32*)R->d_minrow, (const u32*)R->d_rank, n_rows, R->d_ids);
+    hipLaunchKernelGGL(k_col_ids, dim3(tile_grid), dim3(CL_TILE), 0, st, (const u32*)d_rep, (const u32*)d_minrow, (const u32*)d_rank, n_rows, R->d_ids);
     KMX_HIP(ctx, hipGetLastError());
     const u32 ggrid = (u32)std::min<u64>(std::max<u64>((n * W + CL_TILE - 1) / CL_TILE, 1), cl_grid(CL_MAX_GRID));
-    hipLaunchKernelGGL(k_col_gather, dim3(ggrid), dim3(CL_TILE), 0, st, (const u64*)R->d_pat, (const u32*)R->d_first, (const u32*)(R->d_tiles + tiles), n_rows, W,
+    hipLaunchKernelGGL(k_col_gather, dim3(ggrid), dim3(CL_TILE), 0, st, (const u64*)d_pat, (const u32*)R->d_first, (const u32*)(d_tiles + tiles), n_rows, W,
                        R->d_patterns);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[3], st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_back[0], R->d_tiles + tiles, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_back[1], R->d_status, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R, d_tiles + tiles, d_status);
 }
 
-static int colors_call(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = colors_check(ctx, task, who, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_colors_result* R = new kmx_colors_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->n_cols = task->n_cols; R->n_use = task->n_use; R->row_bytes = row_bytes;
-  R->W = (u32)(((u64)task->n_use + 63) / 64);
-  kmx_colors_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); colors_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = colors_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_colors_dev(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out) { return colors_call(ctx, task, out, false, "kmx_colors_dev"); }
-extern "C" int kmx_colors_host(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out) { return colors_call(ctx, task, out, true, "kmx_colors_host"); }
+extern "C" int kmx_colors_dev(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_colors_dev", "kmx_colors", colors_check, colors_queue); }
+extern "C" int kmx_colors_host(kmx_ctx* ctx, const kmx_colors_task* task, kmx_colors_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_colors_host", "kmx_colors", colors_check, colors_queue); }
 
 extern "C" int kmx_colors_result_wait(kmx_colors_result* R)
 {
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_colors: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; ids, first, size and patterns stay
-  kmx_ctx* c = R->ctx;
-  void** blocks[] = {(void**)&R->d_pat, (void**)&R->d_sig, (void**)&R->d_colt, (void**)&R->d_table, (void**)&R->d_minrow, (void**)&R->d_cnt, (void**)&R->d_rep,
-                     (void**)&R->d_rank, (void**)&R->d_tiles, (void**)&R->d_status, &R->d_in};
-  for (void** p : blocks) { c->dfree(*p); *p = nullptr; }
-  if (R->h_back[1] || R->h_back[0] > R->n_rows)
-    return R->status = c->fail(KMX_E_INTERNAL, "kmx_colors: a row found no slot within the table's probe bound");
-  return R->status = KMX_OK;
+  if (!R || R->waited) return mat_wait(R);
+  const int rc = mat_wait(R);
+  if (rc != KMX_OK) return rc;
+  if (R->h_tot[1] || R->h_tot[0] > R->n_rows)
+    return R->status = R->ctx->fail(KMX_E_INTERNAL, "kmx_colors: a row found no slot within the table's probe bound");
+  return KMX_OK;
 }
-extern "C" uint64_t kmx_colors_result_n_classes(kmx_colors_result* R) { return R && kmx_colors_result_wait(R) == KMX_OK ? R->h_back[0] : 0; }
-extern "C" const uint32_t* kmx_colors_result_ids_dev(kmx_colors_result* R) { return R && kmx_colors_result_wait(R) == KMX_OK ? R->d_ids : nullptr; }
+extern "C" uint64_t kmx_colors_result_n_classes(kmx_colors_result* R) { return kmx_colors_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" const uint32_t* kmx_colors_result_ids_dev(kmx_colors_result* R) { return kmx_colors_result_wait(R) == KMX_OK ? R->d_ids : nullptr; }
+// (kmx_colors_result_wait first: behind it mat_copy_out's own wait returns its status)
 static int colors_copy_out(kmx_colors_result* R, void* dst, uint64_t dst_entries, const void* src, u64 entries, u32 entry_bytes)
 {
   const int rc = kmx_colors_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!entries) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, entry_bytes * entries);
+  return rc != KMX_OK ? rc : mat_copy_out(R, dst, dst_entries, src, entries, entry_bytes);
 }
 extern "C" int kmx_colors_result_copy_ids(kmx_colors_result* R, uint32_t* host_dst, uint64_t dst_entries)
 { return R ? colors_copy_out(R, host_dst, dst_entries, R->d_ids, R->n_rows, 4) : KMX_E_INVAL; }
@@ -464,34 +373,16 @@ extern "C" int kmx_colors_result_copy_sizes(kmx_colors_result* R, uint32_t* host
 { return R ? colors_copy_out(R, host_dst, dst_entries, R->d_size, kmx_colors_result_n_classes(R), 4) : KMX_E_INVAL; }
 extern "C" int kmx_colors_result_copy_patterns(kmx_colors_result* R, uint64_t* host_dst, uint64_t dst_entries)
 { return R ? colors_copy_out(R, host_dst, dst_entries, R->d_patterns, kmx_colors_result_n_classes(R) * R->W, 8) : KMX_E_INVAL; }
-extern "C" double kmx_colors_result_kernel_ms(kmx_colors_result* R)
-{
-  if (!R || !R->ev[0] || !R->ev[3] || kmx_colors_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev[0], R->ev[3]) == hipSuccess ? (double)ms : -1.0;
-}
+extern "C" double kmx_colors_result_kernel_ms(kmx_colors_result* R) { return R && R->ev[0] && kmx_colors_result_wait(R) == KMX_OK ? mat_kernel_ms(R) : -1.0; }
 extern "C" int kmx_colors_result_kernel_parts_ms(kmx_colors_result* R, double* pack_ms, double* claim_ms, double* number_ms)
 {
-  double* o[3] = {pack_ms, claim_ms, number_ms};
-  for (double* p : o) if (p) *p = -1.0;
-  if (!R) return KMX_E_INVAL;
-  if (!R->ev[0] || !R->ev[3] || kmx_colors_result_wait(R) != KMX_OK) return KMX_OK;
-  for (int i = 0; i < 3; i++) {
-    float ms = 0;
-    if (o[i] && hipEventElapsedTime(&ms, R->ev[i], R->ev[i + 1]) == hipSuccess) *o[i] = (double)ms;
-  }
-  return KMX_OK;
+  if (R && R->ev[0]) (void)kmx_colors_result_wait(R);      // (without profiling nothing is waited for)
+  return mat_kernel_parts_ms(R, {pack_ms, claim_ms, number_ms});
 }
 extern "C" uint64_t kmx_colors_result_algo_bytes(kmx_colors_result* R)
 {
-  if (!R || kmx_colors_result_wait(R) != KMX_OK) return 0;
-  const u64 n = R->n_rows, C = R->h_back[0], W = R->W;
+  if (kmx_colors_result_wait(R) != KMX_OK) return 0;
+  const u64 n = R->n_rows, C = R->h_tot[0], W = R->W;
   return n * R->row_bytes + 2 * n * (8 * W + 8) + 4 * n + C * (8 + 8 * W);
 }
-extern "C" void kmx_colors_result_free(kmx_colors_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  colors_release(R);
-}
+extern "C" void kmx_colors_result_free(kmx_colors_result* R) { mat_free(R); }

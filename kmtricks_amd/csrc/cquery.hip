@@ -28,16 +28,14 @@ namespace kmx {
 
 constexpr u32 CQ_RUN = 128;               // records of a gather item: 128 x 2^31 fits a u64 sum, 128 a u32 hit counter
 
-struct __attribute__((packed, aligned(1))) CQDword { u32 v; };      // a dword at any address: one global_load_dword
-struct __attribute__((packed, aligned(1))) CQShort { u16 v; };      // two bytes at any address: one global_load_ushort
 
 // the w bytes (1 ... 8) at rp as one big-endian number, in pieces of 4, 2 and 1 bytes (w is the same in every lane: no divergence)
 __device__ __forceinline__ u64 cq_load_be(const u8* rp, u32 w)
 {
   u64 x = 0;
-  if (w == 8) { x = __builtin_bswap32(reinterpret_cast<const CQDword*>(rp)->v); rp += 4; w = 4; }
-  if (w & 4u) { x = (x << 32) | __builtin_bswap32(reinterpret_cast<const CQDword*>(rp)->v); rp += 4; }
-  if (w & 2u) { x = (x << 16) | __builtin_bswap16(reinterpret_cast<const CQShort*>(rp)->v); rp += 2; }
+  if (w == 8) { x = __builtin_bswap32(reinterpret_cast<const UDword*>(rp)->v); rp += 4; w = 4; }
+  if (w & 4u) { x = (x << 32) | __builtin_bswap32(reinterpret_cast<const UDword*>(rp)->v); rp += 4; }
+  if (w & 2u) { x = (x << 16) | __builtin_bswap16(reinterpret_cast<const UShort*>(rp)->v); rp += 2; }
   if (w & 1u) x = (x << 8) | rp[0];
   return x;
 }

@@ -17,7 +17,7 @@
 // Every load of a body byte is inside [rows, rows + n_rows * row_bytes) by construction: an address is rows + r * row_bytes + skip + b
 // with r < n_rows and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads; nothing is loaded in wider pieces
 // than the piece that is tested (a byte for PA, a count's dword for COUNT) and nothing is rounded to an aligned address.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -30,7 +30,6 @@ constexpr u32 DF_MAX_GRID = 1u << 18;     // workgroups of a launch: the kernels
 constexpr u32 DF_WAVES_PER_SIMD = 8;      // chunks of long rows are made small enough for this many waves a SIMD
 constexpr u32 CS_WGS_PER_CU = 8;          // workgroups k_colsums aims at
 
-struct __attribute__((packed, aligned(1))) FDword { u32 v; };      // a dword at any address: one global_load_dword
 
 struct DiffRec { u64 sum_ctrl, sum_case; double stat; u32 rec_ctrl, rec_case, row, over; };      // kmx_diff_rec
 static_assert(sizeof(DiffRec) == 40 && sizeof(kmx_diff_rec) == 40, "a record is 40 bytes");
@@ -51,7 +50,7 @@ void k_colsums(const u8* __restrict__ rows, u64 n_rows, u64 row_bytes, u32 skip,
     const u8* p = rows + skip + (COUNT ? 4ull * unit : (u64)unit);
     if (COUNT) {
       u64 acc = 0;
-      for (u64 r = r0 + sub; r < r1; r += RP) acc += reinterpret_cast<const FDword*>(p + r * row_bytes)->v;
+      for (u64 r = r0 + sub; r < r1; r += RP) acc += reinterpret_cast<const UDword*>(p + r * row_bytes)->v;
       if (acc) atomicAdd(&s_acc[u], acc);
     } else {
       const u32 keep = 8ull * unit + 8 <= N ? 0xFFu : (1u << (N - 8 * unit)) - 1u;      // the padding bits of the last byte
@@ -124,7 +123,7 @@ void k_diff_score(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 sk
         u32 i = 0;
         for (u64 un = u; un < units; un += L, i++) {
           if (COUNT) {
-            const u32 v = reinterpret_cast<const FDword*>(q + 4 * un)->v;
+            const u32 v = reinterpret_cast<const UDword*>(q + 4 * un)->v;
             const u32 gr = i < 16 ? (gp >> (2 * i)) & 3u : (u32)grp[un];
             const u64 nz = v != 0;
             if (gr == 0) { a0 += v; ar += nz; }
@@ -183,45 +182,27 @@ void k_diff_place(const u32* __restrict__ keep, const DiffRec* __restrict__ recs
   }
 }
 
-static u32 pow2_at_or_above(u64 x, u32 cap) { u32 p = 1; while (p < cap && p < x) p <<= 1; return p; }
-
 }  // namespace kmx
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-static int diff_check_body(kmx_ctx* ctx, const std::string& w, u32 key_words, u32 mode, u32 n_cols, const void* rows, u64 n_rows, u64* row_bytes)
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+static int diff_check_body(const MatCheck& c, u32 key_words, u32 mode, u32 n_cols, const void* rows, u64 n_rows, u64* row_bytes)
 {
-  if (n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
-  if (mode == KMX_MODE_BF || mode == KMX_MODE_BFC || mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (mode != KMX_MODE_COUNT && mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (key_words < 1 || key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  *row_bytes = 8ull * key_words + (mode == KMX_MODE_COUNT ? 4ull * n_cols : ((u64)n_cols + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if (n_rows && !rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  return KMX_OK;
+  int rc;
+  if ((rc = c.n_cols(n_cols)) || (rc = c.no_bloom(mode, "")) || (rc = c.mode(mode)) || (rc = c.key_words(key_words))) return rc;
+  *row_bytes = MatCheck::row_bytes(key_words, mode, n_cols);
+  if ((rc = c.row_fits(*row_bytes)) || (rc = c.n_rows(n_rows))) return rc;
+  return c.rows(n_rows, rows);
 }
 
 // ---- column sums ----
-struct kmx_colsums_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_rows = 0, row_bytes = 0;
-  u32 n_cols = 0;
-  u64 *d_sums_own = nullptr, *d_sums = nullptr;
-  void* d_in = nullptr;                 // kmx_colsums_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
+struct kmx_colsums_result : MatResult {
+  u64* d_sums = nullptr;
 };
 
-static void colsums_release(kmx_colsums_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_sums_own); c->dfree(R->d_in);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
+static int colsums_check(kmx_ctx* ctx, const kmx_colsums_task* T, const char* who, u64* row_bytes)
+{ return diff_check_body(MatCheck{ctx, who}, T->key_words, T->mode, T->n_cols, T->rows, T->n_rows, row_bytes); }
 
 static int colsums_queue(kmx_ctx* ctx, const kmx_colsums_task* T, kmx_colsums_result* R)
 {
@@ -229,12 +210,11 @@ static int colsums_queue(kmx_ctx* ctx, const kmx_colsums_task* T, kmx_colsums_re
   const u32 N = T->n_cols, skip = 8 * T->key_words;
   const bool count = T->mode == KMX_MODE_COUNT;
   R->d_sums = (u64*)T->sums;
-  if (!R->d_sums && !(R->d_sums = R->d_sums_own = (u64*)ctx->dalloc(8ull * N))) return ctx->fail(KMX_E_NOMEM, "kmx_colsums: device allocation failed");
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  if (R->d_sums_own) KMX_HIP(ctx, hipMemsetAsync(R->d_sums_own, 0, 8ull * N, st));
+  const bool own = !R->d_sums;
+  if (own && !(R->d_sums = (u64*)R->keep(8ull * N))) return ctx->fail(KMX_E_NOMEM, "kmx_colsums: device allocation failed");
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  if (own) KMX_HIP(ctx, hipMemsetAsync(R->d_sums, 0, 8ull * N, st));
   if (T->n_rows) {
     const u32 units = count ? N : (N + 7) / 8, LU = pow2_at_or_above(units, 256), ub = (units + LU - 1) / LU;
     u64 tiles = std::max<u64>(1, (u64)std::max(kmx_plan_cus(ctx), 1) * CS_WGS_PER_CU / ub);
@@ -246,268 +226,116 @@ static int colsums_queue(kmx_ctx* ctx, const kmx_colsums_task* T, kmx_colsums_re
     else hipLaunchKernelGGL(k_colsums<false>, grid, dim3(256), 0, st, (const u8*)T->rows, (u64)T->n_rows, R->row_bytes, skip, N, LU, tile_rows, R->d_sums);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R);
 }
 
-static int colsums_call(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = diff_check_body(ctx, who, task->key_words, task->mode, task->n_cols, task->rows, task->n_rows, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_colsums_result* R = new kmx_colsums_result();
-  R->ctx = ctx; R->n_rows = task->n_rows; R->row_bytes = row_bytes; R->n_cols = task->n_cols;
-  kmx_colsums_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); colsums_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = colsums_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_colsums_dev(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_colsums_dev", "kmx_colsums", colsums_check, colsums_queue); }
+extern "C" int kmx_colsums_host(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_colsums_host", "kmx_colsums", colsums_check, colsums_queue); }
 
-extern "C" int kmx_colsums_dev(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out) { return colsums_call(ctx, task, out, false, "kmx_colsums_dev"); }
-extern "C" int kmx_colsums_host(kmx_ctx* ctx, const kmx_colsums_task* task, kmx_colsums_result** out) { return colsums_call(ctx, task, out, true, "kmx_colsums_host"); }
-
-extern "C" int kmx_colsums_result_wait(kmx_colsums_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_colsums: ") + hipGetErrorString(e));
-  R->ctx->dfree(R->d_in); R->d_in = nullptr;      // the call has run: the upload goes back to the pool; the table stays
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t* kmx_colsums_result_sums_dev(kmx_colsums_result* R) { return R && kmx_colsums_result_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
+extern "C" int kmx_colsums_result_wait(kmx_colsums_result* R) { return mat_wait(R); }
+extern "C" uint64_t* kmx_colsums_result_sums_dev(kmx_colsums_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_sums : nullptr; }
 extern "C" int kmx_colsums_result_copy_sums(kmx_colsums_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_colsums_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < R->n_cols) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!host_dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, host_dst, R->d_sums, 8ull * R->n_cols);
-}
-extern "C" double kmx_colsums_result_kernel_ms(kmx_colsums_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_colsums_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_sums, R->n_cols, 8) : KMX_E_INVAL; }
+extern "C" double kmx_colsums_result_kernel_ms(kmx_colsums_result* R) { return mat_kernel_ms(R); }
 extern "C" uint64_t kmx_colsums_result_algo_bytes(kmx_colsums_result* R)
 {
-  if (!R || kmx_colsums_result_wait(R) != KMX_OK) return 0;
+  if (mat_wait(R) != KMX_OK) return 0;
   return R->n_rows * R->row_bytes + 8ull * R->n_cols;
 }
-extern "C" void kmx_colsums_result_free(kmx_colsums_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  colsums_release(R);
-}
+extern "C" void kmx_colsums_result_free(kmx_colsums_result* R) { mat_free(R); }
 
 // ---- the test ----
-struct kmx_diff_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_cols = 0;
-  u64 row_bytes = 0;
-  u32 *d_keep = nullptr, *d_tiles = nullptr;
-  DiffRec *d_recs_all = nullptr, *d_recs = nullptr;
-  u8 *d_grp = nullptr, *d_out = nullptr;
-  u8* h_grp = nullptr;                  // page-locked: the group table (COUNT) or the two byte masks (PA) on their way up
-  u32* h_tot = nullptr;                 // page-locked: kept rows
-  void* d_in = nullptr;                 // kmx_diff_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
+struct kmx_diff_result : MatResult {
+  DiffRec* d_recs = nullptr;
+  u8* d_out = nullptr;
 };
 
 static int diff_check(kmx_ctx* ctx, const kmx_diff_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
-  const int rc = diff_check_body(ctx, w, T->key_words, T->mode, T->n_cols, T->rows, T->n_rows, row_bytes);
+  const MatCheck c{ctx, who};
+  const int rc = diff_check_body(c, T->key_words, T->mode, T->n_cols, T->rows, T->n_rows, row_bytes);
   if (rc != KMX_OK) return rc;
-  if (!T->group) return ctx->fail(KMX_E_INVAL, w + ": null group table");
+  if (!T->group) return c.no(KMX_E_INVAL, ": null group table");
   u64 n[3] = {0, 0, 0};
   for (u32 i = 0; i < T->n_cols; i++) {
-    if (T->group[i] > 2) return ctx->fail(KMX_E_INVAL, w + ": a group is 0 (control), 1 (case) or 2 (ignored)");
+    if (T->group[i] > 2) return c.no(KMX_E_INVAL, ": a group is 0 (control), 1 (case) or 2 (ignored)");
     n[T->group[i]]++;
   }
-  if (!n[0] || !n[1]) return ctx->fail(KMX_E_INVAL, w + ": at least one control and one case column are needed");
-  if (T->total_ctrl == 0 || T->total_case == 0) return ctx->fail(KMX_E_INVAL, w + ": total_ctrl and total_case must be above 0");
-  if (T->total_ctrl + T->total_case < T->total_ctrl) return ctx->fail(KMX_E_INVAL, w + ": total_ctrl + total_case must be below 2^64");
-  if (std::isnan(T->threshold) || T->threshold < 0.0) return ctx->fail(KMX_E_INVAL, w + ": the threshold is a number at or above 0");
+  if (!n[0] || !n[1]) return c.no(KMX_E_INVAL, ": at least one control and one case column are needed");
+  if (T->total_ctrl == 0 || T->total_case == 0) return c.no(KMX_E_INVAL, ": total_ctrl and total_case must be above 0");
+  if (T->total_ctrl + T->total_case < T->total_ctrl) return c.no(KMX_E_INVAL, ": total_ctrl + total_case must be below 2^64");
+  if (std::isnan(T->threshold) || T->threshold < 0.0) return c.no(KMX_E_INVAL, ": the threshold is a number at or above 0");
   return KMX_OK;
-}
-
-static void diff_release(kmx_diff_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keep, R->d_tiles, R->d_recs_all, R->d_recs, R->d_grp, R->d_out, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_grp); c->hfree(R->h_tot);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
 static int diff_queue(kmx_ctx* ctx, const kmx_diff_task* T, kmx_diff_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, skip = 8 * T->key_words, n_rows = R->n_rows, tiles = filter_tiles(n_rows);
+  const u32 N = T->n_cols, skip = 8 * T->key_words, n_rows = (u32)R->n_rows, tiles = filter_tiles(n_rows);
   const bool count = T->mode == KMX_MODE_COUNT;
   const u32 units = count ? N : (N + 7) / 8;
   const u64 grp_bytes = count ? N : 2ull * units;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_grp = (u8*)ctx->halloc(grp_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_diff: host allocation failed");
+  u8* h_grp;      // page-locked: the group table (COUNT) or the two byte masks (PA) on their way up
+  if (!(R->h_tot = (u32*)R->pin(64)) || !(h_grp = (u8*)R->pin(grp_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_diff: host allocation failed");
   R->h_tot[0] = 0;
-  if (count) memcpy(R->h_grp, T->group, N);
+  if (count) memcpy(h_grp, T->group, N);
   else {      // per-group byte masks: bit i & 7 of byte i >> 3; the padding bits stay 0
-    memset(R->h_grp, 0, grp_bytes);
-    for (u32 i = 0; i < N; i++) if (T->group[i] < 2) R->h_grp[(T->group[i] ? units : 0) + (i >> 3)] |= (u8)(1u << (i & 7));
+    memset(h_grp, 0, grp_bytes);
+    for (u32 i = 0; i < N; i++) if (T->group[i] < 2) h_grp[(T->group[i] ? units : 0) + (i >> 3)] |= (u8)(1u << (i & 7));
   }
-  R->d_keep = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_tiles = (u32*)ctx->dalloc(4ull * ((u64)tiles + 1));
-  R->d_recs_all = (DiffRec*)ctx->dalloc(sizeof(DiffRec) * (u64)n_rows);
-  R->d_recs = (DiffRec*)ctx->dalloc(sizeof(DiffRec) * (u64)n_rows);      // every row kept
-  R->d_out = (u8*)ctx->dalloc((u64)n_rows * R->row_bytes + 16);
-  R->d_grp = (u8*)ctx->dalloc(grp_bytes);
-  if (!R->d_keep || !R->d_tiles || !R->d_recs_all || !R->d_recs || !R->d_out || !R->d_grp)
-    return ctx->fail(KMX_E_NOMEM, "kmx_diff: device allocation failed (send the body in runs of rows)");
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_grp, R->h_grp, grp_bytes, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_tiles, 0, 4ull * ((u64)tiles + 1), st));
+  u32* d_keep = (u32*)R->tmp(4ull * n_rows);
+  u32* d_tiles = (u32*)R->keep(4ull * ((u64)tiles + 1));
+  DiffRec* d_recs_all = (DiffRec*)R->tmp(sizeof(DiffRec) * (u64)n_rows);
+  R->d_recs = (DiffRec*)R->keep(sizeof(DiffRec) * (u64)n_rows);      // every row kept
+  R->d_out = (u8*)R->keep((u64)n_rows * R->row_bytes + 16);
+  u8* d_grp = (u8*)R->tmp(grp_bytes);
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_diff: device allocation failed (send the body in runs of rows)");
+  KMX_HIP(ctx, hipMemcpyAsync(d_grp, h_grp, grp_bytes, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_tiles, 0, 4ull * ((u64)tiles + 1), st));
   if (n_rows) {
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has DF_WAVES_PER_SIMD waves a SIMD to hide the loads
-    const u32 L = pow2_at_or_above(units, 64);
-    u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(kmx_plan_cus(ctx), 1) * 4 * DF_WAVES_PER_SIMD) RW >>= 1;
-    const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, kmx_grid_cap(DF_MAX_GRID));
-    if (count) hipLaunchKernelGGL(k_diff_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, L, RW, (const u8*)R->d_grp,
-                                  (u64)T->total_ctrl, (u64)T->total_case, T->threshold, T->min_rec, R->d_keep, R->d_recs_all, R->d_tiles);
-    else hipLaunchKernelGGL(k_diff_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, L, RW, (const u8*)R->d_grp,
-                            (u64)T->total_ctrl, (u64)T->total_case, T->threshold, T->min_rec, R->d_keep, R->d_recs_all, R->d_tiles);
+    const RowPlan p = mat_row_plan(units, n_rows, (u32)std::max(kmx_plan_cus(ctx), 1), DF_WAVES_PER_SIMD);
+    const u32 grid = (u32)std::min<u64>((p.chunks + 3) / 4, kmx_grid_cap(DF_MAX_GRID));
+    if (count) hipLaunchKernelGGL(k_diff_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, p.L, p.RW, (const u8*)d_grp,
+                                  (u64)T->total_ctrl, (u64)T->total_case, T->threshold, T->min_rec, d_keep, d_recs_all, d_tiles);
+    else hipLaunchKernelGGL(k_diff_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, p.L, p.RW, (const u8*)d_grp,
+                            (u64)T->total_ctrl, (u64)T->total_case, T->threshold, T->min_rec, d_keep, d_recs_all, d_tiles);
     KMX_HIP(ctx, hipGetLastError());
   }
-  KMX_HIP(ctx, launch_filter_scan(R->d_tiles, tiles, st));
+  KMX_HIP(ctx, launch_filter_scan(d_tiles, tiles, st));
   if (n_rows) {
-    KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, R->d_keep, R->d_keep, R->d_tiles, R->d_out, st));
-    hipLaunchKernelGGL(k_diff_place, dim3(std::min(tiles, kmx_grid_cap(DF_MAX_GRID))), dim3(DF_TILE), 0, st, (const u32*)R->d_keep, (const DiffRec*)R->d_recs_all, n_rows,
-                       (const u32*)R->d_tiles, R->d_recs);
+    KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, d_keep, d_keep, d_tiles, R->d_out, st));
+    hipLaunchKernelGGL(k_diff_place, dim3(std::min(tiles, kmx_grid_cap(DF_MAX_GRID))), dim3(DF_TILE), 0, st, (const u32*)d_keep, (const DiffRec*)d_recs_all, n_rows,
+                       (const u32*)d_tiles, R->d_recs);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_tiles + tiles, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R, d_tiles + tiles);
 }
 
-static int diff_call(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = diff_check(ctx, task, who, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_diff_result* R = new kmx_diff_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->row_bytes = row_bytes; R->n_cols = task->n_cols;
-  kmx_diff_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); diff_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = diff_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_diff_dev(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_diff_dev", "kmx_diff", diff_check, diff_queue); }
+extern "C" int kmx_diff_host(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_diff_host", "kmx_diff", diff_check, diff_queue); }
 
-extern "C" int kmx_diff_dev(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out) { return diff_call(ctx, task, out, false, "kmx_diff_dev"); }
-extern "C" int kmx_diff_host(kmx_ctx* ctx, const kmx_diff_task* task, kmx_diff_result** out) { return diff_call(ctx, task, out, true, "kmx_diff_host"); }
-
-extern "C" int kmx_diff_result_wait(kmx_diff_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_diff: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; the kept rows and their records stay
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_keep); R->d_keep = nullptr;
-  c->dfree(R->d_recs_all); R->d_recs_all = nullptr;
-  c->dfree(R->d_grp); R->d_grp = nullptr;
-  c->dfree(R->d_in); R->d_in = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_diff_result_rows(kmx_diff_result* R) { return R && kmx_diff_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" int kmx_diff_result_wait(kmx_diff_result* R) { return mat_wait(R); }
+extern "C" uint64_t kmx_diff_result_rows(kmx_diff_result* R) { return mat_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
 extern "C" uint64_t kmx_diff_result_row_bytes(const kmx_diff_result* R) { return R ? R->row_bytes : 0; }
 extern "C" uint64_t kmx_diff_result_body_bytes(kmx_diff_result* R) { return R ? kmx_diff_result_rows(R) * R->row_bytes : 0; }
-extern "C" const void* kmx_diff_result_body_dev(kmx_diff_result* R) { return R && kmx_diff_result_wait(R) == KMX_OK ? R->d_out : nullptr; }
-extern "C" const kmx_diff_rec* kmx_diff_result_recs_dev(kmx_diff_result* R) { return R && kmx_diff_result_wait(R) == KMX_OK ? (const kmx_diff_rec*)R->d_recs : nullptr; }
-static int diff_copy_out(kmx_diff_result* R, void* dst, uint64_t dst_bytes, const void* src, u64 bytes)
-{
-  if (dst_bytes < bytes) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!bytes) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, bytes);
-}
+extern "C" const void* kmx_diff_result_body_dev(kmx_diff_result* R) { return mat_wait(R) == KMX_OK ? R->d_out : nullptr; }
+extern "C" const kmx_diff_rec* kmx_diff_result_recs_dev(kmx_diff_result* R) { return mat_wait(R) == KMX_OK ? (const kmx_diff_rec*)R->d_recs : nullptr; }
 extern "C" int kmx_diff_result_copy_body(kmx_diff_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_diff_result_wait(R);
-  return rc != KMX_OK ? rc : diff_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_diff_result_body_bytes(R));
-}
+{ return R ? mat_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_diff_result_body_bytes(R), 1) : KMX_E_INVAL; }
 extern "C" int kmx_diff_result_copy_recs(kmx_diff_result* R, kmx_diff_rec* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_diff_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < R->h_tot[0]) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  return diff_copy_out(R, host_dst, ~0ull, R->d_recs, sizeof(DiffRec) * (u64)R->h_tot[0]);
-}
-extern "C" double kmx_diff_result_kernel_ms(kmx_diff_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_diff_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_recs, kmx_diff_result_rows(R), sizeof(DiffRec)) : KMX_E_INVAL; }
+extern "C" double kmx_diff_result_kernel_ms(kmx_diff_result* R) { return mat_kernel_ms(R); }
 extern "C" uint64_t kmx_diff_result_algo_bytes(kmx_diff_result* R)
 {
-  if (!R || kmx_diff_result_wait(R) != KMX_OK) return 0;
-  return (u64)R->n_rows * R->row_bytes + (u64)R->h_tot[0] * (R->row_bytes + sizeof(DiffRec));
+  if (mat_wait(R) != KMX_OK) return 0;
+  return R->n_rows * R->row_bytes + (u64)R->h_tot[0] * (R->row_bytes + sizeof(DiffRec));
 }
-extern "C" void kmx_diff_result_free(kmx_diff_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  diff_release(R);
-}
+extern "C" void kmx_diff_result_free(kmx_diff_result* R) { mat_free(R); }

@@ -18,7 +18,7 @@
 // Every load of a body byte is inside [rows, rows + n_rows * row_bytes) by construction: an address is rows + r * row_bytes + skip + b
 // with r < n_rows and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads; nothing is loaded in wider pieces
 // than the piece that is tested (a byte for PA / BF, a count's dword for COUNT) and nothing is rounded to an aligned address.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -32,7 +32,6 @@ constexpr u32 DM_TR = 32;                 // rows of a tile of k_dist_mins in LD
 constexpr u64 DM_RUN_MIN = 256;           // rows of the shortest run of k_dist_mins
 constexpr u32 DIST_WGS_PER_CU = 8;        // workgroups a launch aims at: the number of runs per block pair follows
 
-struct __attribute__((packed, aligned(1))) DDword { u32 v; };      // a dword at any address: one global_load_dword
 
 template <bool COUNT>
 __global__ __launch_bounds__(256)
@@ -51,8 +50,8 @@ void k_dist_slab(const u8* __restrict__ rows, u64 n_rows, u64 row_bytes, u32 ski
       u32 lo = 0, hi = 0;
       if (c < N) {
         const u8* p = rows + r0 * row_bytes + skip + 4ull * c;
-        for (u32 r = 0; r < min(nr, 32u); r++) lo |= (u32)(reinterpret_cast<const DDword*>(p + r * row_bytes)->v != 0) << r;
-        for (u32 r = 32; r < nr; r++) hi |= (u32)(reinterpret_cast<const DDword*>(p + r * row_bytes)->v != 0) << (r - 32);
+        for (u32 r = 0; r < min(nr, 32u); r++) lo |= (u32)(reinterpret_cast<const UDword*>(p + r * row_bytes)->v != 0) << r;
+        for (u32 r = 32; r < nr; r++) hi |= (u32)(reinterpret_cast<const UDword*>(p + r * row_bytes)->v != 0) << (r - 32);
       }
       slab[((u64)ct * W + w) * 64 + lane] = (u64)lo | ((u64)hi << 32);
     } else {          // a tile: 64 rows x 64 payload bytes (the 8 column blocks from 8 ct on)
@@ -166,8 +165,8 @@ void k_dist_mins(const u8* __restrict__ rows, u64 n_rows, u64 row_bytes, u32 ski
     for (u32 i = tid; i < cn * 64; i += 256) {      // a wave a row: 256 contiguous bytes
       const u8* p = rows + (rc + (i >> 6)) * row_bytes + skip;
       const u32 ca = I * 64 + (i & 63u), cb = J * 64 + (i & 63u);
-      Aw[i] = ca < N ? reinterpret_cast<const DDword*>(p + 4ull * ca)->v : 0u;
-      if (!diag) Bw[i] = cb < N ? reinterpret_cast<const DDword*>(p + 4ull * cb)->v : 0u;
+      Aw[i] = ca < N ? reinterpret_cast<const UDword*>(p + 4ull * ca)->v : 0u;
+      if (!diag) Bw[i] = cb < N ? reinterpret_cast<const UDword*>(p + 4ull * cb)->v : 0u;
     }
     __syncthreads();
     for (u32 k = 0; k < cn; k++) {
@@ -207,44 +206,32 @@ static void dist_runs(u64 units, u64 pairs, u32 n_cu, u64 run_min, u64 run_max, 
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_dist_result {
-  kmx_ctx* ctx = nullptr;
-  u64 n_rows = 0, row_bytes = 0, slab_bytes = 0;
-  u32 n_cols = 0;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_dist_result : MatResult {
+  u64 slab_bytes = 0;
   bool want_mins = false;
-  u64 *d_slab = nullptr, *d_inter_own = nullptr, *d_inter = nullptr, *d_mins_own = nullptr, *d_mins = nullptr;
-  void* d_in = nullptr;                 // kmx_dist_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev[4] = {};      // ev: start, behind the slab, behind the pairs, end
-  bool waited = false; int status = KMX_OK;
+  u64 *d_inter = nullptr, *d_mins = nullptr;
 };
 
 static int dist_check(kmx_ctx* ctx, const kmx_dist_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
-  if (T->n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
+  const MatCheck c{ctx, who};
+  int rc;
+  if ((rc = c.n_cols(T->n_cols))) return rc;
   if (T->mode == KMX_MODE_BFC || T->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": counting Bloom filter and transposed bodies are not supported (KMX_MODE_COUNT, KMX_MODE_PA and KMX_MODE_BF only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA && T->mode != KMX_MODE_BF) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT, KMX_MODE_PA or KMX_MODE_BF");
-  if (T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be at most 4");
-  if (T->key_words == 0 && T->mode != KMX_MODE_BF) return ctx->fail(KMX_E_INVAL, w + ": count and presence/absence rows have a key (key_words 1 ... 4)");
-  if (T->key_words != 0 && T->mode == KMX_MODE_BF) return ctx->fail(KMX_E_INVAL, w + ": Bloom filter rows have no key (key_words 0)");
-  if ((T->want_mins || T->mins) && T->mode != KMX_MODE_COUNT) return ctx->fail(KMX_E_INVAL, w + ": only count rows have counts to take minima of (want_mins needs KMX_MODE_COUNT)");
-  if (T->mins && !T->want_mins) return ctx->fail(KMX_E_INVAL, w + ": a mins table without want_mins");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  *row_bytes = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * T->n_cols : ((u64)T->n_cols + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (T->n_cols > 32768) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 32768 samples (a table would be 8 GiB and more)");
-  if (T->n_rows > (1ull << 56) / *row_bytes) return ctx->fail(KMX_E_UNSUPPORTED, w + ": a body of 2^56 bytes and more");
+    return c.no(KMX_E_UNSUPPORTED, ": counting Bloom filter and transposed bodies are not supported (KMX_MODE_COUNT, KMX_MODE_PA and KMX_MODE_BF only)");
+  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA && T->mode != KMX_MODE_BF) return c.no(KMX_E_INVAL, ": mode must be KMX_MODE_COUNT, KMX_MODE_PA or KMX_MODE_BF");
+  if (T->key_words > 4) return c.no(KMX_E_INVAL, ": key_words must be at most 4");
+  if (T->key_words == 0 && T->mode != KMX_MODE_BF) return c.no(KMX_E_INVAL, ": count and presence/absence rows have a key (key_words 1 ... 4)");
+  if (T->key_words != 0 && T->mode == KMX_MODE_BF) return c.no(KMX_E_INVAL, ": Bloom filter rows have no key (key_words 0)");
+  if ((T->want_mins || T->mins) && T->mode != KMX_MODE_COUNT) return c.no(KMX_E_INVAL, ": only count rows have counts to take minima of (want_mins needs KMX_MODE_COUNT)");
+  if (T->mins && !T->want_mins) return c.no(KMX_E_INVAL, ": a mins table without want_mins");
+  if ((rc = c.rows(T->n_rows, T->rows))) return rc;
+  *row_bytes = MatCheck::row_bytes(T->key_words, T->mode, T->n_cols);
+  if ((rc = c.row_fits(*row_bytes))) return rc;
+  if (T->n_cols > 32768) return c.no(KMX_E_UNSUPPORTED, ": more than 32768 samples (a table would be 8 GiB and more)");
+  if (T->n_rows > (1ull << 56) / *row_bytes) return c.no(KMX_E_UNSUPPORTED, ": a body of 2^56 bytes and more");
   return KMX_OK;
-}
-
-static void dist_release(kmx_dist_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_slab); c->dfree(R->d_inter_own); c->dfree(R->d_mins_own); c->dfree(R->d_in);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev[0], R->ev[1], R->ev[2], R->ev[3]}) if (e) (void)hipEventDestroy(e);
-  delete R;
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
@@ -254,6 +241,7 @@ static int dist_queue(kmx_ctx* ctx, const kmx_dist_task* T, kmx_dist_result* R)
   const u32 N = T->n_cols, NB = (N + 63) / 64, skip = 8 * T->key_words, n_cu = (u32)std::max(kmx_plan_cus(ctx), 1);
   const u64 n_rows = T->n_rows, W = (n_rows + 63) / 64, table = (u64)N * N, pairs = (u64)NB * (NB + 1) / 2;
   const bool count = T->mode == KMX_MODE_COUNT;
+  R->want_mins = T->want_mins != 0;
   u32 p_runs = 1, m_runs = 1; u64 p_len = DP_CH, m_len = DM_TR;
   if (n_rows) {
     dist_runs(W, pairs, n_cu, DP_RUN_MIN, DP_RUN_MAX, DP_CH, &p_runs, &p_len);
@@ -262,30 +250,29 @@ static int dist_queue(kmx_ctx* ctx, const kmx_dist_task* T, kmx_dist_result* R)
       return ctx->fail(KMX_E_UNSUPPORTED, "kmx_dist: too many rows for one call (send the body in runs of rows)");
   }
   R->slab_bytes = (u64)NB * 64 * W * 8;
-  if (n_rows && !(R->d_slab = (u64*)ctx->dalloc(R->slab_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_dist: device allocation failed (send the body in runs of rows)");
-  R->d_inter = (u64*)T->inter;
-  if (!R->d_inter) R->d_inter = R->d_inter_own = (u64*)ctx->dalloc(8 * table);
-  R->d_mins = R->want_mins ? (u64*)T->mins : nullptr;
-  if (R->want_mins && !R->d_mins) R->d_mins = R->d_mins_own = (u64*)ctx->dalloc(8 * table);
-  if (!R->d_inter || (R->want_mins && !R->d_mins)) return ctx->fail(KMX_E_NOMEM, "kmx_dist: device allocation failed");
-  if (ctx->profiling) {
-    for (int i = 0; i < 4; i++) KMX_HIP(ctx, hipEventCreate(&R->ev[i]));
-    KMX_HIP(ctx, hipEventRecord(R->ev[0], st));
-  }
-  if (R->d_inter_own) KMX_HIP(ctx, hipMemsetAsync(R->d_inter_own, 0, 8 * table, st));
-  if (R->d_mins_own) KMX_HIP(ctx, hipMemsetAsync(R->d_mins_own, 0, 8 * table, st));
+  u64* d_slab = nullptr;
+  if (n_rows && !(d_slab = (u64*)R->tmp(R->slab_bytes))) return ctx->fail(KMX_E_NOMEM, "kmx_dist: device allocation failed (send the body in runs of rows)");
+  // a table of the call's own starts at zero; one the caller handed in is on neither list
+  const bool own_inter = !T->inter, own_mins = R->want_mins && !T->mins;
+  R->d_inter = own_inter ? (u64*)R->keep(8 * table) : (u64*)T->inter;
+  R->d_mins = own_mins ? (u64*)R->keep(8 * table) : R->want_mins ? (u64*)T->mins : nullptr;
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_dist: device allocation failed");
+  int rc = mat_queue_head(R, 4);      // ev: start, behind the slab, behind the pairs, end
+  if (rc != KMX_OK) return rc;
+  if (own_inter) KMX_HIP(ctx, hipMemsetAsync(R->d_inter, 0, 8 * table, st));
+  if (own_mins) KMX_HIP(ctx, hipMemsetAsync(R->d_mins, 0, 8 * table, st));
   if (n_rows) {
     const u8* rows = (const u8*)T->rows;
     const u32 ct_n = count ? NB : (NB + 7) / 8;
     const u64 n_tiles = W * ct_n;
     const u32 grid = (u32)std::min<u64>((n_tiles + 3) / 4, kmx_grid_cap(1u << 20));
-    if (count) hipLaunchKernelGGL(k_dist_slab<true>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, R->d_slab);
-    else hipLaunchKernelGGL(k_dist_slab<false>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, R->d_slab);
+    if (count) hipLaunchKernelGGL(k_dist_slab<true>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, d_slab);
+    else hipLaunchKernelGGL(k_dist_slab<false>, dim3(grid), dim3(256), 0, st, rows, n_rows, R->row_bytes, skip, N, NB, W, ct_n, n_tiles, d_slab);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[1], st));
   if (n_rows) {
-    hipLaunchKernelGGL(k_dist_pairs, dim3((u32)(pairs * p_runs)), dim3(256), 0, st, (const u64*)R->d_slab, W, N, NB, p_runs, p_len, R->d_inter);
+    hipLaunchKernelGGL(k_dist_pairs, dim3((u32)(pairs * p_runs)), dim3(256), 0, st, (const u64*)d_slab, W, N, NB, p_runs, p_len, R->d_inter);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[2], st));
@@ -293,118 +280,28 @@ static int dist_queue(kmx_ctx* ctx, const kmx_dist_task* T, kmx_dist_result* R)
     hipLaunchKernelGGL(k_dist_mins, dim3((u32)(pairs * m_runs)), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, NB, m_runs, m_len, R->d_mins);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[3], st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-static kmx_dist_result* dist_new(kmx_ctx* ctx, const kmx_dist_task* T, u64 row_bytes)
-{
-  kmx_dist_result* R = new kmx_dist_result();
-  R->ctx = ctx; R->n_rows = T->n_rows; R->row_bytes = row_bytes; R->n_cols = T->n_cols; R->want_mins = T->want_mins != 0;
-  return R;
+  return mat_queue_tail(R);
 }
 
 extern "C" int kmx_dist_dev(kmx_ctx* ctx, const kmx_dist_task* task, kmx_dist_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_dist_dev: null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = dist_check(ctx, task, "kmx_dist_dev", &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_dist_result* R = dist_new(ctx, task, row_bytes);
-  if ((rc = dist_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); dist_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
+{ return mat_call(ctx, task, out, false, "kmx_dist_dev", "kmx_dist", dist_check, dist_queue); }
 extern "C" int kmx_dist_host(kmx_ctx* ctx, const kmx_dist_task* task, kmx_dist_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_dist_host: null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = dist_check(ctx, task, "kmx_dist_host", &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_dist_result* R = dist_new(ctx, task, row_bytes);
-  kmx_dist_task dt = *task;
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); dist_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_dist_host: upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_dist_host: upload: ") + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = dist_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+{ return mat_call(ctx, task, out, true, "kmx_dist_host", "kmx_dist", dist_check, dist_queue); }
 
-extern "C" int kmx_dist_result_wait(kmx_dist_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_dist: ") + hipGetErrorString(e));
-  // the call has run: the slab and the upload go back to the pool; the tables stay
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_slab); R->d_slab = nullptr;
-  c->dfree(R->d_in); R->d_in = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t* kmx_dist_result_inter_dev(kmx_dist_result* R) { return R && kmx_dist_result_wait(R) == KMX_OK ? (uint64_t*)R->d_inter : nullptr; }
-extern "C" uint64_t* kmx_dist_result_mins_dev(kmx_dist_result* R) { return R && kmx_dist_result_wait(R) == KMX_OK ? (uint64_t*)R->d_mins : nullptr; }
-static int dist_copy_out(kmx_dist_result* R, uint64_t* dst, uint64_t dst_entries, const u64* src)
-{
-  const int rc = kmx_dist_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  const u64 entries = (u64)R->n_cols * R->n_cols;
-  if (!src) return R->ctx->fail(KMX_E_INVAL, "kmx_dist_result_copy_mins: the call was made without want_mins");
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, 8 * entries);
-}
+extern "C" int kmx_dist_result_wait(kmx_dist_result* R) { return mat_wait(R); }
+extern "C" uint64_t* kmx_dist_result_inter_dev(kmx_dist_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_inter : nullptr; }
+extern "C" uint64_t* kmx_dist_result_mins_dev(kmx_dist_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_mins : nullptr; }
 extern "C" int kmx_dist_result_copy_inter(kmx_dist_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? dist_copy_out(R, host_dst, dst_entries, R->d_inter) : KMX_E_INVAL; }
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_inter, (u64)R->n_cols * R->n_cols, 8) : KMX_E_INVAL; }
 extern "C" int kmx_dist_result_copy_mins(kmx_dist_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? dist_copy_out(R, host_dst, dst_entries, R->d_mins) : KMX_E_INVAL; }
-extern "C" double kmx_dist_result_kernel_ms(kmx_dist_result* R)
-{
-  if (!R || !R->ev[0] || !R->ev[3] || kmx_dist_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev[0], R->ev[3]) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_mins, (u64)R->n_cols * R->n_cols, 8, "kmx_dist_result_copy_mins: the call was made without want_mins") : KMX_E_INVAL; }
+extern "C" double kmx_dist_result_kernel_ms(kmx_dist_result* R) { return mat_kernel_ms(R); }
 extern "C" int kmx_dist_result_kernel_parts_ms(kmx_dist_result* R, double* slab_ms, double* pairs_ms, double* mins_ms)
-{
-  double* o[3] = {slab_ms, pairs_ms, mins_ms};
-  for (double* p : o) if (p) *p = -1.0;
-  if (!R) return KMX_E_INVAL;
-  if (!R->ev[0] || !R->ev[3] || kmx_dist_result_wait(R) != KMX_OK) return KMX_OK;
-  for (int i = 0; i < 3; i++) {
-    float ms = 0;
-    if (o[i] && (i < 2 || R->want_mins) && hipEventElapsedTime(&ms, R->ev[i], R->ev[i + 1]) == hipSuccess) *o[i] = (double)ms;
-  }
-  return KMX_OK;
-}
+{ return mat_kernel_parts_ms(R, {slab_ms, pairs_ms, mins_ms}, R && R->want_mins ? 7u : 3u); }
 extern "C" uint64_t kmx_dist_result_algo_bytes(kmx_dist_result* R)
 {
-  if (!R || kmx_dist_result_wait(R) != KMX_OK) return 0;
+  if (mat_wait(R) != KMX_OK) return 0;
   const u64 table = 8ull * R->n_cols * R->n_cols;
   return R->n_rows * R->row_bytes + 2 * R->slab_bytes + table + (R->want_mins ? R->n_rows * 4 * R->n_cols + table : 0);
 }
-extern "C" void kmx_dist_result_free(kmx_dist_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  dist_release(R);
-}
+extern "C" void kmx_dist_result_free(kmx_dist_result* R) { mat_free(R); }

@@ -25,7 +25,7 @@
 // r * row_bytes + skip + b with r < n_rows and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads; nothing is
 // loaded in wider pieces than the piece that is tested and nothing is rounded to an aligned address.  The launch knobs of this file are
 // its own: KMX_GRAM_CUS and KMX_GRAM_GRID.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -41,7 +41,6 @@ constexpr u32 GP_CH = 32;                 // slab words (64 places each) of a pa
 constexpr u64 GP_RUN_MIN = 64;            // words of the shortest run a workgroup of k_gram_pairs takes (4096 places) ...
 constexpr u64 GP_RUN_MAX = 1ull << 24;    // ... and of the longest: see k_gram_pairs
 
-struct __attribute__((packed, aligned(1))) GDword { u32 v; };      // a dword at any address: one global_load_dword
 static_assert(sizeof(kmx_gram_task) == 64, "kmx_gram_task is 64 bytes");
 
 // lst: a byte a unit -- COUNT: 1 where the column is listed; PA: the listed columns of the payload byte.
@@ -71,7 +70,7 @@ void k_gram_score(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 sk
         const u8* q = rows + row * row_bytes + skip;
         for (u64 un = u; un < units; un += L) {
           const u32 m = lst[un];
-          if (COUNT) { if (m) acc += (u32)(reinterpret_cast<const GDword*>(q + 4 * un)->v >= a); }
+          if (COUNT) { if (m) acc += (u32)(reinterpret_cast<const UDword*>(q + 4 * un)->v >= a); }
           else if (m) acc += (u32)__popc((u32)q[un] & m);
         }
       }
@@ -182,7 +181,7 @@ void k_gram_slab(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 ski
       for (u32 r = 0; r < nr; r++) {      // (every lane of the wave goes round: place r is read from lane r)
         const u32 row = (u32)__builtin_amdgcn_readlane((int)mine, (int)r);
         u32 bit = 0;
-        if (ok && row != GR_NONE) bit = (u32)(reinterpret_cast<const GDword*>(p + (u64)row * row_bytes)->v >= a);
+        if (ok && row != GR_NONE) bit = (u32)(reinterpret_cast<const UDword*>(p + (u64)row * row_bytes)->v >= a);
         if (r < 32) lo |= bit << r; else hi |= bit << (r - 32);
       }
       slab[((u64)ct * W + w) * 64 + lane] = (u64)lo | ((u64)hi << 32);
@@ -293,19 +292,8 @@ void k_gram_pairs(const u64* __restrict__ slab, const u32* __restrict__ ww, cons
   }
 }
 
-static u32 gr_pow2_at_or_above(u64 x, u32 cap) { u32 p = 1; while (p < cap && p < x) p <<= 1; return p; }
-// KMX_GRAM_CUS=c: the CU count the launches plan for, 1 <= c <= the device's (it may only lower the count)
-static u32 gr_cus(const kmx_ctx* ctx)
-{
-  const long c = kmx_env_int("KMX_GRAM_CUS"), n = std::max(ctx->n_cu, 1);
-  return (u32)(c >= 1 && c <= n ? c : n);
-}
-// KMX_GRAM_GRID=g: the cap on the workgroups of a launch (every kernel here strides over its work), 1 <= g <= the built-in cap
-static u32 gr_grid(u64 dflt)
-{
-  const long g = kmx_env_int("KMX_GRAM_GRID");
-  return (u32)(g >= 1 && (u64)g <= dflt ? (u64)g : dflt);
-}
+static u32 gr_cus(const kmx_ctx* ctx) { return (u32)std::max(kmx_env_cus("KMX_GRAM_CUS", ctx), 1); }
+static u32 gr_grid(u64 dflt) { return kmx_env_grid("KMX_GRAM_GRID", dflt); }
 // runs per block pair (dist's rule): enough workgroups to fill the chip, no run below GP_RUN_MIN words or above GP_RUN_MAX, a run a
 // multiple of a panel
 static void gr_runs(u64 words, u64 pairs, u32 cus, u32* runs, u64* run_len)
@@ -323,70 +311,40 @@ static void gr_runs(u64 words, u64 pairs, u32 cus, u32* runs, u64* run_len)
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_gram_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_cols = 0, n_use = 0;
-  u64 row_bytes = 0;
-  u64 *d_table_own = nullptr, *d_table = nullptr, *d_cursor = nullptr, *d_slab = nullptr;
-  u32 *d_par = nullptr, *d_hist = nullptr, *d_meta = nullptr, *d_recv = nullptr, *d_order = nullptr, *d_ww = nullptr;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_gram_result : MatResult {
+  u64* d_table = nullptr;
   u32* h_par = nullptr;                 // page-locked: [0] the words of the order on their way down; the weights and the list on their way up
-  void* d_in = nullptr;                 // kmx_gram_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev[5] = {};      // ev: start, behind score + fold, behind the order, behind the slab, end
-  bool waited = false; int status = KMX_OK;
 };
 
 static int gram_check(kmx_ctx* ctx, const kmx_gram_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
+  const MatCheck c{ctx, who};
   const u32 N = T->n_cols, M = T->n_use;
-  if (N == 0 || M == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column, and so has the list");
-  if (T->mode == KMX_MODE_BF || T->mode == KMX_MODE_BFC || T->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported: a Bloom row is a hash bit, its recurrence is not a k-mer's (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->key_words < 1 || T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (T->min_abund == 0) return ctx->fail(KMX_E_INVAL, w + ": min_abund must be at least 1");
-  if (T->min_abund > 1 && T->mode == KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": min_abund above 1 needs counts");
-  if (T->flags) return ctx->fail(KMX_E_INVAL, w + ": unknown flag bits");
-  if (!T->weights) return ctx->fail(KMX_E_INVAL, w + ": null weights");
-  if (M > N) return ctx->fail(KMX_E_INVAL, w + ": more listed columns than input columns");
-  if (!T->cols && M != N) return ctx->fail(KMX_E_INVAL, w + ": cols = NULL is the identity and needs n_use = n_cols");
-  *row_bytes = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * N : ((u64)N + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (N > 32768) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 32768 samples (a table would be 8 GiB and more)");
-  if (T->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  if (T->cols) {
-    std::vector<u32> s(T->cols, T->cols + M);
-    std::sort(s.begin(), s.end());
-    if (s.back() >= N) return ctx->fail(KMX_E_INVAL, w + ": a column index at or above n_cols");
-    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return ctx->fail(KMX_E_INVAL, w + ": a column is listed twice");
-  }
-  return KMX_OK;
-}
-
-static void gram_release(kmx_gram_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_table_own, R->d_cursor, R->d_slab, R->d_par, R->d_hist, R->d_meta, R->d_recv, R->d_order, R->d_ww, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_par);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev[0], R->ev[1], R->ev[2], R->ev[3], R->ev[4]}) if (e) (void)hipEventDestroy(e);
-  delete R;
+  int rc;
+  if ((rc = c.n_cols(N, M, "list")) || (rc = c.no_bloom(T->mode, ": a Bloom row is a hash bit, its recurrence is not a k-mer's")) || (rc = c.mode(T->mode)) ||
+      (rc = c.key_words(T->key_words)) || (rc = c.min_abund(T->min_abund, T->mode)) || (rc = c.flags(T->flags, 0))) return rc;
+  if (!T->weights) return c.no(KMX_E_INVAL, ": null weights");
+  if ((rc = c.list_fits(M, N, "listed")) || (rc = c.identity(T->cols, M, N, "n_use"))) return rc;
+  *row_bytes = MatCheck::row_bytes(T->key_words, T->mode, N);
+  if ((rc = c.row_fits(*row_bytes))) return rc;
+  if (N > 32768) return c.no(KMX_E_UNSUPPORTED, ": more than 32768 samples (a table would be 8 GiB and more)");
+  if ((rc = c.n_rows(T->n_rows)) || (rc = c.rows(T->n_rows, T->rows))) return rc;
+  return c.col_list(T->cols, M, N);
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
 static int gram_queue(kmx_ctx* ctx, const kmx_gram_task* T, kmx_gram_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, M = T->n_use, NB = (N + 63) / 64, skip = 8 * T->key_words, n_rows = R->n_rows;
+  const u32 N = T->n_cols, M = T->n_use, NB = (N + 63) / 64, skip = 8 * T->key_words, n_rows = (u32)R->n_rows;
   const bool count = T->mode == KMX_MODE_COUNT;
   const u32 units = count ? N : (u32)(((u64)N + 7) / 8);
   const u64 M1 = (u64)M + 1, table = (u64)N * N, pairs = (u64)NB * (NB + 1) / 2;
   const u64 W = (u64)n_rows / 64 + std::min<u64>(M1, n_rows);      // the words of the order at the most
   // page-locked: word 0 comes back (the words in use), then the weights, then the list a byte a unit
   const u64 par_words = 1 + M1 + (units + 3) / 4;
-  if (!(R->h_par = (u32*)ctx->halloc(4 * par_words))) return ctx->fail(KMX_E_NOMEM, "kmx_gram: host allocation failed");
+  if (!(R->h_par = (u32*)R->pin(4 * par_words))) return ctx->fail(KMX_E_NOMEM, "kmx_gram: host allocation failed");
   R->h_par[0] = 0;
   memcpy(R->h_par + 1, T->weights, 4 * M1);
   u8* h_lst = reinterpret_cast<u8*>(R->h_par + 1 + M1);
@@ -395,54 +353,51 @@ static int gram_queue(kmx_ctx* ctx, const kmx_gram_task* T, kmx_gram_result* R)
     const u32 c = T->cols ? T->cols[j] : j;
     if (count) h_lst[c] = 1; else h_lst[c >> 3] |= (u8)(1u << (c & 7));
   }
-  R->d_par = (u32*)ctx->dalloc(4 * par_words);
-  R->d_table = (u64*)T->table;
-  if (!R->d_table) R->d_table = R->d_table_own = (u64*)ctx->dalloc(8 * table);
-  if (!R->d_par || !R->d_table) return ctx->fail(KMX_E_NOMEM, "kmx_gram: device allocation failed");
+  // a table of the call's own starts at zero; one the caller handed in is on neither list
+  const bool own = !T->table;
+  u32* d_par = (u32*)R->tmp(4 * par_words);
+  R->d_table = own ? (u64*)R->keep(8 * table) : (u64*)T->table;
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_gram: device allocation failed");
+  u64 *d_cursor = nullptr, *d_slab = nullptr;
+  u32 *d_hist = nullptr, *d_meta = nullptr, *d_recv = nullptr, *d_order = nullptr, *d_ww = nullptr;
   if (n_rows) {
-    R->d_hist = (u32*)ctx->dalloc(4 * M1);
-    R->d_cursor = (u64*)ctx->dalloc(8 * M1);
-    R->d_meta = (u32*)ctx->dalloc(16);
-    R->d_recv = (u32*)ctx->dalloc(4ull * n_rows);
-    R->d_order = (u32*)ctx->dalloc(4 * 64 * W);
-    R->d_ww = (u32*)ctx->dalloc(4 * W);
-    R->d_slab = (u64*)ctx->dalloc(8 * 64 * NB * W);
-    if (!R->d_hist || !R->d_cursor || !R->d_meta || !R->d_recv || !R->d_order || !R->d_ww || !R->d_slab)
-      return ctx->fail(KMX_E_NOMEM, "kmx_gram: device allocation failed (send the body in runs of rows)");
+    d_hist = (u32*)R->tmp(4 * M1);
+    d_cursor = (u64*)R->tmp(8 * M1);
+    d_meta = (u32*)R->tmp(16);
+    d_recv = (u32*)R->tmp(4ull * n_rows);
+    d_order = (u32*)R->tmp(4 * 64 * W);
+    d_ww = (u32*)R->tmp(4 * W);
+    d_slab = (u64*)R->tmp(8 * 64 * NB * W);
+    if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_gram: device allocation failed (send the body in runs of rows)");
   }
-  const u32* d_wt = R->d_par + 1;
-  const u8* d_lst = reinterpret_cast<const u8*>(R->d_par + 1 + M1);
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_par, R->h_par, 4 * par_words, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    for (int i = 0; i < 5; i++) KMX_HIP(ctx, hipEventCreate(&R->ev[i]));
-    KMX_HIP(ctx, hipEventRecord(R->ev[0], st));
-  }
-  if (R->d_table_own) KMX_HIP(ctx, hipMemsetAsync(R->d_table_own, 0, 8 * table, st));
+  const u32* d_wt = d_par + 1;
+  const u8* d_lst = reinterpret_cast<const u8*>(d_par + 1 + M1);
+  KMX_HIP(ctx, hipMemcpyAsync(d_par, R->h_par, 4 * par_words, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R, 5);      // ev: start, behind score + fold, behind the order, behind the slab, end
+  if (rc != KMX_OK) return rc;
+  if (own) KMX_HIP(ctx, hipMemsetAsync(R->d_table, 0, 8 * table, st));
   const u32 cus = gr_cus(ctx);
   const u32 cap = gr_grid(GR_MAX_GRID);
   if (n_rows) {
-    KMX_HIP(ctx, hipMemsetAsync(R->d_hist, 0, 4 * M1, st));
-    KMX_HIP(ctx, hipMemsetAsync(R->d_order, 0xFF, 4 * 64 * W, st));
+    KMX_HIP(ctx, hipMemsetAsync(d_hist, 0, 4 * M1, st));
+    KMX_HIP(ctx, hipMemsetAsync(d_order, 0xFF, 4 * 64 * W, st));
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has GR_WAVES_PER_SIMD waves a SIMD to hide the loads
-    const u32 L = gr_pow2_at_or_above(units, 64);
-    u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)cus * 4 * GR_WAVES_PER_SIMD) RW >>= 1;
-    const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, std::min<u64>((u64)cus * GR_WGS_PER_CU, cap));
+    const RowPlan p = mat_row_plan(units, n_rows, cus, GR_WAVES_PER_SIMD);
+    const u32 grid = (u32)std::min<u64>((p.chunks + 3) / 4, std::min<u64>((u64)cus * GR_WGS_PER_CU, cap));
     const u32 use_lds = M1 <= GR_LDS_WORDS;
     const size_t lds = use_lds ? (size_t)(4 * M1) : 0;
-    if (count) hipLaunchKernelGGL(k_gram_score<true>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW, d_lst,
-                                  T->min_abund, use_lds, R->d_hist, R->d_recv);
-    else hipLaunchKernelGGL(k_gram_score<false>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW, d_lst,
-                            T->min_abund, use_lds, R->d_hist, R->d_recv);
+    if (count) hipLaunchKernelGGL(k_gram_score<true>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW, d_lst,
+                                  T->min_abund, use_lds, d_hist, d_recv);
+    else hipLaunchKernelGGL(k_gram_score<false>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW, d_lst,
+                            T->min_abund, use_lds, d_hist, d_recv);
     KMX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_gram_fold, dim3(1), dim3(256), 0, st, (const u32*)R->d_hist, d_wt, M, W, R->d_cursor, R->d_meta);
+    hipLaunchKernelGGL(k_gram_fold, dim3(1), dim3(256), 0, st, (const u32*)d_hist, d_wt, M, W, d_cursor, d_meta);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[1], st));
   if (n_rows) {
     const u64 tiles = ((u64)n_rows + 255) / 256;
-    hipLaunchKernelGGL(k_gram_order, dim3((u32)std::min<u64>(tiles, cap)), dim3(256), 0, st, (const u32*)R->d_recv, n_rows, M, d_wt, R->d_cursor, 64 * W, R->d_order);
+    hipLaunchKernelGGL(k_gram_order, dim3((u32)std::min<u64>(tiles, cap)), dim3(256), 0, st, (const u32*)d_recv, n_rows, M, d_wt, d_cursor, 64 * W, d_order);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[2], st));
@@ -451,9 +406,9 @@ static int gram_queue(kmx_ctx* ctx, const kmx_gram_task* T, kmx_gram_result* R)
     const u64 n_tiles = W * ct_n;
     const u32 grid = (u32)std::min<u64>((n_tiles + 3) / 4, cap);
     if (count) hipLaunchKernelGGL(k_gram_slab<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, NB, M, W, ct_n, d_lst, T->min_abund,
-                                  (const u32*)R->d_order, (const u32*)R->d_recv, d_wt, (const u32*)R->d_meta, R->d_slab, R->d_ww);
+                                  (const u32*)d_order, (const u32*)d_recv, d_wt, (const u32*)d_meta, d_slab, d_ww);
     else hipLaunchKernelGGL(k_gram_slab<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, NB, M, W, ct_n, d_lst, T->min_abund,
-                            (const u32*)R->d_order, (const u32*)R->d_recv, d_wt, (const u32*)R->d_meta, R->d_slab, R->d_ww);
+                            (const u32*)d_order, (const u32*)d_recv, d_wt, (const u32*)d_meta, d_slab, d_ww);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[3], st));
@@ -461,101 +416,30 @@ static int gram_queue(kmx_ctx* ctx, const kmx_gram_task* T, kmx_gram_result* R)
     u32 runs = 1; u64 run_len = GP_CH;
     gr_runs(W, pairs, cus, &runs, &run_len);
     const u64 items = pairs * runs;
-    hipLaunchKernelGGL(k_gram_pairs, dim3((u32)std::min<u64>(items, cap)), dim3(256), 0, st, (const u64*)R->d_slab, (const u32*)R->d_ww, (const u32*)R->d_meta, W, N, NB,
+    hipLaunchKernelGGL(k_gram_pairs, dim3((u32)std::min<u64>(items, cap)), dim3(256), 0, st, (const u64*)d_slab, (const u32*)d_ww, (const u32*)d_meta, W, N, NB,
                        runs, run_len, items, R->d_table);
     KMX_HIP(ctx, hipGetLastError());
-    KMX_HIP(ctx, hipMemcpyAsync(R->h_par, R->d_meta, 4, hipMemcpyDeviceToHost, st));      // (for algo_bytes; nothing on the device waits for it)
+    KMX_HIP(ctx, hipMemcpyAsync(R->h_par, d_meta, 4, hipMemcpyDeviceToHost, st));      // (for algo_bytes; nothing on the device waits for it)
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[4], st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R);
 }
 
-static int gram_call(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = gram_check(ctx, task, who, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_gram_result* R = new kmx_gram_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->n_cols = task->n_cols; R->n_use = task->n_use; R->row_bytes = row_bytes;
-  kmx_gram_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); gram_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = gram_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_gram_dev(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_gram_dev", "kmx_gram", gram_check, gram_queue); }
+extern "C" int kmx_gram_host(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_gram_host", "kmx_gram", gram_check, gram_queue); }
 
-extern "C" int kmx_gram_dev(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out) { return gram_call(ctx, task, out, false, "kmx_gram_dev"); }
-extern "C" int kmx_gram_host(kmx_ctx* ctx, const kmx_gram_task* task, kmx_gram_result** out) { return gram_call(ctx, task, out, true, "kmx_gram_host"); }
-
-extern "C" int kmx_gram_result_wait(kmx_gram_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_gram: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; the table stays
-  kmx_ctx* c = R->ctx;
-  void** blocks[] = {(void**)&R->d_cursor, (void**)&R->d_slab, (void**)&R->d_par, (void**)&R->d_hist, (void**)&R->d_meta, (void**)&R->d_recv, (void**)&R->d_order,
-                     (void**)&R->d_ww, &R->d_in};
-  for (void** p : blocks) { c->dfree(*p); *p = nullptr; }
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t* kmx_gram_result_table_dev(kmx_gram_result* R) { return R && kmx_gram_result_wait(R) == KMX_OK ? (uint64_t*)R->d_table : nullptr; }
+extern "C" int kmx_gram_result_wait(kmx_gram_result* R) { return mat_wait(R); }
+extern "C" uint64_t* kmx_gram_result_table_dev(kmx_gram_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_table : nullptr; }
 extern "C" int kmx_gram_result_copy_table(kmx_gram_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_gram_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  const u64 entries = (u64)R->n_cols * R->n_cols;
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!host_dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, host_dst, R->d_table, 8 * entries);
-}
-extern "C" double kmx_gram_result_kernel_ms(kmx_gram_result* R)
-{
-  if (!R || !R->ev[0] || !R->ev[4] || kmx_gram_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev[0], R->ev[4]) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_table, (u64)R->n_cols * R->n_cols, 8) : KMX_E_INVAL; }
+extern "C" double kmx_gram_result_kernel_ms(kmx_gram_result* R) { return mat_kernel_ms(R); }
 extern "C" int kmx_gram_result_kernel_parts_ms(kmx_gram_result* R, double* score_ms, double* order_ms, double* slab_ms, double* pairs_ms)
-{
-  double* o[4] = {score_ms, order_ms, slab_ms, pairs_ms};
-  for (double* p : o) if (p) *p = -1.0;
-  if (!R) return KMX_E_INVAL;
-  if (!R->ev[0] || !R->ev[4] || kmx_gram_result_wait(R) != KMX_OK) return KMX_OK;
-  for (int i = 0; i < 4; i++) {
-    float ms = 0;
-    if (o[i] && hipEventElapsedTime(&ms, R->ev[i], R->ev[i + 1]) == hipSuccess) *o[i] = (double)ms;
-  }
-  return KMX_OK;
-}
+{ return mat_kernel_parts_ms(R, {score_ms, order_ms, slab_ms, pairs_ms}); }
 extern "C" uint64_t kmx_gram_result_algo_bytes(kmx_gram_result* R)
 {
-  if (!R || kmx_gram_result_wait(R) != KMX_OK) return 0;
+  if (mat_wait(R) != KMX_OK) return 0;
   const u64 NB = ((u64)R->n_cols + 63) / 64, wu = R->n_rows ? R->h_par[0] : 0;
-  return 2 * (u64)R->n_rows * R->row_bytes + 16ull * R->n_rows + 2 * 8 * 64 * NB * wu + 8ull * R->n_cols * R->n_cols;
+  return 2 * R->n_rows * R->row_bytes + 16ull * R->n_rows + 2 * 8 * 64 * NB * wu + 8ull * R->n_cols * R->n_cols;
 }
-extern "C" void kmx_gram_result_free(kmx_gram_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  gram_release(R);
-}
+extern "C" void kmx_gram_result_free(kmx_gram_result* R) { mat_free(R); }

@@ -12,6 +12,9 @@ typedef uint16_t u16;
 typedef uint8_t u8;
 // explicit global address space for record streams (global_load instead of flat_load)
 typedef __attribute__((address_space(1))) const u32 gu32;
+// matrix rows start at any byte
+struct __attribute__((packed, aligned(1))) UDword { u32 v; };      // a dword at any address: one global_load_dword
+struct __attribute__((packed, aligned(1))) UShort { u16 v; };      // two bytes at any address: one global_load_ushort
 
 // ---- merge task as the kernels see it (one per partition, array in HBM) ----------------------
 struct Seg {            // one row segment of a COUNT/PA task: rows [row_off, row_off + nrows) of the arena

@@ -276,7 +276,8 @@ struct kmx_ctx {
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-// ---- test knobs of the matrix tools' launch heuristics (diff, select, filter, combine, dist, the four sequence queries), read per call.
+// ---- test knobs of the matrix tools' launch heuristics (diff, select, filter, combine, dist, the four sequence queries: KMX_PLAN_CUS and
+//      KMX_MAX_GRID; pan, colors, gram and assoc each have a pair of their own, KMX_PAN_CUS / KMX_PAN_GRID, ...), read per call.
 //      They make a small input take the launch shape of a large one; none of those kernels waits on another workgroup, so any grid is
 //      a correct one.  The merge, count and super-k-mer paths size scratch and look-back chains by the real CU count: not for them.
 inline long kmx_env_int(const char* name)      // the variable as a whole decimal integer; -1: unset or anything else
@@ -287,18 +288,20 @@ inline long kmx_env_int(const char* name)      // the variable as a whole decima
   const long v = strtol(s, &end, 10);
   return *end == 0 ? v : -1;
 }
-// KMX_PLAN_CUS=c: the CU count the heuristics plan for, 1 <= c <= the device's (it may only lower the count)
-inline int kmx_plan_cus(const kmx_ctx* ctx)
+// <name>=c: the CU count the heuristics plan for, 1 <= c <= the device's (it may only lower the count)
+inline int kmx_env_cus(const char* name, const kmx_ctx* ctx)
 {
-  const long c = kmx_env_int("KMX_PLAN_CUS");
+  const long c = kmx_env_int(name);
   return c >= 1 && c <= (long)ctx->n_cu ? (int)c : ctx->n_cu;
 }
-// KMX_MAX_GRID=g: the cap on the workgroups of a launch whose kernel strides over its work, 1 <= g <= the built-in cap
-inline kmx::u32 kmx_grid_cap(kmx::u32 dflt)
+// <name>=g: the cap on the workgroups of a launch whose kernel strides over its work, 1 <= g <= the built-in cap
+inline kmx::u32 kmx_env_grid(const char* name, kmx::u64 dflt)
 {
-  const long g = kmx_env_int("KMX_MAX_GRID");
-  return g >= 1 && g <= (long)dflt ? (kmx::u32)g : dflt;
+  const long g = kmx_env_int(name);
+  return (kmx::u32)(g >= 1 && (kmx::u64)g <= dflt ? (kmx::u64)g : dflt);
 }
+inline int kmx_plan_cus(const kmx_ctx* ctx) { return kmx_env_cus("KMX_PLAN_CUS", ctx); }
+inline kmx::u32 kmx_grid_cap(kmx::u32 dflt) { return kmx_env_grid("KMX_MAX_GRID", dflt); }
 
 struct StageClock {     // KMX_TRACE=1: per-stage wall times of the batched count on stderr
   const char* name; bool on; hipStream_t st; std::chrono::steady_clock::time_point t0; std::string log;

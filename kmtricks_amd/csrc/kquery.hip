@@ -130,7 +130,6 @@ void k_kquery_search(u64* __restrict__ recs, const u32* __restrict__ pstart, u32
   if ((threadIdx.x & 63u) == 0 && met) atomicAdd(n_found, met);
 }
 
-struct __attribute__((packed, aligned(1))) KQDword { u32 v; };      // a dword at any address: one global_load_dword
 
 // LOG_L: log2 of the lanes of a group; SUMS: the u64 count sums are asked for
 template <int LOG_L, bool SUMS>
@@ -175,7 +174,7 @@ void k_kquery_gather(const u64* __restrict__ recs, const u32* __restrict__ pstar
         for (u32 j = 0; j < KQ_COLS; j++) {
           const u32 col = c0 + j * L;
           if (col < n_cols) {
-            const u32 x = reinterpret_cast<const KQDword*>(rp + 4ull * col)->v;
+            const u32 x = reinterpret_cast<const UDword*>(rp + 4ull * col)->v;
             h[j] += x != 0;
             s[j] += x;
           }

@@ -27,7 +27,7 @@
 // and b + (bytes loaded) <= row_bytes - skip, both tested by the lane that loads; nothing is loaded in wider pieces than the piece that
 // is tested and nothing is rounded to an aligned address.  Every (row, rec) that k_pan_shared takes from the order is tested again
 // (row < n_rows, rec <= M) before it becomes an address.  The launch knobs of this file are its own: KMX_PAN_CUS and KMX_PAN_GRID.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -42,7 +42,6 @@ constexpr u32 PN_WAVES_PER_SIMD = 8;      // chunks of long rows are made small 
 constexpr u32 PN_RUN = 256;               // places of the order a workgroup of k_pan_shared sums before it must flush
 constexpr u32 PN_BLOCK = 256;             // units of a row a workgroup of k_pan_shared takes: a lane a unit
 
-struct __attribute__((packed, aligned(1))) PDword { u32 v; };      // a dword at any address: one global_load_dword
 static_assert(sizeof(kmx_pan_task) == 64, "kmx_pan_task is 64 bytes");
 
 // ordt: the ordinal of every input column in the list, PN_NONE where it is not listed, 8 * ceil(N / 8) entries.
@@ -73,7 +72,7 @@ void k_pan_score(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 ski
         const u8* q = rows + row * row_bytes + skip;
         for (u64 un = u; un < units; un += L) {
           if (COUNT) {
-            const u32 v = reinterpret_cast<const PDword*>(q + 4 * un)->v;
+            const u32 v = reinterpret_cast<const UDword*>(q + 4 * un)->v;
             const u32 o = ordt[un];
             const bool pres = v >= a;
             acc += (u32)(pres && o != PN_NONE);
@@ -222,7 +221,7 @@ void k_pan_shared(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 sk
         v[k] = 0;
         if (e[k].y) {
           const u8* src = q + (u64)e[k].x * row_bytes;
-          if (COUNT) v[k] = reinterpret_cast<const PDword*>(src)->v >= a; else v[k] = (u32)*src & m;
+          if (COUNT) v[k] = reinterpret_cast<const UDword*>(src)->v >= a; else v[k] = (u32)*src & m;
         }
       }
 #pragma unroll
@@ -240,132 +239,86 @@ void k_pan_shared(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 sk
   }
 }
 
-static u32 pn_pow2_at_or_above(u64 x, u32 cap) { u32 p = 1; while (p < cap && p < x) p <<= 1; return p; }
-// KMX_PAN_CUS=c: the CU count the launches plan for, 1 <= c <= the device's (it may only lower the count)
-static u32 pn_cus(const kmx_ctx* ctx)
-{
-  const long c = kmx_env_int("KMX_PAN_CUS"), n = std::max(ctx->n_cu, 1);
-  return (u32)(c >= 1 && c <= n ? c : n);
-}
-// KMX_PAN_GRID=g: the cap on the workgroups of a launch whose kernel strides over its work, 1 <= g <= the built-in cap
-static u32 pn_grid(u64 dflt)
-{
-  const long g = kmx_env_int("KMX_PAN_GRID");
-  return (u32)(g >= 1 && (u64)g <= dflt ? (u64)g : dflt);
-}
+static u32 pn_cus(const kmx_ctx* ctx) { return (u32)std::max(kmx_env_cus("KMX_PAN_CUS", ctx), 1); }
+static u32 pn_grid(u64 dflt) { return kmx_env_grid("KMX_PAN_GRID", dflt); }
 
 }  // namespace kmx
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_pan_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_cols = 0, n_use = 0;
-  u64 row_bytes = 0;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_pan_result : MatResult {
+  u32 n_use = 0;
   bool want_shared = false;
-  u64 *d_spec_own = nullptr, *d_spec = nullptr, *d_shared_own = nullptr, *d_shared = nullptr, *d_loc = nullptr;
-  u32 *d_ordt = nullptr, *d_cursor = nullptr, *d_recv = nullptr;
-  uint2* d_order = nullptr;
-  u32* h_ordt = nullptr;                // page-locked: the ordinal table on its way up
-  void* d_in = nullptr;                 // kmx_pan_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev[4] = {};      // ev: start, behind score + fold, behind the order, end
-  bool waited = false; int status = KMX_OK;
+  u64 *d_spec = nullptr, *d_shared = nullptr;
 };
 
 static int pan_check(kmx_ctx* ctx, const kmx_pan_task* T, const char* who, u64* row_bytes)
 {
-  const std::string w(who);
+  const MatCheck c{ctx, who};
   const u32 N = T->n_cols, M = T->n_use;
-  if (N == 0 || M == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column, and so has the list");
-  if (T->mode == KMX_MODE_BF || T->mode == KMX_MODE_BFC || T->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported: a Bloom row is a hash bit, its recurrence is not a k-mer's (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->key_words < 1 || T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (T->min_abund == 0) return ctx->fail(KMX_E_INVAL, w + ": min_abund must be at least 1");
-  if (T->min_abund > 1 && T->mode == KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": min_abund above 1 needs counts");
-  if (T->flags & ~(u32)KMX_PAN_SHARED) return ctx->fail(KMX_E_INVAL, w + ": unknown flag bits");
-  if (T->shared && !(T->flags & KMX_PAN_SHARED)) return ctx->fail(KMX_E_INVAL, w + ": a shared table without KMX_PAN_SHARED");
-  if (M > N) return ctx->fail(KMX_E_INVAL, w + ": more listed columns than input columns");
-  if (!T->cols && M != N) return ctx->fail(KMX_E_INVAL, w + ": cols = NULL is the identity and needs n_use = n_cols");
-  *row_bytes = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * N : ((u64)N + 7) / 8);
-  if (*row_bytes > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (T->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if ((T->flags & KMX_PAN_SHARED) && ((u64)M + 1) * N >= (1ull << 30)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": a shared table of 8 GiB and more");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  if (T->cols) {
-    std::vector<u32> s(T->cols, T->cols + M);
-    std::sort(s.begin(), s.end());
-    if (s.back() >= N) return ctx->fail(KMX_E_INVAL, w + ": a column index at or above n_cols");
-    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return ctx->fail(KMX_E_INVAL, w + ": a column is listed twice");
-  }
-  return KMX_OK;
-}
-
-static void pan_release(kmx_pan_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_spec_own, R->d_shared_own, R->d_loc, R->d_ordt, R->d_cursor, R->d_recv, R->d_order, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_ordt);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev[0], R->ev[1], R->ev[2], R->ev[3]}) if (e) (void)hipEventDestroy(e);
-  delete R;
+  int rc;
+  if ((rc = c.n_cols(N, M, "list")) || (rc = c.no_bloom(T->mode, ": a Bloom row is a hash bit, its recurrence is not a k-mer's")) || (rc = c.mode(T->mode)) ||
+      (rc = c.key_words(T->key_words)) || (rc = c.min_abund(T->min_abund, T->mode)) || (rc = c.flags(T->flags, KMX_PAN_SHARED))) return rc;
+  if (T->shared && !(T->flags & KMX_PAN_SHARED)) return c.no(KMX_E_INVAL, ": a shared table without KMX_PAN_SHARED");
+  if ((rc = c.list_fits(M, N, "listed")) || (rc = c.identity(T->cols, M, N, "n_use"))) return rc;
+  *row_bytes = MatCheck::row_bytes(T->key_words, T->mode, N);
+  if ((rc = c.row_fits(*row_bytes)) || (rc = c.n_rows(T->n_rows))) return rc;
+  if ((T->flags & KMX_PAN_SHARED) && ((u64)M + 1) * N >= (1ull << 30)) return c.no(KMX_E_UNSUPPORTED, ": a shared table of 8 GiB and more");
+  if ((rc = c.rows(T->n_rows, T->rows))) return rc;
+  return c.col_list(T->cols, M, N);
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
 static int pan_queue(kmx_ctx* ctx, const kmx_pan_task* T, kmx_pan_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, M = T->n_use, skip = 8 * T->key_words, n_rows = R->n_rows;
-  const bool count = T->mode == KMX_MODE_COUNT, sh = R->want_shared;
+  const u32 N = T->n_cols, M = R->n_use = T->n_use, skip = 8 * T->key_words, n_rows = (u32)R->n_rows;
+  const bool count = T->mode == KMX_MODE_COUNT, sh = R->want_shared = (T->flags & KMX_PAN_SHARED) != 0;
   const u32 units = count ? N : (u32)(((u64)N + 7) / 8);
   const u64 M1 = (u64)M + 1, n_ord = ((u64)N + 7) / 8 * 8, spec_bytes = 24 * M1, shared_bytes = 8 * M1 * N;
-  if (!(R->h_ordt = (u32*)ctx->halloc(4 * n_ord))) return ctx->fail(KMX_E_NOMEM, "kmx_pan: host allocation failed");
-  for (u64 i = 0; i < n_ord; i++) R->h_ordt[i] = !T->cols && i < N ? (u32)i : PN_NONE;
-  if (T->cols) for (u32 j = 0; j < M; j++) R->h_ordt[T->cols[j]] = j;
-  R->d_ordt = (u32*)ctx->dalloc(4 * n_ord);
-  R->d_loc = (u64*)ctx->dalloc(spec_bytes);
-  R->d_spec = (u64*)T->spectrum;
-  if (!R->d_spec) R->d_spec = R->d_spec_own = (u64*)ctx->dalloc(spec_bytes);
-  if (!R->d_ordt || !R->d_loc || !R->d_spec) return ctx->fail(KMX_E_NOMEM, "kmx_pan: device allocation failed");
+  u32* h_ordt = (u32*)R->pin(4 * n_ord);      // page-locked: the ordinal table on its way up
+  if (!h_ordt) return ctx->fail(KMX_E_NOMEM, "kmx_pan: host allocation failed");
+  for (u64 i = 0; i < n_ord; i++) h_ordt[i] = !T->cols && i < N ? (u32)i : PN_NONE;
+  if (T->cols) for (u32 j = 0; j < M; j++) h_ordt[T->cols[j]] = j;
+  // a table of the call's own starts at zero; one the caller handed in is on neither list
+  const bool own_spec = !T->spectrum, own_shared = sh && !T->shared;
+  u32* d_ordt = (u32*)R->tmp(4 * n_ord);
+  u64* d_loc = (u64*)R->tmp(spec_bytes);
+  R->d_spec = own_spec ? (u64*)R->keep(spec_bytes) : (u64*)T->spectrum;
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_pan: device allocation failed");
+  u32 *d_cursor = nullptr, *d_recv = nullptr; uint2* d_order = nullptr;
   if (sh) {
-    R->d_shared = (u64*)T->shared;
-    if (!R->d_shared) R->d_shared = R->d_shared_own = (u64*)ctx->dalloc(shared_bytes);
-    R->d_cursor = (u32*)ctx->dalloc(4 * M1);
-    if (n_rows) { R->d_recv = (u32*)ctx->dalloc(4ull * n_rows); R->d_order = (uint2*)ctx->dalloc(8ull * n_rows); }
-    if (!R->d_shared || !R->d_cursor || (n_rows && (!R->d_recv || !R->d_order)))
-      return ctx->fail(KMX_E_NOMEM, "kmx_pan: device allocation failed (send the body in runs of rows)");
+    R->d_shared = own_shared ? (u64*)R->keep(shared_bytes) : (u64*)T->shared;
+    d_cursor = (u32*)R->tmp(4 * M1);
+    if (n_rows) { d_recv = (u32*)R->tmp(4ull * n_rows); d_order = (uint2*)R->tmp(8ull * n_rows); }
+    if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_pan: device allocation failed (send the body in runs of rows)");
   }
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_ordt, R->h_ordt, 4 * n_ord, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    for (int i = 0; i < 4; i++) KMX_HIP(ctx, hipEventCreate(&R->ev[i]));
-    KMX_HIP(ctx, hipEventRecord(R->ev[0], st));
-  }
-  if (R->d_spec_own) KMX_HIP(ctx, hipMemsetAsync(R->d_spec_own, 0, spec_bytes, st));
-  if (R->d_shared_own) KMX_HIP(ctx, hipMemsetAsync(R->d_shared_own, 0, shared_bytes, st));
+  KMX_HIP(ctx, hipMemcpyAsync(d_ordt, h_ordt, 4 * n_ord, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R, 4);      // ev: start, behind score + fold, behind the order, end
+  if (rc != KMX_OK) return rc;
+  if (own_spec) KMX_HIP(ctx, hipMemsetAsync(R->d_spec, 0, spec_bytes, st));
+  if (own_shared) KMX_HIP(ctx, hipMemsetAsync(R->d_shared, 0, shared_bytes, st));
   const u32 cus = pn_cus(ctx);
   if (n_rows) {
-    KMX_HIP(ctx, hipMemsetAsync(R->d_loc, 0, spec_bytes, st));
+    KMX_HIP(ctx, hipMemsetAsync(d_loc, 0, spec_bytes, st));
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has PN_WAVES_PER_SIMD waves a SIMD to hide the loads
-    const u32 L = pn_pow2_at_or_above(units, 64);
-    u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)cus * 4 * PN_WAVES_PER_SIMD) RW >>= 1;
-    const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, pn_grid(std::min<u64>((u64)cus * PN_WGS_PER_CU, PN_MAX_GRID)));
+    const RowPlan p = mat_row_plan(units, n_rows, cus, PN_WAVES_PER_SIMD);
+    const u32 grid = (u32)std::min<u64>((p.chunks + 3) / 4, pn_grid(std::min<u64>((u64)cus * PN_WGS_PER_CU, PN_MAX_GRID)));
     const u32 use_lds = 3 * M1 <= PN_LDS_WORDS;
     const size_t lds = use_lds ? (size_t)(12 * M1) : 0;
-    if (count) hipLaunchKernelGGL(k_pan_score<true>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW,
-                                  (const u32*)R->d_ordt, T->min_abund, use_lds, R->d_loc, R->d_recv);
-    else hipLaunchKernelGGL(k_pan_score<false>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, L, RW,
-                            (const u32*)R->d_ordt, T->min_abund, use_lds, R->d_loc, R->d_recv);
+    if (count) hipLaunchKernelGGL(k_pan_score<true>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW,
+                                  (const u32*)d_ordt, T->min_abund, use_lds, d_loc, d_recv);
+    else hipLaunchKernelGGL(k_pan_score<false>, dim3(grid), dim3(256), lds, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, p.L, p.RW,
+                            (const u32*)d_ordt, T->min_abund, use_lds, d_loc, d_recv);
     KMX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_pan_fold, dim3(1), dim3(256), 0, st, (const u64*)R->d_loc, M, R->d_spec, sh ? R->d_cursor : (u32*)nullptr);
+    hipLaunchKernelGGL(k_pan_fold, dim3(1), dim3(256), 0, st, (const u64*)d_loc, M, R->d_spec, sh ? d_cursor : (u32*)nullptr);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[1], st));
   if (n_rows && sh) {
     const u64 tiles = ((u64)n_rows + 255) / 256;
-    hipLaunchKernelGGL(k_pan_order, dim3((u32)std::min<u64>(tiles, pn_grid(PN_MAX_GRID))), dim3(256), 0, st, (const u32*)R->d_recv, n_rows, M, R->d_cursor, R->d_order);
+    hipLaunchKernelGGL(k_pan_order, dim3((u32)std::min<u64>(tiles, pn_grid(PN_MAX_GRID))), dim3(256), 0, st, (const u32*)d_recv, n_rows, M, d_cursor, d_order);
     KMX_HIP(ctx, hipGetLastError());
   }
   if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[2], st));
@@ -373,106 +326,34 @@ static int pan_queue(kmx_ctx* ctx, const kmx_pan_task* T, kmx_pan_result* R)
     const u32 n_blocks = (units + PN_BLOCK - 1) / PN_BLOCK;
     const u64 work = (((u64)n_rows + PN_RUN - 1) / PN_RUN) * n_blocks;
     const u32 grid = (u32)std::min<u64>(work, pn_grid(PN_MAX_GRID));
-    if (count) hipLaunchKernelGGL(k_pan_shared<true>, dim3(grid), dim3(PN_BLOCK), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, (const u32*)R->d_ordt,
-                                  T->min_abund, (const uint2*)R->d_order, n_blocks, R->d_shared);
-    else hipLaunchKernelGGL(k_pan_shared<false>, dim3(grid), dim3(PN_BLOCK), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, (const u32*)R->d_ordt,
-                            T->min_abund, (const uint2*)R->d_order, n_blocks, R->d_shared);
+    if (count) hipLaunchKernelGGL(k_pan_shared<true>, dim3(grid), dim3(PN_BLOCK), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, (const u32*)d_ordt,
+                                  T->min_abund, (const uint2*)d_order, n_blocks, R->d_shared);
+    else hipLaunchKernelGGL(k_pan_shared<false>, dim3(grid), dim3(PN_BLOCK), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, M, (const u32*)d_ordt,
+                            T->min_abund, (const uint2*)d_order, n_blocks, R->d_shared);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev[3], st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R);
 }
 
-static int pan_call(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 row_bytes = 0;
-  int rc = pan_check(ctx, task, who, &row_bytes);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_pan_result* R = new kmx_pan_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->n_cols = task->n_cols; R->n_use = task->n_use; R->row_bytes = row_bytes;
-  R->want_shared = (task->flags & KMX_PAN_SHARED) != 0;
-  kmx_pan_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); pan_release(R); return code; };
-  const u64 bytes = task->n_rows * row_bytes;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = pan_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_pan_dev(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_pan_dev", "kmx_pan", pan_check, pan_queue); }
+extern "C" int kmx_pan_host(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_pan_host", "kmx_pan", pan_check, pan_queue); }
 
-extern "C" int kmx_pan_dev(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out) { return pan_call(ctx, task, out, false, "kmx_pan_dev"); }
-extern "C" int kmx_pan_host(kmx_ctx* ctx, const kmx_pan_task* task, kmx_pan_result** out) { return pan_call(ctx, task, out, true, "kmx_pan_host"); }
-
-extern "C" int kmx_pan_result_wait(kmx_pan_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_pan: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; the tables stay
-  kmx_ctx* c = R->ctx;
-  void** blocks[] = {(void**)&R->d_loc, (void**)&R->d_ordt, (void**)&R->d_cursor, (void**)&R->d_recv, (void**)&R->d_order, &R->d_in};
-  for (void** p : blocks) { c->dfree(*p); *p = nullptr; }
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t* kmx_pan_result_spectrum_dev(kmx_pan_result* R) { return R && kmx_pan_result_wait(R) == KMX_OK ? (uint64_t*)R->d_spec : nullptr; }
-extern "C" uint64_t* kmx_pan_result_shared_dev(kmx_pan_result* R) { return R && kmx_pan_result_wait(R) == KMX_OK ? (uint64_t*)R->d_shared : nullptr; }
-static int pan_copy_out(kmx_pan_result* R, uint64_t* dst, uint64_t dst_entries, const u64* src, u64 entries)
-{
-  const int rc = kmx_pan_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (!src) return R->ctx->fail(KMX_E_INVAL, "kmx_pan_result_copy_shared: the call was made without KMX_PAN_SHARED");
-  if (dst_entries < entries) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, 8 * entries);
-}
+extern "C" int kmx_pan_result_wait(kmx_pan_result* R) { return mat_wait(R); }
+extern "C" uint64_t* kmx_pan_result_spectrum_dev(kmx_pan_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_spec : nullptr; }
+extern "C" uint64_t* kmx_pan_result_shared_dev(kmx_pan_result* R) { return mat_wait(R) == KMX_OK ? (uint64_t*)R->d_shared : nullptr; }
 extern "C" int kmx_pan_result_copy_spectrum(kmx_pan_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? pan_copy_out(R, host_dst, dst_entries, R->d_spec, 3 * ((u64)R->n_use + 1)) : KMX_E_INVAL; }
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_spec, 3 * ((u64)R->n_use + 1), 8) : KMX_E_INVAL; }
 extern "C" int kmx_pan_result_copy_shared(kmx_pan_result* R, uint64_t* host_dst, uint64_t dst_entries)
-{ return R ? pan_copy_out(R, host_dst, dst_entries, R->d_shared, ((u64)R->n_use + 1) * R->n_cols) : KMX_E_INVAL; }
-extern "C" double kmx_pan_result_kernel_ms(kmx_pan_result* R)
-{
-  if (!R || !R->ev[0] || !R->ev[3] || kmx_pan_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev[0], R->ev[3]) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_shared, ((u64)R->n_use + 1) * R->n_cols, 8, "kmx_pan_result_copy_shared: the call was made without KMX_PAN_SHARED") : KMX_E_INVAL; }
+extern "C" double kmx_pan_result_kernel_ms(kmx_pan_result* R) { return mat_kernel_ms(R); }
 extern "C" int kmx_pan_result_kernel_parts_ms(kmx_pan_result* R, double* score_ms, double* order_ms, double* shared_ms)
-{
-  double* o[3] = {score_ms, order_ms, shared_ms};
-  for (double* p : o) if (p) *p = -1.0;
-  if (!R) return KMX_E_INVAL;
-  if (!R->ev[0] || !R->ev[3] || kmx_pan_result_wait(R) != KMX_OK) return KMX_OK;
-  for (int i = 0; i < 3; i++) {
-    float ms = 0;
-    if (o[i] && (i == 0 || R->want_shared) && hipEventElapsedTime(&ms, R->ev[i], R->ev[i + 1]) == hipSuccess) *o[i] = (double)ms;
-  }
-  return KMX_OK;
-}
+{ return mat_kernel_parts_ms(R, {score_ms, order_ms, shared_ms}, R && R->want_shared ? 7u : 1u); }
 extern "C" uint64_t kmx_pan_result_algo_bytes(kmx_pan_result* R)
 {
-  if (!R || kmx_pan_result_wait(R) != KMX_OK) return 0;
-  const u64 M1 = (u64)R->n_use + 1, body = (u64)R->n_rows * R->row_bytes;
+  if (mat_wait(R) != KMX_OK) return 0;
+  const u64 M1 = (u64)R->n_use + 1, body = R->n_rows * R->row_bytes;
   return body + 24 * M1 + (R->want_shared ? body + 24ull * R->n_rows + 8 * M1 * R->n_cols : 0);
 }
-extern "C" void kmx_pan_result_free(kmx_pan_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  pan_release(R);
-}
+extern "C" void kmx_pan_result_free(kmx_pan_result* R) { mat_free(R); }

@@ -98,7 +98,6 @@ void k_query_scatter(const u64* __restrict__ keys, const u64* __restrict__ offse
   }
 }
 
-struct __attribute__((packed, aligned(1))) QDword { u32 v; };      // a dword at any address: one global_load_dword
 
 // LOG_L: log2 of the lanes of a group (a group's lane wl owns the row's dwords wl, wl + L, ...)
 // KEYED: the rows of a k-mer matrix (kquery.hip) -- a record's row lies at row * stride + skip (the nb presence/absence bytes behind the
@@ -152,7 +151,7 @@ void k_query_gather(const u64* __restrict__ recs, const u32* __restrict__ pstart
         const u8* rp = KEYED ? base + (u64)(u32)rec * stride + skip + 4u * ws
                              : base + (u64)(u32)rec * nb + 4u * ws;      // 64-bit row offsets: window * nb passes 4 GiB
         u32 x;
-        if (whole) x = reinterpret_cast<const QDword*>(rp)->v;
+        if (whole) x = reinterpret_cast<const UDword*>(rp)->v;
         else { x = 0; for (u32 b = 0; 4u * ws + b < nb; b++) x |= (u32)rp[b] << (8u * b); }
         x &= cmask;
 #pragma unroll

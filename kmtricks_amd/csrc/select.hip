@@ -23,7 +23,7 @@
 // and b + (bytes loaded) <= row_bytes - skip (or rows + r * row_bytes + b inside the key), both tested by the lane that loads; nothing
 // is loaded in wider pieces than the piece that is tested and nothing is rounded to an aligned address.  No store lies outside the kept
 // rows.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -36,7 +36,6 @@ constexpr u32 SL_WAVES_PER_SIMD = 8;      // chunks of long rows are made small 
 constexpr u32 SL_LOADS_PER_WG = 8192;     // gathered loads a mover's workgroup aims at: a tile is shared by tile loads / this many
 constexpr u32 SL_NONE = 0xFFFFFFFFu;      // the padding of the column list: no column (N <= 2^32 - 1)
 
-struct __attribute__((packed, aligned(1))) SDword { u32 v; };      // a dword at any address: one global_load_dword
 
 struct SelRec { u32 row, rec; };      // kmx_select_rec
 static_assert(sizeof(SelRec) == 8 && sizeof(kmx_select_rec) == 8, "a record is 8 bytes");
@@ -68,7 +67,7 @@ void k_select_score(const u8* __restrict__ rows, u32 n_rows, u64 row_bytes, u32 
         u32 i = 0;
         for (u64 un = u; un < units; un += L, i++) {
           if (COUNT) {
-            const u32 v = reinterpret_cast<const SDword*>(q + 4 * un)->v;
+            const u32 v = reinterpret_cast<const UDword*>(q + 4 * un)->v;
             const u32 f = i < 32 ? (gp >> i) & 1u : (u32)(sel[un] != 0);
             acc += f & (u32)(v >= a);
           } else {
@@ -130,10 +129,10 @@ void k_select_move_cc(const u8* __restrict__ rows, u32 n_rows, u64 irb, u32 N, u
         if (small) { r = (u32)e / odw; c = (u32)e - r * odw; } else { r = (u32)(e / odw); c = (u32)(e - (u64)r * odw); }
         const u8* src = tile_rows + (u64)s_src[r] * irb;      // (s_src[r] is a row below n_rows: sl_tile_ranks)
         u32 v = 0;
-        if (c < kd) v = reinterpret_cast<const SDword*>(src + 4ull * c)->v;
+        if (c < kd) v = reinterpret_cast<const UDword*>(src + 4ull * c)->v;
         else {
           const u32 col = cols[c - kd];
-          if (col < N) { v = reinterpret_cast<const SDword*>(src + 4ull * kd + 4ull * col)->v; if (v < zb) v = 0; }
+          if (col < N) { v = reinterpret_cast<const UDword*>(src + 4ull * kd + 4ull * col)->v; if (v < zb) v = 0; }
         }
         dst[e] = v;
       }
@@ -174,7 +173,7 @@ void k_select_move_pa(const u8* __restrict__ rows, u32 n_rows, u64 irb, u32 N, u
           for (u32 k = 0; k < 8; k++) {
             const u32 col = cj[k];
             if (col < N) {
-              if (COUNT) x |= (u32)(reinterpret_cast<const SDword*>(pay + 4ull * col)->v >= a) << k;
+              if (COUNT) x |= (u32)(reinterpret_cast<const UDword*>(pay + 4ull * col)->v >= a) << k;
               else x |= (((u32)pay[col >> 3] >> (col & 7u)) & 1u) << k;
             }
           }
@@ -206,235 +205,123 @@ void k_select_place(const u32* __restrict__ keep, const u32* __restrict__ recv, 
   }
 }
 
-static u32 sl_pow2_at_or_above(u64 x, u32 cap) { u32 p = 1; while (p < cap && p < x) p <<= 1; return p; }
-
 }  // namespace kmx
 
 using namespace kmx;
 
-// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-struct kmx_select_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0;
-  u64 irb = 0, orb = 0;
-  u32 *d_keep = nullptr, *d_recv = nullptr, *d_tiles = nullptr;
+// ---- C ABI: the shared host path is matrix_host.hpp ------------------------------------------------------------------------------------
+struct kmx_select_result : MatResult {
+  u64 orb = 0;                          // bytes of an output row (row_bytes: of an input row)
   SelRec* d_recs = nullptr;
-  u8 *d_sel = nullptr, *d_out = nullptr;
-  u8* h_tab = nullptr;                  // page-locked: the selection table, then the column list, on their way up
-  u32* h_tot = nullptr;                 // page-locked: kept rows
-  void* d_in = nullptr;                 // kmx_select_host: the upload
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
+  u8* d_out = nullptr;
 };
 
-static bool sl_is_bloom(u32 m) { return m == KMX_MODE_BF || m == KMX_MODE_BFC || m == KMX_MODE_BFT; }
-
-static int select_check(kmx_ctx* ctx, const kmx_select_task* T, const char* who, u64* irb, u64* orb)
+static int select_check(kmx_ctx* ctx, const kmx_select_task* T, const char* who, u64* irb)
 {
-  const std::string w(who);
+  const MatCheck c{ctx, who};
   const u32 N = T->n_cols, M = T->n_out;
-  if (N == 0 || M == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column, and so has the selection");
-  if (sl_is_bloom(T->mode)) return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter bodies are not supported: a Bloom row's identity is its position (KMX_MODE_COUNT and KMX_MODE_PA only)");
-  if (T->mode != KMX_MODE_COUNT && T->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->out_mode != KMX_MODE_COUNT && T->out_mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": out_mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (T->mode == KMX_MODE_PA && T->out_mode == KMX_MODE_COUNT) return ctx->fail(KMX_E_INVAL, w + ": counts cannot be made out of presence/absence rows");
-  if (T->key_words < 1 || T->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (T->min_abund == 0) return ctx->fail(KMX_E_INVAL, w + ": min_abund must be at least 1");
-  if (T->min_abund > 1 && T->mode == KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": min_abund above 1 needs counts");
-  if (T->flags & ~(u32)KMX_SELECT_ZERO_BELOW) return ctx->fail(KMX_E_INVAL, w + ": unknown flag bits");
-  if ((T->flags & KMX_SELECT_ZERO_BELOW) && T->out_mode != KMX_MODE_COUNT) return ctx->fail(KMX_E_INVAL, w + ": KMX_SELECT_ZERO_BELOW needs a COUNT output");
-  if (M > N) return ctx->fail(KMX_E_INVAL, w + ": more output columns than input columns");
-  if (!T->cols && M != N) return ctx->fail(KMX_E_INVAL, w + ": cols = NULL is the identity and needs n_out = n_cols");
-  *irb = 8ull * T->key_words + (T->mode == KMX_MODE_COUNT ? 4ull * N : ((u64)N + 7) / 8);
-  *orb = 8ull * T->key_words + (T->out_mode == KMX_MODE_COUNT ? 4ull * M : ((u64)M + 7) / 8);
-  if (*irb > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (T->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (send the body in runs of rows)");
-  if (T->n_rows && !T->rows) return ctx->fail(KMX_E_INVAL, w + ": null rows");
-  if (T->cols) {
-    std::vector<u32> s(T->cols, T->cols + M);
-    std::sort(s.begin(), s.end());
-    if (s.back() >= N) return ctx->fail(KMX_E_INVAL, w + ": a column index at or above n_cols");
-    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return ctx->fail(KMX_E_INVAL, w + ": a column is listed twice");
-  }
-  return KMX_OK;
-}
-
-static void select_release(kmx_select_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_keep, R->d_recv, R->d_tiles, R->d_recs, R->d_sel, R->d_out, R->d_in};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_tab); c->hfree(R->h_tot);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
+  int rc;
+  if ((rc = c.n_cols(N, M, "selection")) || (rc = c.no_bloom(T->mode, ": a Bloom row's identity is its position")) || (rc = c.mode(T->mode))) return rc;
+  if (T->out_mode != KMX_MODE_COUNT && T->out_mode != KMX_MODE_PA) return c.no(KMX_E_INVAL, ": out_mode must be KMX_MODE_COUNT or KMX_MODE_PA");
+  if (T->mode == KMX_MODE_PA && T->out_mode == KMX_MODE_COUNT) return c.no(KMX_E_INVAL, ": counts cannot be made out of presence/absence rows");
+  if ((rc = c.key_words(T->key_words)) || (rc = c.min_abund(T->min_abund, T->mode)) || (rc = c.flags(T->flags, KMX_SELECT_ZERO_BELOW))) return rc;
+  if ((T->flags & KMX_SELECT_ZERO_BELOW) && T->out_mode != KMX_MODE_COUNT) return c.no(KMX_E_INVAL, ": KMX_SELECT_ZERO_BELOW needs a COUNT output");
+  if ((rc = c.list_fits(M, N, "output")) || (rc = c.identity(T->cols, M, N, "n_out"))) return rc;
+  *irb = MatCheck::row_bytes(T->key_words, T->mode, N);
+  if ((rc = c.row_fits(*irb)) || (rc = c.n_rows(T->n_rows)) || (rc = c.rows(T->n_rows, T->rows))) return rc;
+  return c.col_list(T->cols, M, N);
 }
 
 // the kernels of one call, queued on ctx->stream; T->rows a device pointer
 static int select_queue(kmx_ctx* ctx, const kmx_select_task* T, kmx_select_result* R)
 {
   hipStream_t st = ctx->stream;
-  const u32 N = T->n_cols, M = T->n_out, kw = T->key_words, skip = 8 * kw, n_rows = R->n_rows, tiles = filter_tiles(n_rows);
+  const u32 N = T->n_cols, M = T->n_out, kw = T->key_words, skip = 8 * kw, n_rows = (u32)R->n_rows, tiles = filter_tiles(n_rows);
   const bool count = T->mode == KMX_MODE_COUNT, out_count = T->out_mode == KMX_MODE_COUNT, zb = (T->flags & KMX_SELECT_ZERO_BELOW) != 0;
   const u32 units = count ? N : (u32)(((u64)N + 7) / 8);
+  R->orb = MatCheck::row_bytes(kw, T->out_mode, M);
   // an output row is the input row: k_filter_move takes it whole (PA: only without padding bits, which must leave as 0)
   const bool whole = !T->cols && T->mode == T->out_mode && !zb && (count || N % 8 == 0);
   const u64 sel_bytes = ((u64)units + 3) & ~3ull, n_list = whole ? 0 : ((u64)M + 7) & ~7ull;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_tab = (u8*)ctx->halloc(sel_bytes + 4 * n_list + 4))) return ctx->fail(KMX_E_NOMEM, "kmx_select: host allocation failed");
+  u8* h_tab;      // page-locked: the selection table, then the column list, on their way up
+  if (!(R->h_tot = (u32*)R->pin(64)) || !(h_tab = (u8*)R->pin(sel_bytes + 4 * n_list + 4))) return ctx->fail(KMX_E_NOMEM, "kmx_select: host allocation failed");
   R->h_tot[0] = 0;
   // per input column: is it selected?  (PA: as a mask per payload byte -- bit i & 7 of byte i >> 3; the padding bits stay 0)
-  u32* h_cols = reinterpret_cast<u32*>(R->h_tab + sel_bytes);
+  u32* h_cols = reinterpret_cast<u32*>(h_tab + sel_bytes);
   if (!T->cols) {
-    if (count) memset(R->h_tab, 1, N);
-    else { memset(R->h_tab, 0xFF, units); if (N % 8) R->h_tab[units - 1] = (u8)((1u << (N % 8)) - 1u); }
+    if (count) memset(h_tab, 1, N);
+    else { memset(h_tab, 0xFF, units); if (N % 8) h_tab[units - 1] = (u8)((1u << (N % 8)) - 1u); }
   } else {
-    memset(R->h_tab, 0, sel_bytes);
-    for (u32 j = 0; j < M; j++) { const u32 c = T->cols[j]; if (count) R->h_tab[c] = 1; else R->h_tab[c >> 3] |= (u8)(1u << (c & 7)); }
+    memset(h_tab, 0, sel_bytes);
+    for (u32 j = 0; j < M; j++) { const u32 c = T->cols[j]; if (count) h_tab[c] = 1; else h_tab[c >> 3] |= (u8)(1u << (c & 7)); }
   }
   for (u64 j = 0; j < n_list; j++) h_cols[j] = j < M ? (T->cols ? T->cols[j] : (u32)j) : SL_NONE;
-  R->d_keep = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_recv = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_tiles = (u32*)ctx->dalloc(4ull * ((u64)tiles + 1));
-  R->d_recs = (SelRec*)ctx->dalloc(sizeof(SelRec) * (u64)n_rows);      // every row kept
-  R->d_out = (u8*)ctx->dalloc((u64)n_rows * R->orb + 16);
-  R->d_sel = (u8*)ctx->dalloc(sel_bytes + 4 * n_list + 4);           // the table, and behind it (at a multiple of 4) the list
-  if (!R->d_keep || !R->d_recv || !R->d_tiles || !R->d_recs || !R->d_out || !R->d_sel)
-    return ctx->fail(KMX_E_NOMEM, "kmx_select: device allocation failed (send the body in runs of rows)");
-  const u32* d_cols = reinterpret_cast<const u32*>(R->d_sel + sel_bytes);
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_sel, R->h_tab, sel_bytes + 4 * n_list, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_tiles, 0, 4ull * ((u64)tiles + 1), st));
+  u32* d_keep = (u32*)R->tmp(4ull * n_rows);
+  u32* d_recv = (u32*)R->tmp(4ull * n_rows);
+  u32* d_tiles = (u32*)R->keep(4ull * ((u64)tiles + 1));
+  R->d_recs = (SelRec*)R->keep(sizeof(SelRec) * (u64)n_rows);      // every row kept
+  R->d_out = (u8*)R->keep((u64)n_rows * R->orb + 16);
+  u8* d_sel = (u8*)R->tmp(sel_bytes + 4 * n_list + 4);             // the table, and behind it (at a multiple of 4) the list
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_select: device allocation failed (send the body in runs of rows)");
+  const u32* d_cols = reinterpret_cast<const u32*>(d_sel + sel_bytes);
+  KMX_HIP(ctx, hipMemcpyAsync(d_sel, h_tab, sel_bytes + 4 * n_list, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_tiles, 0, 4ull * ((u64)tiles + 1), st));
   const u32 max_rec = T->max_rec >= M ? 0xFFFFFFFFu : T->max_rec;
   if (n_rows) {
     // rows of 64 units and more get a wave each; their chunks shrink until the chip has SL_WAVES_PER_SIMD waves a SIMD to hide the loads
-    const u32 L = sl_pow2_at_or_above(units, 64);
-    u32 RW = 64;
-    if (L == 64) while (RW > 4 && (u64)n_rows / RW < (u64)std::max(kmx_plan_cus(ctx), 1) * 4 * SL_WAVES_PER_SIMD) RW >>= 1;
-    const u64 chunks = ((u64)n_rows + RW - 1) / RW;
-    const u32 grid = (u32)std::min<u64>((chunks + 3) / 4, kmx_grid_cap(SL_MAX_GRID));
-    if (count) hipLaunchKernelGGL(k_select_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->irb, skip, N, L, RW, (const u8*)R->d_sel,
-                                  T->min_abund, T->min_rec, max_rec, R->d_keep, R->d_recv, R->d_tiles);
-    else hipLaunchKernelGGL(k_select_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->irb, skip, N, L, RW, (const u8*)R->d_sel,
-                            T->min_abund, T->min_rec, max_rec, R->d_keep, R->d_recv, R->d_tiles);
+    const RowPlan p = mat_row_plan(units, n_rows, (u32)std::max(kmx_plan_cus(ctx), 1), SL_WAVES_PER_SIMD);
+    const u32 grid = (u32)std::min<u64>((p.chunks + 3) / 4, kmx_grid_cap(SL_MAX_GRID));
+    if (count) hipLaunchKernelGGL(k_select_score<true>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, p.L, p.RW, (const u8*)d_sel,
+                                  T->min_abund, T->min_rec, max_rec, d_keep, d_recv, d_tiles);
+    else hipLaunchKernelGGL(k_select_score<false>, dim3(grid), dim3(256), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, skip, N, p.L, p.RW, (const u8*)d_sel,
+                            T->min_abund, T->min_rec, max_rec, d_keep, d_recv, d_tiles);
     KMX_HIP(ctx, hipGetLastError());
   }
-  KMX_HIP(ctx, launch_filter_scan(R->d_tiles, tiles, st));
+  KMX_HIP(ctx, launch_filter_scan(d_tiles, tiles, st));
   if (n_rows) {
-    if (whole) KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->irb, R->irb, R->d_keep, R->d_keep, R->d_tiles, R->d_out, st));
+    if (whole) KMX_HIP(ctx, launch_filter_move((const u8*)T->rows, n_rows, R->row_bytes, R->row_bytes, d_keep, d_keep, d_tiles, R->d_out, st));
     else {
       // gathered loads of a tile with every row kept: the key's units, then one a count (-> COUNT) or eight a payload byte (-> PA)
       const u64 loads = (u64)SL_TILE * (out_count ? 2ull * kw + M : 8ull * kw + 8ull * (((u64)M + 7) / 8));
       const u32 S = (u32)std::min<u64>(std::max<u64>((loads + SL_LOADS_PER_WG - 1) / SL_LOADS_PER_WG, 1), 1024);
       const u32 grid = (u32)std::min<u64>((u64)tiles * S, kmx_grid_cap(SL_MAX_GRID));
       const u32 ob = (u32)(((u64)M + 7) / 8);
-      if (out_count) hipLaunchKernelGGL(k_select_move_cc, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->irb, N, 2 * kw, M, d_cols,
-                                        zb ? T->min_abund : 0u, (const u32*)R->d_keep, (const u32*)R->d_tiles, S, (u32*)R->d_out);
-      else if (count) hipLaunchKernelGGL(k_select_move_pa<true>, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->irb, N, skip, ob, d_cols,
-                                         T->min_abund, (const u32*)R->d_keep, (const u32*)R->d_tiles, S, R->d_out);
-      else hipLaunchKernelGGL(k_select_move_pa<false>, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->irb, N, skip, ob, d_cols,
-                              T->min_abund, (const u32*)R->d_keep, (const u32*)R->d_tiles, S, R->d_out);
+      if (out_count) hipLaunchKernelGGL(k_select_move_cc, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, N, 2 * kw, M, d_cols,
+                                        zb ? T->min_abund : 0u, (const u32*)d_keep, (const u32*)d_tiles, S, (u32*)R->d_out);
+      else if (count) hipLaunchKernelGGL(k_select_move_pa<true>, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, N, skip, ob, d_cols,
+                                         T->min_abund, (const u32*)d_keep, (const u32*)d_tiles, S, R->d_out);
+      else hipLaunchKernelGGL(k_select_move_pa<false>, dim3(grid), dim3(SL_TILE), 0, st, (const u8*)T->rows, n_rows, R->row_bytes, N, skip, ob, d_cols,
+                              T->min_abund, (const u32*)d_keep, (const u32*)d_tiles, S, R->d_out);
       KMX_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_select_place, dim3(std::min(tiles, kmx_grid_cap(SL_MAX_GRID))), dim3(SL_TILE), 0, st, (const u32*)R->d_keep, (const u32*)R->d_recv, n_rows,
-                       (const u32*)R->d_tiles, R->d_recs);
+    hipLaunchKernelGGL(k_select_place, dim3(std::min(tiles, kmx_grid_cap(SL_MAX_GRID))), dim3(SL_TILE), 0, st, (const u32*)d_keep, (const u32*)d_recv, n_rows,
+                       (const u32*)d_tiles, R->d_recs);
     KMX_HIP(ctx, hipGetLastError());
   }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_tiles + tiles, 4, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
+  return mat_queue_tail(R, d_tiles + tiles);
 }
 
-static int select_call(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out, bool host, const char* who)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
-  *out = nullptr;
-  u64 irb = 0, orb = 0;
-  int rc = select_check(ctx, task, who, &irb, &orb);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_select_result* R = new kmx_select_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->irb = irb; R->orb = orb;
-  kmx_select_task dt = *task;
-  auto fail = [&](int code) { if (host) (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); select_release(R); return code; };
-  const u64 bytes = task->n_rows * irb;
-  if (host && bytes) {
-    if (!(R->d_in = ctx->dalloc(bytes))) return fail(ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)"));
-    hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-    if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e)));
-    dt.rows = R->d_in;
-  }
-  if ((rc = select_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
+extern "C" int kmx_select_dev(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out)
+{ return mat_call(ctx, task, out, false, "kmx_select_dev", "kmx_select", select_check, select_queue); }
+extern "C" int kmx_select_host(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out)
+{ return mat_call(ctx, task, out, true, "kmx_select_host", "kmx_select", select_check, select_queue); }
 
-extern "C" int kmx_select_dev(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out) { return select_call(ctx, task, out, false, "kmx_select_dev"); }
-extern "C" int kmx_select_host(kmx_ctx* ctx, const kmx_select_task* task, kmx_select_result** out) { return select_call(ctx, task, out, true, "kmx_select_host"); }
-
-extern "C" int kmx_select_result_wait(kmx_select_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_select: ") + hipGetErrorString(e));
-  // the call has run: the scratch and the upload go back to the pool; the kept rows and their records stay
-  kmx_ctx* c = R->ctx;
-  c->dfree(R->d_keep); R->d_keep = nullptr;
-  c->dfree(R->d_recv); R->d_recv = nullptr;
-  c->dfree(R->d_sel); R->d_sel = nullptr;
-  c->dfree(R->d_in); R->d_in = nullptr;
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_select_result_rows(kmx_select_result* R) { return R && kmx_select_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" int kmx_select_result_wait(kmx_select_result* R) { return mat_wait(R); }
+extern "C" uint64_t kmx_select_result_rows(kmx_select_result* R) { return mat_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
 extern "C" uint64_t kmx_select_result_row_bytes(const kmx_select_result* R) { return R ? R->orb : 0; }
 extern "C" uint64_t kmx_select_result_body_bytes(kmx_select_result* R) { return R ? kmx_select_result_rows(R) * R->orb : 0; }
-extern "C" const void* kmx_select_result_body_dev(kmx_select_result* R) { return R && kmx_select_result_wait(R) == KMX_OK ? R->d_out : nullptr; }
-extern "C" const kmx_select_rec* kmx_select_result_recs_dev(kmx_select_result* R) { return R && kmx_select_result_wait(R) == KMX_OK ? (const kmx_select_rec*)R->d_recs : nullptr; }
-static int select_copy_out(kmx_select_result* R, void* dst, uint64_t dst_bytes, const void* src, u64 bytes)
-{
-  if (dst_bytes < bytes) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!bytes) return KMX_OK;
-  if (!dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, dst, src, bytes);
-}
+extern "C" const void* kmx_select_result_body_dev(kmx_select_result* R) { return mat_wait(R) == KMX_OK ? R->d_out : nullptr; }
+extern "C" const kmx_select_rec* kmx_select_result_recs_dev(kmx_select_result* R) { return mat_wait(R) == KMX_OK ? (const kmx_select_rec*)R->d_recs : nullptr; }
 extern "C" int kmx_select_result_copy_body(kmx_select_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_select_result_wait(R);
-  return rc != KMX_OK ? rc : select_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_select_result_body_bytes(R));
-}
+{ return R ? mat_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_select_result_body_bytes(R), 1) : KMX_E_INVAL; }
 extern "C" int kmx_select_result_copy_recs(kmx_select_result* R, kmx_select_rec* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_select_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  if (dst_entries < R->h_tot[0]) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  return select_copy_out(R, host_dst, ~0ull, R->d_recs, sizeof(SelRec) * (u64)R->h_tot[0]);
-}
-extern "C" double kmx_select_result_kernel_ms(kmx_select_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_select_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
+{ return R ? mat_copy_out(R, host_dst, dst_entries, R->d_recs, kmx_select_result_rows(R), sizeof(SelRec)) : KMX_E_INVAL; }
+extern "C" double kmx_select_result_kernel_ms(kmx_select_result* R) { return mat_kernel_ms(R); }
 extern "C" uint64_t kmx_select_result_algo_bytes(kmx_select_result* R)
 {
-  if (!R || kmx_select_result_wait(R) != KMX_OK) return 0;
-  return (u64)R->n_rows * R->irb + (u64)R->h_tot[0] * (R->orb + sizeof(SelRec));
+  if (mat_wait(R) != KMX_OK) return 0;
+  return R->n_rows * R->row_bytes + (u64)R->h_tot[0] * (R->orb + sizeof(SelRec));
 }
-extern "C" void kmx_select_result_free(kmx_select_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  select_release(R);
-}
+extern "C" void kmx_select_result_free(kmx_select_result* R) { mat_free(R); }

@@ -54,7 +54,6 @@ void k_zquery_scatter(const u64* __restrict__ keys, u64 n_bases, QChunks ch, u32
   }
 }
 
-struct __attribute__((packed, aligned(1))) ZDword { u32 v; };      // a dword at any address: one global_load_dword
 
 // LOG_L: log2 of the lanes of a group (a group's lane wl owns the row's dwords wl, wl + L, ...)
 template <int LOG_L>
@@ -85,7 +84,7 @@ void k_zquery_rows(const u64* __restrict__ recs, const u32* __restrict__ pstart,
         const u32 col0 = 32u * ws;
         const u32 cmask = n_cols - col0 >= 32u ? 0xFFFFFFFFu : (1u << (n_cols - col0)) - 1u;      // the padding bits never reach the table
         u32 x;
-        if (4u * ws + 4u <= nb) x = reinterpret_cast<const ZDword*>(rp)->v;
+        if (4u * ws + 4u <= nb) x = reinterpret_cast<const UDword*>(rp)->v;
         else { x = 0; for (u32 b = 0; 4u * ws + b < nb; b++) x |= (u32)rp[b] << (8u * b); }      // nothing behind a body is read
         dst[ws] = x & cmask;
       }

@@ -1425,439 +1425,12 @@ class QueryOutput:
         self.n_kmers, self.hits, self.kernel_ms, self.algo_bytes = n_kmers, hits, kernel_ms, algo_bytes
 
 
-class DistOutput:
-    """inter uint64[n_cols, n_cols]: rows that hold both samples (the table the call added to, when one was given); mins
-    uint64[n_cols, n_cols] (None unless asked for): the sums of the smaller count; kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, inter, mins, kernel_ms, algo_bytes):
-        self.inter, self.mins, self.kernel_ms, self.algo_bytes = inter, mins, kernel_ms, algo_bytes
-
-
-class DistResult:
-    def __init__(self, ctx, h, n_cols, has_mins):
-        self._ctx, self._h, self._n, self._mins = ctx, h, n_cols, has_mins
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_dist_result_wait(self._h), "kmx_dist_result_wait")
-
-    def inter_dev(self):
-        return _lib.kmx_dist_result_inter_dev(self._h)
-
-    def mins_dev(self):
-        return _lib.kmx_dist_result_mins_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_dist_result_kernel_ms(self._h)
-
-    def kernel_parts_ms(self):
-        """(clearing + k_dist_slab, k_dist_pairs, k_dist_mins) in ms; -1 where unavailable"""
-        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
-        self._ctx._check(_lib.kmx_dist_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_dist_result_kernel_parts_ms")
-        return a.value, b.value, c.value
-
-    def algo_bytes(self):
-        return _lib.kmx_dist_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        inter = np.zeros((self._n, self._n), np.uint64)
-        self._ctx._check(_lib.kmx_dist_result_copy_inter(self._h, inter.ctypes.data, inter.size), "kmx_dist_result_copy_inter")
-        mins = None
-        if self._mins:
-            mins = np.zeros((self._n, self._n), np.uint64)
-            self._ctx._check(_lib.kmx_dist_result_copy_mins(self._h, mins.ctypes.data, mins.size), "kmx_dist_result_copy_mins")
-        return DistOutput(inter, mins, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_dist_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class ColsumsResult:
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_colsums_result_wait(self._h), "kmx_colsums_result_wait")
-
-    def sums_dev(self):
-        return _lib.kmx_colsums_result_sums_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_colsums_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_colsums_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        sums = np.zeros(self._n, np.uint64)
-        self._ctx._check(_lib.kmx_colsums_result_copy_sums(self._h, sums.ctypes.data, sums.size), "kmx_colsums_result_copy_sums")
-        return sums
-
-    def free(self):
-        if self._h:
-            _lib.kmx_colsums_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DiffOutput:
-    """body: the kept rows, whole and in the input's order (bytes); recs: one DIFF_REC (kmx_diff_rec, 40 bytes) per kept row in the
-    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, body, recs, kernel_ms, algo_bytes):
-        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
-
-
-class DiffResult:
-    def __init__(self, ctx, h):
-        self._ctx, self._h = ctx, h
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_diff_result_wait(self._h), "kmx_diff_result_wait")
-
-    def rows(self):
-        return _lib.kmx_diff_result_rows(self._h)
-
-    def row_bytes(self):
-        return _lib.kmx_diff_result_row_bytes(self._h)
-
-    def body_bytes(self):
-        return _lib.kmx_diff_result_body_bytes(self._h)
-
-    def body_dev(self):
-        return _lib.kmx_diff_result_body_dev(self._h)
-
-    def recs_dev(self):
-        return _lib.kmx_diff_result_recs_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_diff_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_diff_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        body = np.zeros(self.body_bytes(), np.uint8)
-        self._ctx._check(_lib.kmx_diff_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_diff_result_copy_body")
-        recs = np.zeros(self.rows(), DIFF_REC)
-        self._ctx._check(_lib.kmx_diff_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_diff_result_copy_recs")
-        return DiffOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_diff_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class AssocOutput:
-    """body: the kept rows, whole and in the input's order (bytes); recs: one ASSOC_REC (kmx_assoc_rec, 32 bytes) per kept row in the
-    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, body, recs, kernel_ms, algo_bytes):
-        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
-
-
-class AssocResult:
-    def __init__(self, ctx, h):
-        self._ctx, self._h = ctx, h
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_assoc_result_wait(self._h), "kmx_assoc_result_wait")
-
-    def rows(self):
-        return _lib.kmx_assoc_result_rows(self._h)
-
-    def row_bytes(self):
-        return _lib.kmx_assoc_result_row_bytes(self._h)
-
-    def body_bytes(self):
-        return _lib.kmx_assoc_result_body_bytes(self._h)
-
-    def body_dev(self):
-        return _lib.kmx_assoc_result_body_dev(self._h)
-
-    def recs_dev(self):
-        return _lib.kmx_assoc_result_recs_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_assoc_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_assoc_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        body = np.zeros(self.body_bytes(), np.uint8)
-        self._ctx._check(_lib.kmx_assoc_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_assoc_result_copy_body")
-        recs = np.zeros(self.rows(), ASSOC_REC)
-        self._ctx._check(_lib.kmx_assoc_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_assoc_result_copy_recs")
-        return AssocOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_assoc_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class PanOutput:
-    """spectrum uint64[3, M + 1]: rows by recurrence, by first ordinal, by first missing ordinal (the table the call added to, when one
-    was given); shared uint64[M + 1, n_cols] (None unless asked for): rows of recurrence r that input column c holds; kernel_ms < 0
-    without set_profiling"""
-
-    def __init__(self, spectrum, shared, kernel_ms, algo_bytes):
-        self.spectrum, self.shared, self.kernel_ms, self.algo_bytes = spectrum, shared, kernel_ms, algo_bytes
-
-
-class PanResult:
-    def __init__(self, ctx, h, n_cols, n_use, has_shared):
-        self._ctx, self._h, self._n, self._m, self._shared = ctx, h, n_cols, n_use, has_shared
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_pan_result_wait(self._h), "kmx_pan_result_wait")
-
-    def spectrum_dev(self):
-        return _lib.kmx_pan_result_spectrum_dev(self._h)
-
-    def shared_dev(self):
-        return _lib.kmx_pan_result_shared_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_pan_result_kernel_ms(self._h)
-
-    def kernel_parts_ms(self):
-        """(clearing + k_pan_score + k_pan_fold, k_pan_order, k_pan_shared) in ms; -1 where unavailable"""
-        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
-        self._ctx._check(_lib.kmx_pan_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_pan_result_kernel_parts_ms")
-        return a.value, b.value, c.value
-
-    def algo_bytes(self):
-        return _lib.kmx_pan_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        spectrum = np.zeros((3, self._m + 1), np.uint64)
-        self._ctx._check(_lib.kmx_pan_result_copy_spectrum(self._h, spectrum.ctypes.data, spectrum.size), "kmx_pan_result_copy_spectrum")
-        shared = None
-        if self._shared:
-            shared = np.zeros((self._m + 1, self._n), np.uint64)
-            self._ctx._check(_lib.kmx_pan_result_copy_shared(self._h, shared.ctypes.data, shared.size), "kmx_pan_result_copy_shared")
-        return PanOutput(spectrum, shared, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_pan_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class GramOutput:
-    """table uint64[n_cols, n_cols]: the class weights summed over the rows that hold both samples (the table the call added to, when
-    one was given); kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, table, kernel_ms, algo_bytes):
-        self.table, self.kernel_ms, self.algo_bytes = table, kernel_ms, algo_bytes
-
-
-class GramResult:
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_gram_result_wait(self._h), "kmx_gram_result_wait")
-
-    def table_dev(self):
-        return _lib.kmx_gram_result_table_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_gram_result_kernel_ms(self._h)
-
-    def kernel_parts_ms(self):
-        """(clearing + k_gram_score + k_gram_fold, k_gram_order, k_gram_slab, k_gram_pairs) in ms; -1 where unavailable"""
-        p = [C.c_double(-1) for _ in range(4)]
-        self._ctx._check(_lib.kmx_gram_result_kernel_parts_ms(self._h, *[C.byref(x) for x in p]), "kmx_gram_result_kernel_parts_ms")
-        return tuple(x.value for x in p)
-
-    def algo_bytes(self):
-        return _lib.kmx_gram_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        table = np.zeros((self._n, self._n), np.uint64)
-        self._ctx._check(_lib.kmx_gram_result_copy_table(self._h, table.ctypes.data, table.size), "kmx_gram_result_copy_table")
-        return GramOutput(table, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_gram_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class ColorsOutput:
-    """n_classes C; ids uint32[n_rows]: the class of every row; first uint32[C]: a class's first row; sizes uint32[C]: its rows;
-    patterns uint64[C, W]: ordinal j of the list = bit j & 63 of word j >> 6; kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, n_classes, ids, first, sizes, patterns, kernel_ms, algo_bytes):
-        self.n_classes, self.ids, self.first, self.sizes, self.patterns = n_classes, ids, first, sizes, patterns
-        self.kernel_ms, self.algo_bytes = kernel_ms, algo_bytes
-
-
-class ColorsResult:
-    def __init__(self, ctx, h, n_rows, n_use):
-        self._ctx, self._h, self._rows, self._w = ctx, h, n_rows, (n_use + 63) // 64
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_colors_result_wait(self._h), "kmx_colors_result_wait")
-
-    def n_classes(self):
-        return _lib.kmx_colors_result_n_classes(self._h)
-
-    def ids_dev(self):
-        return _lib.kmx_colors_result_ids_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_colors_result_kernel_ms(self._h)
-
-    def kernel_parts_ms(self):
-        """(k_col_pack, clearing + k_col_claim, the numbering kernels) in ms; -1 where unavailable"""
-        a, b, c = C.c_double(-1), C.c_double(-1), C.c_double(-1)
-        self._ctx._check(_lib.kmx_colors_result_kernel_parts_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "kmx_colors_result_kernel_parts_ms")
-        return a.value, b.value, c.value
-
-    def algo_bytes(self):
-        return _lib.kmx_colors_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        n = self.n_classes()
-        ids, first, sizes = np.zeros(self._rows, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        patterns = np.zeros((n, self._w), np.uint64)
-        self._ctx._check(_lib.kmx_colors_result_copy_ids(self._h, ids.ctypes.data, ids.size), "kmx_colors_result_copy_ids")
-        self._ctx._check(_lib.kmx_colors_result_copy_first(self._h, first.ctypes.data, first.size), "kmx_colors_result_copy_first")
-        self._ctx._check(_lib.kmx_colors_result_copy_sizes(self._h, sizes.ctypes.data, sizes.size), "kmx_colors_result_copy_sizes")
-        self._ctx._check(_lib.kmx_colors_result_copy_patterns(self._h, patterns.ctypes.data, patterns.size), "kmx_colors_result_copy_patterns")
-        return ColorsOutput(n, ids, first, sizes, patterns, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_colors_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class SelectOutput:
-    """body: the kept rows at their new size, in the input's order (bytes); recs: one SELECT_REC (kmx_select_rec, 8 bytes) per kept row
-    in the same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, body, recs, kernel_ms, algo_bytes):
-        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
-
-
-class SelectResult:
-    def __init__(self, ctx, h):
-        self._ctx, self._h = ctx, h
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_select_result_wait(self._h), "kmx_select_result_wait")
-
-    def rows(self):
-        return _lib.kmx_select_result_rows(self._h)
-
-    def row_bytes(self):
-        return _lib.kmx_select_result_row_bytes(self._h)
-
-    def body_bytes(self):
-        return _lib.kmx_select_result_body_bytes(self._h)
-
-    def body_dev(self):
-        return _lib.kmx_select_result_body_dev(self._h)
-
-    def recs_dev(self):
-        return _lib.kmx_select_result_recs_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_select_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_select_result_algo_bytes(self._h)
-
-    def output(self):
-        self.wait()
-        body = np.zeros(self.body_bytes(), np.uint8)
-        self._ctx._check(_lib.kmx_select_result_copy_body(self._h, body.ctypes.data, body.size), "kmx_select_result_copy_body")
-        recs = np.zeros(self.rows(), SELECT_REC)
-        self._ctx._check(_lib.kmx_select_result_copy_recs(self._h, recs.ctypes.data, recs.size), "kmx_select_result_copy_recs")
-        return SelectOutput(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_select_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class KqueryOutput:
-    """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose k-mer is a row's key with a
-    non-zero count / a set bit in the column; sums uint64[queries, n_cols] (None unless asked for): those rows' counts added up;
-    kernel_ms < 0 without set_profiling"""
-
-    def __init__(self, n_kmers, hits, sums, kernel_ms, algo_bytes):
-        self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
-
-
-class _SeqResult:
-    """what the results of the four sequence-query families share: the calls kmx_<_prefix>_result_<name> of libkmx"""
+class _Result:
+    """what the result wrappers of the matrix tools and of the sequence queries share: the calls kmx_<_prefix>_result_<name> of libkmx"""
     _prefix = None
 
-    def __init__(self, ctx, h, n_cols):
-        self._ctx, self._h, self._n = ctx, h, n_cols
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
 
     def _call(self, name, *args, check=False):
         full = f"kmx_{self._prefix}_result_{name}"
@@ -1869,14 +1442,13 @@ class _SeqResult:
     def wait(self):
         self._call("wait", check=True)
 
-    def n_seqs(self):
-        return self._call("n_seqs")
-
-    def hits_dev(self):
-        return self._call("hits_dev")
-
     def kernel_ms(self):
         return self._call("kernel_ms")
+
+    def _kernel_parts_ms(self, n):
+        p = [C.c_double(-1) for _ in range(n)]
+        self._call("kernel_parts_ms", *[C.byref(x) for x in p], check=True)
+        return tuple(x.value for x in p)
 
     def algo_bytes(self):
         return self._call("algo_bytes")
@@ -1885,13 +1457,6 @@ class _SeqResult:
         """the result's table `name` into array (kmx_..._result_copy_<name>) -> array"""
         self._call("copy_" + name, array.ctypes.data, array.size, check=True)
         return array
-
-    def _tables(self, sums=False):
-        """-> n_kmers uint32[queries], hits uint32[queries, n_cols], sums uint64[queries, n_cols] or None: numpy copies"""
-        self.wait()
-        q = self.n_seqs()
-        return (self._copy("kmers", np.zeros(q, np.uint32)), self._copy("hits", np.zeros((q, self._n), np.uint32)),
-                self._copy("sums", np.zeros((q, self._n), np.uint64)) if sums else None)
 
     def free(self):
         if self._h:
@@ -1903,6 +1468,233 @@ class _SeqResult:
             self.free()
         except Exception:
             pass
+
+
+class _RowsResult(_Result):
+    """a result of kept rows and one record a kept row (diff, assoc, select): _rec the records' dtype, _output the *Output class"""
+    _rec = _output = None
+
+    def rows(self):
+        return self._call("rows")
+
+    def row_bytes(self):
+        return self._call("row_bytes")
+
+    def body_bytes(self):
+        return self._call("body_bytes")
+
+    def body_dev(self):
+        return self._call("body_dev")
+
+    def recs_dev(self):
+        return self._call("recs_dev")
+
+    def output(self):
+        self.wait()
+        body = self._copy("body", np.zeros(self.body_bytes(), np.uint8))
+        recs = self._copy("recs", np.zeros(self.rows(), self._rec))
+        return self._output(body.tobytes(), recs, self.kernel_ms(), self.algo_bytes())
+
+
+class DistOutput:
+    """inter uint64[n_cols, n_cols]: rows that hold both samples (the table the call added to, when one was given); mins
+    uint64[n_cols, n_cols] (None unless asked for): the sums of the smaller count; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, inter, mins, kernel_ms, algo_bytes):
+        self.inter, self.mins, self.kernel_ms, self.algo_bytes = inter, mins, kernel_ms, algo_bytes
+
+class DistResult(_Result):
+    _prefix = "dist"
+
+    def __init__(self, ctx, h, n_cols, has_mins):
+        super().__init__(ctx, h)
+        self._n, self._mins = n_cols, has_mins
+
+    def inter_dev(self):
+        return self._call("inter_dev")
+
+    def mins_dev(self):
+        return self._call("mins_dev")
+
+    def kernel_parts_ms(self):
+        """(clearing + k_dist_slab, k_dist_pairs, k_dist_mins) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(3)
+
+    def output(self):
+        self.wait()
+        inter = self._copy("inter", np.zeros((self._n, self._n), np.uint64))
+        mins = self._copy("mins", np.zeros((self._n, self._n), np.uint64)) if self._mins else None
+        return DistOutput(inter, mins, self.kernel_ms(), self.algo_bytes())
+
+
+class ColsumsResult(_Result):
+    _prefix = "colsums"
+
+    def __init__(self, ctx, h, n_cols):
+        super().__init__(ctx, h)
+        self._n = n_cols
+
+    def sums_dev(self):
+        return self._call("sums_dev")
+
+    def output(self):
+        self.wait()
+        return self._copy("sums", np.zeros(self._n, np.uint64))
+
+
+class DiffOutput:
+    """body: the kept rows, whole and in the input's order (bytes); recs: one DIFF_REC (kmx_diff_rec, 40 bytes) per kept row in the
+    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+class DiffResult(_RowsResult):
+    _prefix, _rec, _output = "diff", DIFF_REC, DiffOutput
+
+
+class AssocOutput:
+    """body: the kept rows, whole and in the input's order (bytes); recs: one ASSOC_REC (kmx_assoc_rec, 32 bytes) per kept row in the
+    same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+class AssocResult(_RowsResult):
+    _prefix, _rec, _output = "assoc", ASSOC_REC, AssocOutput
+
+
+class PanOutput:
+    """spectrum uint64[3, M + 1]: rows by recurrence, by first ordinal, by first missing ordinal (the table the call added to, when one
+    was given); shared uint64[M + 1, n_cols] (None unless asked for): rows of recurrence r that input column c holds; kernel_ms < 0
+    without set_profiling"""
+
+    def __init__(self, spectrum, shared, kernel_ms, algo_bytes):
+        self.spectrum, self.shared, self.kernel_ms, self.algo_bytes = spectrum, shared, kernel_ms, algo_bytes
+
+class PanResult(_Result):
+    _prefix = "pan"
+
+    def __init__(self, ctx, h, n_cols, n_use, has_shared):
+        super().__init__(ctx, h)
+        self._n, self._m, self._shared = n_cols, n_use, has_shared
+
+    def spectrum_dev(self):
+        return self._call("spectrum_dev")
+
+    def shared_dev(self):
+        return self._call("shared_dev")
+
+    def kernel_parts_ms(self):
+        """(clearing + k_pan_score + k_pan_fold, k_pan_order, k_pan_shared) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(3)
+
+    def output(self):
+        self.wait()
+        spectrum = self._copy("spectrum", np.zeros((3, self._m + 1), np.uint64))
+        shared = self._copy("shared", np.zeros((self._m + 1, self._n), np.uint64)) if self._shared else None
+        return PanOutput(spectrum, shared, self.kernel_ms(), self.algo_bytes())
+
+
+class GramOutput:
+    """table uint64[n_cols, n_cols]: the class weights summed over the rows that hold both samples (the table the call added to, when
+    one was given); kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, table, kernel_ms, algo_bytes):
+        self.table, self.kernel_ms, self.algo_bytes = table, kernel_ms, algo_bytes
+
+class GramResult(_Result):
+    _prefix = "gram"
+
+    def __init__(self, ctx, h, n_cols):
+        super().__init__(ctx, h)
+        self._n = n_cols
+
+    def table_dev(self):
+        return self._call("table_dev")
+
+    def kernel_parts_ms(self):
+        """(clearing + k_gram_score + k_gram_fold, k_gram_order, k_gram_slab, k_gram_pairs) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(4)
+
+    def output(self):
+        self.wait()
+        return GramOutput(self._copy("table", np.zeros((self._n, self._n), np.uint64)), self.kernel_ms(), self.algo_bytes())
+
+
+class ColorsOutput:
+    """n_classes C; ids uint32[n_rows]: the class of every row; first uint32[C]: a class's first row; sizes uint32[C]: its rows;
+    patterns uint64[C, W]: ordinal j of the list = bit j & 63 of word j >> 6; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_classes, ids, first, sizes, patterns, kernel_ms, algo_bytes):
+        self.n_classes, self.ids, self.first, self.sizes, self.patterns = n_classes, ids, first, sizes, patterns
+        self.kernel_ms, self.algo_bytes = kernel_ms, algo_bytes
+
+class ColorsResult(_Result):
+    _prefix = "colors"
+
+    def __init__(self, ctx, h, n_rows, n_use):
+        super().__init__(ctx, h)
+        self._rows, self._w = n_rows, (n_use + 63) // 64
+
+    def n_classes(self):
+        return self._call("n_classes")
+
+    def ids_dev(self):
+        return self._call("ids_dev")
+
+    def kernel_parts_ms(self):
+        """(k_col_pack, clearing + k_col_claim, the numbering kernels) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(3)
+
+    def output(self):
+        self.wait()
+        n = self.n_classes()
+        ids = self._copy("ids", np.zeros(self._rows, np.uint32))
+        first, sizes = self._copy("first", np.zeros(n, np.uint32)), self._copy("sizes", np.zeros(n, np.uint32))
+        patterns = self._copy("patterns", np.zeros((n, self._w), np.uint64))
+        return ColorsOutput(n, ids, first, sizes, patterns, self.kernel_ms(), self.algo_bytes())
+
+
+class SelectOutput:
+    """body: the kept rows at their new size, in the input's order (bytes); recs: one SELECT_REC (kmx_select_rec, 8 bytes) per kept row
+    in the same order, a numpy structured array; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, body, recs, kernel_ms, algo_bytes):
+        self.body, self.recs, self.kernel_ms, self.algo_bytes = body, recs, kernel_ms, algo_bytes
+
+class SelectResult(_RowsResult):
+    _prefix, _rec, _output = "select", SELECT_REC, SelectOutput
+
+
+class KqueryOutput:
+    """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose k-mer is a row's key with a
+    non-zero count / a set bit in the column; sums uint64[queries, n_cols] (None unless asked for): those rows' counts added up;
+    kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_kmers, hits, sums, kernel_ms, algo_bytes):
+        self.n_kmers, self.hits, self.sums, self.kernel_ms, self.algo_bytes = n_kmers, hits, sums, kernel_ms, algo_bytes
+
+
+class _SeqResult(_Result):
+    """what the results of the four sequence-query families add: the queries, their hits, their tables as numpy copies"""
+
+    def __init__(self, ctx, h, n_cols):
+        super().__init__(ctx, h)
+        self._n = n_cols
+
+    def n_seqs(self):
+        return self._call("n_seqs")
+
+    def hits_dev(self):
+        return self._call("hits_dev")
+
+    def _tables(self, sums=False):
+        """-> n_kmers uint32[queries], hits uint32[queries, n_cols], sums uint64[queries, n_cols] or None: numpy copies"""
+        self.wait()
+        q = self.n_seqs()
+        return (self._copy("kmers", np.zeros(q, np.uint32)), self._copy("hits", np.zeros((q, self._n), np.uint32)),
+                self._copy("sums", np.zeros((q, self._n), np.uint64)) if sums else None)
 
 
 class KqueryResult(_SeqResult):

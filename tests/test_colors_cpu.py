@@ -208,8 +208,8 @@ def test_colors_hip_has_knobs_of_its_own():
     src = open(os.path.join(csrc, "colors.hip")).read()
     for word in ("kmx_plan_cus", "kmx_grid_cap", "KMX_PLAN_CUS", "KMX_MAX_GRID", "KMX_PAN_"):
         assert word not in src, word
-    for knob in ("KMX_COLORS_CUS", "KMX_COLORS_GRID", "KMX_COLORS_HASH_BITS"):
-        assert f'kmx_env_int("{knob}")' in src
+    for read in ('kmx_env_cus("KMX_COLORS_CUS", ctx)', 'kmx_env_grid("KMX_COLORS_GRID", dflt)', 'kmx_env_int("KMX_COLORS_HASH_BITS")'):
+        assert read in src, read
     assert "__threadfence" not in src and "__atomic_load" not in src      # what is compared was written by the launch before
     assert "colors.hip" in open(os.path.join(csrc, "Makefile")).read()
     assert "kmx_colors.cpp" in open(os.path.join(ROOT, "kmtricks_amd", "host", "Makefile")).read()

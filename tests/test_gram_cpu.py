@@ -182,7 +182,7 @@ def test_gram_hip_has_knobs_of_its_own():
     src = open(os.path.join(csrc, "gram.hip")).read()
     for word in ("kmx_plan_cus", "kmx_grid_cap", "KMX_PLAN_CUS", "KMX_MAX_GRID", "KMX_PAN_"):
         assert word not in src, word
-    assert 'kmx_env_int("KMX_GRAM_CUS")' in src and 'kmx_env_int("KMX_GRAM_GRID")' in src
+    assert 'kmx_env_cus("KMX_GRAM_CUS", ctx)' in src and 'kmx_env_grid("KMX_GRAM_GRID", dflt)' in src
     assert "gram.hip" in open(os.path.join(csrc, "Makefile")).read()
     host = open(os.path.join(ROOT, "kmtricks_amd", "host", "Makefile")).read()
     assert "kmx_pca.cpp" in host and "kmx_pca_math.hpp" in host

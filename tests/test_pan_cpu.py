@@ -293,7 +293,7 @@ def test_pan_hip_has_knobs_of_its_own():
     src = open(os.path.join(csrc, "pan.hip")).read()
     for word in ("kmx_plan_cus", "kmx_grid_cap", "KMX_PLAN_CUS", "KMX_MAX_GRID"):
         assert word not in src, word
-    assert 'kmx_env_int("KMX_PAN_CUS")' in src and 'kmx_env_int("KMX_PAN_GRID")' in src
+    assert 'kmx_env_cus("KMX_PAN_CUS", ctx)' in src and 'kmx_env_grid("KMX_PAN_GRID", dflt)' in src
     assert "pan.hip" in open(os.path.join(csrc, "Makefile")).read()
     assert "kmx_pan.cpp" in open(os.path.join(ROOT, "kmtricks_amd", "host", "Makefile")).read()
     curves = open(os.path.join(ROOT, "kmtricks_amd", "host", "kmx_pan_curves.hpp")).read()
