@@ -44,7 +44,11 @@
  *                               table of shared rows, each row weighted by its recurrence class -- what the samples' PCs follow from
  *   kmx_assoc_dev / _host       no counterpart either (kmdiff's and EIGENSTRAT's corrected test, a k-mer GWAS): the rows whose presence
  *                               pattern is associated with a phenotype once covariates (the PCs) are projected out, kept in file order
- *   kmx_superk_partition        replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
+ *   kmx_unitigs_dev / _host     no counterpart either (ggcat behind MUSET's `kmat_tools filter`, kmdiff's merge of its significant k-mers):
+ *                               a set of distinct canonical k-mers compacted into the unitigs of its de Bruijn graph
+ *   kmx_groupsum_dev / _host    no counterpart either (MUSET's `kmat_tools unitig`): a matrix's rows summed by a label per row -- per
+ *                               group and sample the rows present and the counts' sum, the unitig x sample table among others
+ *   kmx_superk_partition       replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
  *
@@ -75,7 +79,7 @@ enum {
   KMX_E_NOMEM    = -3,   /* host or device allocation failed */
   KMX_E_HIP      = -4,   /* HIP runtime error during a call */
   KMX_E_UNSUPPORTED = -5,/* configuration outside what this build handles (message says which) */
-  KMX_E_INTERNAL = -6    /* a bound inside the library was reached on the device (kmx_colors_*: the table's probe bound); never expected */
+  KMX_E_INTERNAL = -6    /* a bound inside the library was reached on the device (kmx_colors_*, kmx_unitigs_*: the table's probe bound; kmx_unitigs_*: a cycle walk's); never expected */
 };
 
 /* matrix row encodings; names follow kmtricks' --mode <kmer|hash>:<count|pa|bf|bfc>:bin */
@@ -1214,6 +1218,156 @@ double    kmx_assoc_result_kernel_ms(kmx_assoc_result* r);           /* needs km
 /* algorithmic bytes: the body read once + the kept rows written + 32 bytes per kept row + the vectors (4 * N * V) */
 uint64_t  kmx_assoc_result_algo_bytes(kmx_assoc_result* r);
 void      kmx_assoc_result_free(kmx_assoc_result* r);
+
+/* ---------------------------------------------------------------- unitigs */
+
+/* The compacted de Bruijn graph of a set of k-mers (what MUSET asks of ggcat behind `kmat_tools filter`, what kmdiff does when it merges
+ * its significant k-mers into contigs; no counterpart in the kmtricks tree): every k-mer's unitig, its place and strand in it, and the
+ * unitigs' sequences.  This comment is the contract.
+ * INPUT: keys[n][key_words] u64, low word first, as the key part of a matrix row; dense (stride 8 * key_words bytes), 8-byte aligned.
+ * key_words = ceil(kmer_size / 32).  The keys are n DISTINCT CANONICAL k-mers in ANY order (the rows of several partitions one behind
+ * the other are not sorted).  The encoding is the matrices' own: digit i (bits 2i, 2i + 1) is base k - 1 - i, A0 C1 T2 G3, the
+ * complement is digit ^ 2.  Node v is keys[v]; x is its key read as a string.
+ * SIDES: side 1 is the right end of x, side 0 the left end.  The four EXTENSIONS of side 1 are x[1:] + c, those of side 0 c + x[:-1].
+ * An extension y is PRESENT when canonical(y) is a key, of node u say; y ENTERS u on side t: from side 1, t = 0 if y == key(u), else 1;
+ * from side 0, t = 1 if y == key(u), else 0.
+ * deg(v, s) = the number of present extensions, 0 ... 4: STRINGS are counted; self-loops and hairpins (u == v) count.  (Two extensions
+ * of one side cannot be each other's reverse complement -- x[1:] + c == revcomp(x[1:] + d) forces c == d --, so a side's present
+ * extensions are distinct nodes; both SIDES of a node may lead to one node.)
+ * A node is PALINDROMIC when key == revcomp(key) (even k only).
+ * cand(v, s) = (u, t) when deg(v, s) == 1, u != v and neither v nor u is palindromic; otherwise there is none.
+ * link(v, s) = (u, t) iff cand(v, s) = (u, t) and cand(u, t) = (v, s).  So each side has at most one link, links are symmetric, and a
+ * component of the link graph is a simple path or a simple cycle: one UNITIG.
+ * TRAVEL: leaving v through side s along link (u, t) means entering u at t and leaving it through 1 - t.  Node u is read forward
+ * (ori = 0) when it is left through side 1, and as its reverse complement (ori = 1) otherwise.
+ * A PATH has two traversals, one from each end: the one taken is the traversal whose FIRST oriented k-mer is the smaller key (most
+ * significant word first); the two are never equal unless the path is a single palindromic node.  A single node is read forward.
+ * A CYCLE starts at its node with the smallest key, read forward, leaving through side 1; it is flagged circular.
+ * SEQUENCE: a unitig of L nodes is L + k - 1 bases: the first oriented k-mer, then the last base of each following one; a cycle the
+ * same way, linearised at its start node.  Unitigs are numbered 0 ... U - 1 by ascending index of their start node (pos 0).
+ * OUTPUTS, device memory the result owns (the _copy_ accessors bring them to the host; all wait for the call themselves):
+ *   n_unitigs       U
+ *   unitig[n]       u32, the node's unitig          pos[n]  u32, its position in it          ori[n]  u8, 0 forward, 1 reverse complement
+ *   start[U]        u32, the node at pos 0, strictly ascending       len[U]  u32, k-mers       circ[U]  u8, 1 for a cycle
+ *   seq_off[U + 1]  u64, exclusive sums of len + k - 1
+ *   seqs            seq_off[U] = n + U (k - 1) bytes of ACGT, made by the first accessor that asks for them (sized from U on the host)
+ * EXAMPLE.  k = 5 (below the call's own limit: for the reader and the CPU restatement), keys (ATTGC, CAATG, CAGGA, CCTGC, CTGCA, TTGCA,
+ * TGCAC) = (173, 267, 316, 365, 436, 692, 721):
+ *   U = 3, seqs = CATTGCA, TCCTGCA, TGCAC; unitig = (0,0,1,1,1,0,2), pos = (1,0,0,1,2,2,0), ori = (0,1,1,0,0,0,0), start = (1,2,6),
+ *   len = (3,3,1), circ = (0,0,0)
+ *   keys (ACCTG, AGGTC, CCTGA, CTGAC, TGACC): U = 1, seq ACCTGACCT, pos = (0,4,1,2,3), ori = (0,1,0,0,0), circ = (1)
+ * IDENTITIES: len sums to n; unitig[start[u]] = u; pos is a permutation of 0 ... len - 1 within each unitig; the k-mers of a unitig's
+ * sequence are its nodes' oriented keys in pos order.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: kmer_size outside 8 ... 127; key_words != ceil(kmer_size / 32); null keys with
+ * n > 0; flag bits.  KMX_E_UNSUPPORTED: n > 2^31 - 2 (a state 2 v + s and the sentinel 0xFFFFFFFF must fit in u32).  n = 0 is a valid
+ * call with U = 0.
+ * DATA ERRORS, found on the device and returned as KMX_E_INVAL by _wait and every accessor, the message naming the cause: a key with bits
+ * set from 2 k upwards; a key greater than its reverse complement; a key that occurs twice.  KMX_E_INTERNAL: a probe sequence ran T
+ * slots or a cycle walk 2 n steps (never expected: the table is at most half full).
+ * SCRATCH from the context's pool, per call, given back when the call has run: PER NODE 16 bytes of candidates and links, 64 of the two
+ * state buffers of the ranking (2 states x 16 bytes x 2), 13 for the numbering, plus the table, 4 bytes a slot, T = the power of two
+ * >= 2 n slots: 8 to 16 bytes a node -- 109 bytes a node at the most; 8 bytes per 256 nodes.  The RESULT keeps 8 * key_words + 26 bytes
+ * per node until it is freed (its own copy of the keys, unitig, pos, ori, and start / len / circ / seq_off sized for U = n: U is known
+ * on the device only), and n + U (k - 1) bytes of sequence once they are asked for. */
+typedef struct {
+  const uint64_t* keys;          /* n * key_words words */
+  uint64_t        n;
+  uint32_t        kmer_size;     /* k: 8 ... 127 */
+  uint32_t        key_words;     /* ceil(k / 32) */
+  uint32_t        flags;         /* 0 */
+  uint32_t        reserved;      /* not read */
+} kmx_unitigs_task;              /* 32 bytes */
+
+typedef struct kmx_unitigs_result kmx_unitigs_result;
+
+/* _dev: keys a DEVICE pointer, copied by the call on the context's stream (free for reuse once _result_wait has returned), the kernels
+ * queued behind it and the call back without waiting.  _host: a HOST pointer, uploaded on a stream of its own. */
+int kmx_unitigs_dev(kmx_ctx* ctx, const kmx_unitigs_task* task, kmx_unitigs_result** out);
+int kmx_unitigs_host(kmx_ctx* ctx, const kmx_unitigs_task* task, kmx_unitigs_result** out);
+int       kmx_unitigs_result_wait(kmx_unitigs_result* r);
+/* (the accessors below wait for the call themselves; after a data error each returns that error, 0 or NULL) */
+uint64_t  kmx_unitigs_result_n_unitigs(kmx_unitigs_result* r);           /* U */
+const uint32_t* kmx_unitigs_result_unitig_dev(kmx_unitigs_result* r);    /* n u32 on the device: the `groups` of kmx_groupsum_dev */
+int       kmx_unitigs_result_copy_unitig(kmx_unitigs_result* r, uint32_t* host_dst, uint64_t dst_entries);      /* n */
+int       kmx_unitigs_result_copy_pos(kmx_unitigs_result* r, uint32_t* host_dst, uint64_t dst_entries);         /* n */
+int       kmx_unitigs_result_copy_ori(kmx_unitigs_result* r, uint8_t* host_dst, uint64_t dst_entries);          /* n */
+int       kmx_unitigs_result_copy_start(kmx_unitigs_result* r, uint32_t* host_dst, uint64_t dst_entries);       /* U */
+int       kmx_unitigs_result_copy_len(kmx_unitigs_result* r, uint32_t* host_dst, uint64_t dst_entries);         /* U */
+int       kmx_unitigs_result_copy_circ(kmx_unitigs_result* r, uint8_t* host_dst, uint64_t dst_entries);         /* U */
+int       kmx_unitigs_result_copy_seq_off(kmx_unitigs_result* r, uint64_t* host_dst, uint64_t dst_entries);     /* U + 1 */
+uint64_t  kmx_unitigs_result_seq_bytes(kmx_unitigs_result* r);           /* n + U (k - 1) */
+int       kmx_unitigs_result_copy_seqs(kmx_unitigs_result* r, uint8_t* host_dst, uint64_t dst_bytes);           /* seq_bytes */
+/* duration in ms of the call's kernels, the clearing of the table included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_unitigs_result_kernel_ms(kmx_unitigs_result* r);
+/* the same interval in its parts: clearing + k_ug_table; k_ug_cand + k_ug_link; the rounds of k_ug_jump; k_ug_paths, k_ug_cycles and the
+ * numbering; any pointer may be NULL */
+int       kmx_unitigs_result_kernel_parts_ms(kmx_unitigs_result* r, double* table_ms, double* links_ms, double* rank_ms, double* finish_ms);
+/* algorithmic bytes: the keys read and the table cleared and filled; 8 look-ups a node, each a slot and a key; candidates and links
+ * written and read; per round of the ranking a state's tuple read twice and written once (48 bytes a state); the ends' keys and the
+ * outputs */
+uint64_t  kmx_unitigs_result_algo_bytes(kmx_unitigs_result* r);
+void      kmx_unitigs_result_free(kmx_unitigs_result* r);
+
+/* --------------------------------------------------------------- groupsum */
+
+/* A group-by over one partition's matrix body (MUSET's `kmat_tools unitig` with the unitig ids of kmx_unitigs_* as labels; the class ids
+ * of kmx_colors_* are labels as well; no counterpart in the kmtricks tree): per group and listed sample how many of the group's rows
+ * hold the sample and the sum of their counts.
+ * INPUT, as for kmx_pan_*: n_rows rows of ONE partition's body, n_cols = N samples, KMX_MODE_COUNT or KMX_MODE_PA, `rows` at any
+ * address; cols / n_use = M and min_abund = a are pan's.  groups[n_rows] u32, a label per row, lives where `rows` lives (device memory
+ * for _dev, host memory for _host).  A window of labels: g0 and n_groups = G.
+ * TABLES the call ADDS to, DEVICE pointers in both calls; NULL: the result owns a zeroed one -- exactly as the hits / sums of
+ * kmx_kquery_*, so that the partitions of a run accumulate:
+ *   size[G]         u32
+ *   present[G][M]   u32
+ *   sums[G][M]      u64   KMX_MODE_COUNT with KMX_GROUPSUM_SUMS only
+ * PER ROW with g = groups[row] in [g0, g0 + G): size[g - g0] += 1; for each ordinal j that is present (count[cols[j]] >= a, or the PA
+ * bit of cols[j]): present[g - g0][j] += 1 and, with sums, sums[g - g0][j] += count[cols[j]].  Rows outside the window -- 0xFFFFFFFF
+ * among them -- add nothing.  The padding bits of a PA row never reach a result.
+ * EXAMPLE.  N = 3, COUNT, a = 1, rows (1,0,2) (0,0,5) (3,0,1) (4,4,4), groups (7, 8, 7, 0xFFFFFFFF), g0 = 7, G = 2:
+ *   size = (2, 1), present = ((2,0,2), (0,0,1)), sums = ((4,0,3), (0,0,5))
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: pan's (n_cols or n_use = 0, n_use > n_cols, a column index >= N or listed
+ * twice, cols = NULL with M != N, key_words 0 or > 4, a mode other than COUNT / PA, min_abund 0 or > 1 with PA, unknown flag bits);
+ * n_groups = 0; KMX_GROUPSUM_SUMS or a sums table with KMX_MODE_PA; a sums table without KMX_GROUPSUM_SUMS; null groups with n_rows > 0;
+ * g0 + n_groups > 2^32.  KMX_E_UNSUPPORTED: Bloom modes; n_rows > 2^32 - 256; a row of 4 GiB or more; G * M > 2^32 table entries.
+ * n_rows = 0 is a valid call.  The tables the result owns take 4 G + 4 G M (+ 8 G M) bytes; scratch: 4 bytes a listed column, for _host
+ * the uploaded rows and labels. */
+#define KMX_GROUPSUM_SUMS 1u
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N */
+  uint32_t        n_use;         /* M */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices (copied by the call), or NULL: the identity */
+  const uint32_t* groups;        /* n_rows labels, where rows lives */
+  uint32_t        min_abund;     /* a */
+  uint32_t        flags;         /* KMX_GROUPSUM_SUMS or 0 */
+  uint32_t        g0;            /* the window's first label */
+  uint32_t        n_groups;      /* G */
+  uint32_t*       present;       /* DEVICE [G][M], added to, or NULL */
+  uint64_t*       sums;          /* DEVICE [G][M], added to, or NULL */
+  uint32_t*       size;          /* DEVICE [G], added to, or NULL */
+} kmx_groupsum_task;             /* 88 bytes */
+
+typedef struct kmx_groupsum_result kmx_groupsum_result;
+
+int kmx_groupsum_dev(kmx_ctx* ctx, const kmx_groupsum_task* task, kmx_groupsum_result** out);
+int kmx_groupsum_host(kmx_ctx* ctx, const kmx_groupsum_task* task, kmx_groupsum_result** out);
+int       kmx_groupsum_result_wait(kmx_groupsum_result* r);
+/* (the accessors below wait for the call themselves; the tables are the ones the call added to, its own or the caller's) */
+uint32_t* kmx_groupsum_result_present_dev(kmx_groupsum_result* r);
+uint64_t* kmx_groupsum_result_sums_dev(kmx_groupsum_result* r);          /* NULL without KMX_GROUPSUM_SUMS */
+uint32_t* kmx_groupsum_result_size_dev(kmx_groupsum_result* r);
+int       kmx_groupsum_result_copy_present(kmx_groupsum_result* r, uint32_t* host_dst, uint64_t dst_entries);   /* G * M */
+int       kmx_groupsum_result_copy_sums(kmx_groupsum_result* r, uint64_t* host_dst, uint64_t dst_entries);      /* G * M */
+int       kmx_groupsum_result_copy_size(kmx_groupsum_result* r, uint32_t* host_dst, uint64_t dst_entries);      /* G */
+double    kmx_groupsum_result_kernel_ms(kmx_groupsum_result* r);         /* needs kmx_set_profiling(ctx, 1); < 0 if unavailable */
+/* algorithmic bytes: the body and the labels read once (n_rows * (row bytes + 4)) + the tables (G * (4 + 4 M), + 8 G M with sums)
+ *  */
+uint64_t  kmx_groupsum_result_algo_bytes(kmx_groupsum_result* r);
+void      kmx_groupsum_result_free(kmx_groupsum_result* r);
 
 /* ------------------------------------------------------------------ count */
 

@@ -140,6 +140,24 @@ class KmxColorsTask(C.Structure):
 assert C.sizeof(KmxColorsTask) == 48
 
 
+class KmxUnitigsTask(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("n", C.c_uint64), ("kmer_size", C.c_uint32), ("key_words", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(KmxUnitigsTask) == 32
+
+
+class KmxGroupsumTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32), ("rows", C.c_void_p),
+                ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("groups", C.c_void_p), ("min_abund", C.c_uint32), ("flags", C.c_uint32),
+                ("g0", C.c_uint32), ("n_groups", C.c_uint32), ("present", C.c_void_p), ("sums", C.c_void_p), ("size", C.c_void_p)]
+
+
+assert C.sizeof(KmxGroupsumTask) == 88
+GROUPSUM_SUMS = 1
+
+
 class KmxGramTask(C.Structure):
     _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("weights", C.c_void_p),
@@ -470,6 +488,39 @@ _lib.kmx_colors_result_free.argtypes = [_vp]
 COLORS_EXPORTS = ["kmx_colors_dev", "kmx_colors_host", "kmx_colors_result_wait", "kmx_colors_result_n_classes", "kmx_colors_result_ids_dev",
                   "kmx_colors_result_copy_ids", "kmx_colors_result_copy_first", "kmx_colors_result_copy_sizes", "kmx_colors_result_copy_patterns",
                   "kmx_colors_result_kernel_ms", "kmx_colors_result_kernel_parts_ms", "kmx_colors_result_algo_bytes", "kmx_colors_result_free"]
+_lib.kmx_unitigs_dev.argtypes = [_vp, C.POINTER(KmxUnitigsTask), C.POINTER(_vp)]
+_lib.kmx_unitigs_host.argtypes = [_vp, C.POINTER(KmxUnitigsTask), C.POINTER(_vp)]
+_lib.kmx_unitigs_result_wait.argtypes = [_vp]
+for _f in ("kmx_unitigs_result_n_unitigs", "kmx_unitigs_result_seq_bytes", "kmx_unitigs_result_algo_bytes"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_unitigs_result_unitig_dev.restype = _vp
+_lib.kmx_unitigs_result_unitig_dev.argtypes = [_vp]
+UNITIGS_COPIES = ["unitig", "pos", "ori", "start", "len", "circ", "seq_off", "seqs"]
+for _f in UNITIGS_COPIES:
+    getattr(_lib, "kmx_unitigs_result_copy_" + _f).argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_unitigs_result_kernel_ms.restype = C.c_double
+_lib.kmx_unitigs_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_unitigs_result_kernel_parts_ms.argtypes = [_vp] + [C.POINTER(C.c_double)] * 4
+_lib.kmx_unitigs_result_free.argtypes = [_vp]
+UNITIGS_EXPORTS = (["kmx_unitigs_dev", "kmx_unitigs_host", "kmx_unitigs_result_wait", "kmx_unitigs_result_n_unitigs", "kmx_unitigs_result_unitig_dev",
+                    "kmx_unitigs_result_seq_bytes", "kmx_unitigs_result_kernel_ms", "kmx_unitigs_result_kernel_parts_ms", "kmx_unitigs_result_algo_bytes",
+                    "kmx_unitigs_result_free"] + ["kmx_unitigs_result_copy_" + _f for _f in UNITIGS_COPIES])
+_lib.kmx_groupsum_dev.argtypes = [_vp, C.POINTER(KmxGroupsumTask), C.POINTER(_vp)]
+_lib.kmx_groupsum_host.argtypes = [_vp, C.POINTER(KmxGroupsumTask), C.POINTER(_vp)]
+_lib.kmx_groupsum_result_wait.argtypes = [_vp]
+_lib.kmx_groupsum_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_groupsum_result_algo_bytes.argtypes = [_vp]
+for _f in ("present", "sums", "size"):
+    getattr(_lib, f"kmx_groupsum_result_{_f}_dev").restype = _vp
+    getattr(_lib, f"kmx_groupsum_result_{_f}_dev").argtypes = [_vp]
+    getattr(_lib, f"kmx_groupsum_result_copy_{_f}").argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_groupsum_result_kernel_ms.restype = C.c_double
+_lib.kmx_groupsum_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_groupsum_result_free.argtypes = [_vp]
+GROUPSUM_EXPORTS = ["kmx_groupsum_dev", "kmx_groupsum_host", "kmx_groupsum_result_wait", "kmx_groupsum_result_present_dev", "kmx_groupsum_result_sums_dev",
+                    "kmx_groupsum_result_size_dev", "kmx_groupsum_result_copy_present", "kmx_groupsum_result_copy_sums", "kmx_groupsum_result_copy_size",
+                    "kmx_groupsum_result_kernel_ms", "kmx_groupsum_result_algo_bytes", "kmx_groupsum_result_free"]
 _lib.kmx_gram_dev.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
 _lib.kmx_gram_host.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
 _lib.kmx_gram_result_wait.argtypes = [_vp]
@@ -1290,6 +1341,65 @@ class Context:
         self._check(_lib.kmx_colors_dev(self._h, C.byref(t), C.byref(res)), "kmx_colors_dev")
         return self._finish(ColorsResult(self, res, n_rows, n_use), keep)
 
+    def unitigs(self, keys, kmer_size, keep=False):
+        """kmx_unitigs_host: keys uint64[n, ceil(kmer_size / 32)] (low word first), n distinct canonical k-mers in any order.
+        -> UnitigsOutput (numpy copies), or with keep the UnitigsResult itself (the arrays left in HBM; .free() it)"""
+        kw = key_words_of(kmer_size)
+        a = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, kw)
+        t = KmxUnitigsTask(a.ctypes.data if len(a) else None, len(a), kmer_size, kw, 0, 0)
+        res = _vp()
+        self._check(_lib.kmx_unitigs_host(self._h, C.byref(t), C.byref(res)), "kmx_unitigs_host")
+        r = UnitigsResult(self, res, len(a), kmer_size)
+        try:
+            r.wait()      # (the host buffer above may go once the call has run)
+        except KmxError:      # a data error found on the device: nothing of the result is of use
+            r.free()
+            raise
+        return self._finish(r, keep)
+
+    def unitigs_dev(self, keys_dev, n, kmer_size, keep=False):
+        """kmx_unitigs_dev: keys_dev a device pointer to n keys.  -> as unitigs"""
+        t = KmxUnitigsTask(keys_dev, n, kmer_size, key_words_of(kmer_size), 0, 0)
+        res = _vp()
+        self._check(_lib.kmx_unitigs_dev(self._h, C.byref(t), C.byref(res)), "kmx_unitigs_dev")
+        return self._finish(UnitigsResult(self, res, n, kmer_size), keep)
+
+    @staticmethod
+    def _groupsum_task(rows, n_rows, n_cols, key_words, mode, groups, g0, n_groups, cols, min_abund, sums, present_dev, sums_dev, size_dev):
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = n_cols if c is None else len(c)
+        want = bool(sums) or sums_dev is not None
+        t = KmxGroupsumTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None, groups, min_abund,
+                            GROUPSUM_SUMS if want else 0, g0, n_groups, present_dev, sums_dev, size_dev)
+        return t, c, n_use, want      # (c is kept alive by the caller until the call has copied it)
+
+    def groupsum(self, body, n_rows, n_cols, key_words, mode, groups, g0, n_groups, cols=None, min_abund=1, sums=False, present_dev=None,
+                 sums_dev=None, size_dev=None, keep=False):
+        """kmx_groupsum_host: body as for pan; groups uint32[n_rows]: a label per row; the window [g0, g0 + n_groups); sums: the counts'
+        sums are wanted too (COUNT); present_dev / sums_dev / size_dev: None (the result owns a zeroed table) or a device pointer to a
+        uint32 [G, M] / uint64 [G, M] / uint32 [G] table the call adds to.
+        -> GroupsumOutput (numpy copies), or with keep the GroupsumResult itself (.free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if len(g) != n_rows:
+            raise ValueError(f"{len(g)} labels for {n_rows} rows")
+        t, c, n_use, want = self._groupsum_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, g.ctypes.data if len(g) else None,
+                                                g0, n_groups, cols, min_abund, sums, present_dev, sums_dev, size_dev)
+        res = _vp()
+        self._check(_lib.kmx_groupsum_host(self._h, C.byref(t), C.byref(res)), "kmx_groupsum_host")
+        r = GroupsumResult(self, res, n_groups, n_use, want)
+        r.wait()      # (the host buffers above may go once the call has run)
+        return self._finish(r, keep)
+
+    def groupsum_dev(self, rows_dev, n_rows, n_cols, key_words, mode, groups_dev, g0, n_groups, cols=None, min_abund=1, sums=False,
+                     present_dev=None, sums_dev=None, size_dev=None, keep=False):
+        """kmx_groupsum_dev: rows_dev and groups_dev device pointers (cols stays a host array).  -> as groupsum"""
+        t, c, n_use, want = self._groupsum_task(rows_dev, n_rows, n_cols, key_words, mode, groups_dev, g0, n_groups, cols, min_abund, sums,
+                                                present_dev, sums_dev, size_dev)
+        res = _vp()
+        self._check(_lib.kmx_groupsum_dev(self._h, C.byref(t), C.byref(res)), "kmx_groupsum_dev")
+        return self._finish(GroupsumResult(self, res, n_groups, n_use, want), keep)
+
     @staticmethod
     def _gram_task(rows, n_rows, n_cols, key_words, mode, weights, cols, min_abund, table_dev):
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
@@ -1654,6 +1764,76 @@ class ColorsResult(_Result):
         first, sizes = self._copy("first", np.zeros(n, np.uint32)), self._copy("sizes", np.zeros(n, np.uint32))
         patterns = self._copy("patterns", np.zeros((n, self._w), np.uint64))
         return ColorsOutput(n, ids, first, sizes, patterns, self.kernel_ms(), self.algo_bytes())
+
+
+class UnitigsOutput:
+    """n_unitigs U; unitig / pos uint32[n], ori uint8[n]: every k-mer's unitig, position and strand; start / len uint32[U], circ uint8[U];
+    seq_off uint64[U + 1]; seqs: the U sequences (bytes each); kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, n_unitigs, unitig, pos, ori, start, length, circ, seq_off, seqs, kernel_ms, algo_bytes):
+        self.n_unitigs, self.unitig, self.pos, self.ori, self.start, self.len, self.circ = n_unitigs, unitig, pos, ori, start, length, circ
+        self.seq_off, self.seqs, self.kernel_ms, self.algo_bytes = seq_off, seqs, kernel_ms, algo_bytes
+
+class UnitigsResult(_Result):
+    _prefix = "unitigs"
+
+    def __init__(self, ctx, h, n, kmer_size):
+        super().__init__(ctx, h)
+        self._n, self._k = n, kmer_size
+
+    def n_unitigs(self):
+        return self._call("n_unitigs")
+
+    def unitig_dev(self):
+        return self._call("unitig_dev")
+
+    def seq_bytes(self):
+        return self._call("seq_bytes")
+
+    def kernel_parts_ms(self):
+        """(clearing + k_ug_table, k_ug_cand + k_ug_link, the rounds of k_ug_jump, the finish) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(4)
+
+    def output(self):
+        self.wait()
+        n, U = self._n, self.n_unitigs()
+        unitig, pos, ori = self._copy("unitig", np.zeros(n, np.uint32)), self._copy("pos", np.zeros(n, np.uint32)), self._copy("ori", np.zeros(n, np.uint8))
+        start, length, circ = self._copy("start", np.zeros(U, np.uint32)), self._copy("len", np.zeros(U, np.uint32)), self._copy("circ", np.zeros(U, np.uint8))
+        seq_off = self._copy("seq_off", np.zeros(U + 1, np.uint64))
+        flat = self._copy("seqs", np.zeros(self.seq_bytes(), np.uint8)).tobytes()
+        seqs = [flat[int(seq_off[u]):int(seq_off[u + 1])] for u in range(U)]
+        return UnitigsOutput(U, unitig, pos, ori, start, length, circ, seq_off, seqs, self.kernel_ms(), self.algo_bytes())
+
+
+class GroupsumOutput:
+    """size uint32[G]: the rows of every group of the window; present uint32[G, M]: those that hold the listed sample; sums uint64[G, M]
+    (None unless asked for): the sums of their counts -- the tables the call added to, when they were given; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, size, present, sums, kernel_ms, algo_bytes):
+        self.size, self.present, self.sums, self.kernel_ms, self.algo_bytes = size, present, sums, kernel_ms, algo_bytes
+
+class GroupsumResult(_Result):
+    _prefix = "groupsum"
+
+    def __init__(self, ctx, h, n_groups, n_use, has_sums):
+        super().__init__(ctx, h)
+        self._g, self._m, self._sums = n_groups, n_use, has_sums
+
+    def present_dev(self):
+        return self._call("present_dev")
+
+    def sums_dev(self):
+        return self._call("sums_dev")
+
+    def size_dev(self):
+        return self._call("size_dev")
+
+    def output(self):
+        self.wait()
+        size = self._copy("size", np.zeros(self._g, np.uint32))
+        present = self._copy("present", np.zeros((self._g, self._m), np.uint32))
+        sums = self._copy("sums", np.zeros((self._g, self._m), np.uint64)) if self._sums else None
+        return GroupsumOutput(size, present, sums, self.kernel_ms(), self.algo_bytes())
 
 
 class SelectOutput:
