@@ -6,16 +6,9 @@
 // `--z Z` asks the Bloom index for (k + Z)-mers (the findere trick: kmx_zquery_host, one bits table a batch across its partition groups).
 // `--index` of a `--mode hash:bfc:bin` run (a counting Bloom index: fields of --bitw bits a sample) goes through kmx_cquery_host: hits are
 // the k-mers whose abundance class is at least --min-class, `--format sums` prints the sums of the classes' least counts.
-#include <kmx.h>
-#include <algorithm>
-#include <cstring>
-#include <mutex>
-#include <thread>
-#include "kmx_io.hpp"
-#include "kmx_run.hpp"
+#include "kmx_driver.hpp"
 
-namespace fs = std::filesystem;
-using namespace kmxio;
+using namespace kmxdrv;
 
 namespace {
 
@@ -37,23 +30,24 @@ const char* USAGE = "usage: kmx query (--index <run dir made with --mode hash:bf
 QOpt parse(int argc, char** argv)
 {
   QOpt o;
-  auto need = [&](int& i) -> std::string { if (i + 1 >= argc) die(std::string("missing value for ") + argv[i] + "\n" + USAGE); return argv[++i]; };
-  auto num = [&](int& i) -> unsigned long { const std::string v = need(i); try { size_t n = 0; const unsigned long x = std::stoul(v, &n); if (n != v.size()) throw 1; return x; } catch (...) { die(std::string("bad number for ") + argv[i - 1] + ": " + v); } };
+  const Args in{argc, argv, USAGE};
+  // (a number may carry a sign here: `--z -1` wraps and is told its range, not that it is no number)
+  auto num = [&](int& i) -> unsigned long { const std::string v = in.need(i); try { size_t n = 0; const unsigned long x = std::stoul(v, &n); if (n != v.size()) throw 1; return x; } catch (...) { die(std::string("bad number for ") + argv[i - 1] + ": " + v); } };
   for (int i = 2; i < argc; i++) {
     const std::string a = argv[i];
-    if (a == "--index") o.index = need(i);
-    else if (a == "--kmer-index") o.kmer_index = need(i);
-    else if (a == "--query") o.query = need(i);
-    else if (a == "--output") o.out = need(i);
-    else if (a == "--threshold") { const std::string v = need(i); try { size_t n = 0; o.threshold = std::stod(v, &n); if (n != v.size()) throw 1; } catch (...) { die("bad number for --threshold: " + v); } }
-    else if (a == "--format") { o.format = need(i); if (o.format != "matrix" && o.format != "list" && o.format != "sums") die("--format must be matrix, list or sums"); }
+    if (a == "--index") o.index = in.need(i);
+    else if (a == "--kmer-index") o.kmer_index = in.need(i);
+    else if (a == "--query") o.query = in.need(i);
+    else if (a == "--output") o.out = in.need(i);
+    else if (a == "--threshold") o.threshold = in.real(i);
+    else if (a == "--format") { o.format = in.need(i); if (o.format != "matrix" && o.format != "list" && o.format != "sums") die("--format must be matrix, list or sums"); }
     else if (a == "--gpus") o.gpus = num(i);
     else if (a == "--z") { const unsigned long v = num(i); if (v > 8) die("--z must be in [0, 8]"); o.z = (int64_t)v; }
     else if (a == "--min-class") o.min_class = (int64_t)std::min<unsigned long>(num(i), 0xFFFFFFFFul);
     else if (a == "--query-batch-mb") o.batch_mb = num(i);
     else if (a == "-t" || a == "--threads") o.threads = num(i);
-    else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
-    else die("unknown option " + a + "\n" + USAGE);
+    else if (in.verbose(a, i)) o.verbose = true;
+    else in.unknown(a);
   }
   if (o.index.empty() == o.kmer_index.empty()) die(std::string("exactly one of --index and --kmer-index is required\n") + USAGE);
   if (o.query.empty()) die(std::string("--query is required\n") + USAGE);
@@ -63,18 +57,6 @@ QOpt parse(int argc, char** argv)
   if (o.min_class >= 0 && !o.kmer_index.empty()) die("--min-class is for a counting Bloom index (--index of a run made with --mode hash:bfc:bin): an exact index has counts, not classes");
   if (o.z >= 0 && o.gpus > 1) die("--z with --gpus above 1 is not supported: shards own partitions, a window's k-mers lie in several shards, and the shards' tables are not joined across devices");
   return o;
-}
-
-void chk(kmx_ctx* c, int rc, const char* what) { if (rc != KMX_OK) die(std::string(what) + ": " + kmx_last_error(c)); }
-
-// `key=value` of the run's options.txt (cmd/all.hpp:85-125: one line of them)
-std::string option_of(const std::string& line, const std::string& key)
-{
-  const size_t at = line.find(" " + key + "="); if (at == std::string::npos) return "";
-  const size_t b = at + key.size() + 2, e = line.find(',', b);
-  std::string v = line.substr(b, e == std::string::npos ? std::string::npos : e - b);
-  while (!v.empty() && (v.back() == '\n' || v.back() == '\r' || v.back() == ' ')) v.pop_back();
-  return v;
 }
 
 constexpr size_t CMBF_HEADER = 49, KMATRIX_HEADER = 45;
@@ -142,16 +124,9 @@ int kquery_main(const QOpt& o)
   if (!out) die("Unable to write at " + o.out);
 
   // ---- devices; how many bases a batch of queries holds and which partitions a group ----
-  if (kmx_version() != KMX_VERSION) die("libkmx.so is not the version this driver was built for");
-  const uint32_t G = o.gpus, ndev = (uint32_t)std::max(1, kmx_device_count());
-  std::vector<kmx_ctx*> ctxs(G, nullptr);
-  for (uint32_t g = 0; g < G; g++) if (kmx_create((int)(g % ndev), &ctxs[g]) != KMX_OK) die(std::string("kmx_create: ") + kmx_last_error(nullptr));
-  uint64_t budget = o.batch_mb << 20;
-  if (!budget) {
-    uint64_t fr = 0, tot = 0;
-    for (uint32_t g = 0; g < std::min(G, ndev); g++) { uint64_t f = 0; if (kmx_device_memory((int)g, &f, &tot) == KMX_OK && (g == 0 || f < fr)) fr = f; }
-    budget = std::max<uint64_t>(fr / 10 * 6 / std::max<uint32_t>(1, (G + ndev - 1) / ndev), 64ull << 20);
-  }
+  Devices dev = open_devices(o.gpus, o.batch_mb, 6);
+  const uint32_t G = dev.G();
+  const uint64_t budget = dev.budget;
   const bool want_sums = o.format == "sums";
   // half for a group's matrices, half for a batch: 11 + 8 * key words bytes a base (the bases and the call's scratch) and a row of the
   // tables a query
@@ -191,57 +166,52 @@ int kquery_main(const QOpt& o)
     std::mutex mu;
     // every shard sees all queries of the batch; its groups add up on its device, the shards' tables on the host
     auto shard = [&](uint32_t g) {
-      try {
-        kmx_ctx* ctx = ctxs[g];
-        kmx_kquery_result* first = nullptr;
-        std::vector<std::vector<uint8_t>> own;
-        const bool keep = groups[g].size() == 1;
-        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
-        std::vector<const uint8_t*> rows(P);
-        std::vector<uint32_t> sk(nq);
-        static const uint8_t no_rows[8] = {0};      // a partition without a row is still part of the call
-        for (size_t gi = 0; gi < groups[g].size(); gi++) {
-          std::fill(rows.begin(), rows.end(), nullptr);
-          const bool loaded = keep && bodies.size() == groups[g][gi].size();
-          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
-          for (size_t i = 0; i < groups[g][gi].size(); i++) {
-            const uint32_t p = groups[g][gi][i];
-            if (!loaded) {
-              uint32_t fk = 0, fn = 0;
-              bodies[i] = read_matrix(files[p], pa, 4, &fk, &fn);
-              if (fk != k || fn != N || bodies[i].size() != n_rows[p] * stride) die("changed while it was read: " + files[p]);
-            }
-            rows[p] = bodies[i].empty() ? no_rows : bodies[i].data();
+      kmx_ctx* ctx = dev.ctxs[g];
+      kmx_kquery_result* first = nullptr;
+      std::vector<std::vector<uint8_t>> own;
+      const bool keep = groups[g].size() == 1;
+      std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+      std::vector<const uint8_t*> rows(P);
+      std::vector<uint32_t> sk(nq);
+      static const uint8_t no_rows[8] = {0};      // a partition without a row is still part of the call
+      for (size_t gi = 0; gi < groups[g].size(); gi++) {
+        std::fill(rows.begin(), rows.end(), nullptr);
+        const bool loaded = keep && bodies.size() == groups[g][gi].size();
+        if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+        for (size_t i = 0; i < groups[g][gi].size(); i++) {
+          const uint32_t p = groups[g][gi][i];
+          if (!loaded) {
+            uint32_t fk = 0, fn = 0;
+            bodies[i] = read_matrix(files[p], pa, 4, &fk, &fn);
+            if (fk != k || fn != N || bodies[i].size() != n_rows[p] * stride) die("changed while it was read: " + files[p]);
           }
-          kmx_kquery_task t; memset(&t, 0, sizeof t);
-          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
-          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N;
-          t.key_words = kw; t.mode = pa ? KMX_MODE_PA : KMX_MODE_COUNT; t.n_rows = n_rows.data(); t.rows = rows.data();
-          t.want_sums = want_sums ? 1 : 0;
-          t.hits = first ? kmx_kquery_result_hits_dev(first) : nullptr;
-          t.sums = first && want_sums ? kmx_kquery_result_sums_dev(first) : nullptr;
-          kmx_kquery_result* r = nullptr;
-          chk(ctx, kmx_kquery_host(ctx, &t, &r), "kmx_kquery_host");
-          chk(ctx, kmx_kquery_result_wait(r), "kmx_kquery");      // (the bodies are reused by the next group)
-          if (!first) first = r; else kmx_kquery_result_free(r);
+          rows[p] = bodies[i].empty() ? no_rows : bodies[i].data();
         }
-        if (!first) return;      // (more shards than partitions)
-        std::vector<uint32_t> sh(nq * N);
-        std::vector<uint64_t> ss(want_sums ? nq * N : 0);
-        chk(ctx, kmx_kquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_kquery_result_copy_hits");
-        if (want_sums) chk(ctx, kmx_kquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_kquery_result_copy_sums");
-        chk(ctx, kmx_kquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_kquery_result_copy_kmers");
-        kmx_kquery_result_free(first);
-        std::lock_guard<std::mutex> lk(mu);
-        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
-        for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
-        kmers = sk;      // (every shard walks every query: the same numbers)
-      } catch (const std::exception& e) { die(e.what()); }
+        kmx_kquery_task t; memset(&t, 0, sizeof t);
+        t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+        t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N;
+        t.key_words = kw; t.mode = pa ? KMX_MODE_PA : KMX_MODE_COUNT; t.n_rows = n_rows.data(); t.rows = rows.data();
+        t.want_sums = want_sums ? 1 : 0;
+        t.hits = first ? kmx_kquery_result_hits_dev(first) : nullptr;
+        t.sums = first && want_sums ? kmx_kquery_result_sums_dev(first) : nullptr;
+        kmx_kquery_result* r = nullptr;
+        chk(ctx, kmx_kquery_host(ctx, &t, &r), "kmx_kquery_host");
+        chk(ctx, kmx_kquery_result_wait(r), "kmx_kquery");      // (the bodies are reused by the next group)
+        if (!first) first = r; else kmx_kquery_result_free(r);
+      }
+      if (!first) return;      // (more shards than partitions)
+      std::vector<uint32_t> sh(nq * N);
+      std::vector<uint64_t> ss(want_sums ? nq * N : 0);
+      chk(ctx, kmx_kquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_kquery_result_copy_hits");
+      if (want_sums) chk(ctx, kmx_kquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_kquery_result_copy_sums");
+      chk(ctx, kmx_kquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_kquery_result_copy_kmers");
+      kmx_kquery_result_free(first);
+      std::lock_guard<std::mutex> lk(mu);
+      for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+      for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
+      kmers = sk;      // (every shard walks every query: the same numbers)
     };
-    std::vector<std::thread> workers;
-    for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
-    shard(0);
-    for (std::thread& w : workers) w.join();
+    in_shards(G, shard);
     std::string txt;
     for (uint64_t i = 0; i < nq; i++) {
       const std::string& name = names[q0 + i];
@@ -258,7 +228,7 @@ int kquery_main(const QOpt& o)
     if (fwrite(txt.data(), 1, txt.size(), out) != txt.size()) die("write failed: " + (o.out.empty() ? std::string("stdout") : o.out));
   }
   if (out != stdout) { if (fclose(out) != 0) die("write failed: " + o.out); } else fflush(stdout);
-  for (uint32_t g = 0; g < G; g++) kmx_destroy(ctxs[g]);
+  dev.close();
   return 0;
 }
 
@@ -323,16 +293,9 @@ int kmx_query_main(int argc, char** argv)
   if (!out) die("Unable to write at " + o.out);
 
   // ---- devices; how many bases a batch of queries holds and how many partitions a group (kmx_device_memory, or --query-batch-mb) ----
-  if (kmx_version() != KMX_VERSION) die("libkmx.so is not the version this driver was built for");
-  const uint32_t G = o.gpus, ndev = (uint32_t)std::max(1, kmx_device_count());
-  std::vector<kmx_ctx*> ctxs(G, nullptr);
-  for (uint32_t g = 0; g < G; g++) if (kmx_create((int)(g % ndev), &ctxs[g]) != KMX_OK) die(std::string("kmx_create: ") + kmx_last_error(nullptr));
-  uint64_t budget = o.batch_mb << 20;
-  if (!budget) {
-    uint64_t fr = 0, tot = 0;
-    for (uint32_t g = 0; g < std::min(G, ndev); g++) { uint64_t f = 0; if (kmx_device_memory((int)g, &f, &tot) == KMX_OK && (g == 0 || f < fr)) fr = f; }
-    budget = std::max<uint64_t>(fr / 10 * 6 / std::max<uint32_t>(1, (G + ndev - 1) / ndev), 64ull << 20);
-  }
+  Devices dev = open_devices(o.gpus, o.batch_mb, 6);
+  const uint32_t G = dev.G();
+  const uint64_t budget = dev.budget;
   // half for a group's matrices, half for a batch: 17 bytes a base (the bases, 16 of scratch) and a row of the table a query.  A
   // call's scratch and uploads go back to the context's pool when it has been waited for, so the accumulating first result of a
   // batch holds its table and n_kmers only while the later groups run
@@ -371,97 +334,93 @@ int kmx_query_main(int argc, char** argv)
     std::mutex mu;
     // a counting index: the same walk through kmx_cquery_host, the groups adding into the first result's two tables
     auto cshard = [&](uint32_t g) {
-      try {
-        kmx_ctx* ctx = ctxs[g];
-        kmx_cquery_result* first = nullptr;
-        std::vector<std::vector<uint8_t>> own;
-        const bool keep = groups[g].size() == 1;
-        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
-        std::vector<const uint8_t*> rows(P);
-        std::vector<uint32_t> sk(nq);
-        for (size_t gi = 0; gi < groups[g].size(); gi++) {
-          std::fill(rows.begin(), rows.end(), nullptr);
-          const bool loaded = keep && bodies.size() == groups[g][gi].size();
-          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
-          for (size_t i = 0; i < groups[g][gi].size(); i++) {
-            const uint32_t p = groups[g][gi][i];
-            if (!loaded) {
-              std::ifstream f(files[p], std::ios::binary);
-              bodies[i].resize(body);
-              if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
-            }
-            rows[p] = bodies[i].data();
+      kmx_ctx* ctx = dev.ctxs[g];
+      kmx_cquery_result* first = nullptr;
+      std::vector<std::vector<uint8_t>> own;
+      const bool keep = groups[g].size() == 1;
+      std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+      std::vector<const uint8_t*> rows(P);
+      std::vector<uint32_t> sk(nq);
+      for (size_t gi = 0; gi < groups[g].size(); gi++) {
+        std::fill(rows.begin(), rows.end(), nullptr);
+        const bool loaded = keep && bodies.size() == groups[g][gi].size();
+        if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+        for (size_t i = 0; i < groups[g][gi].size(); i++) {
+          const uint32_t p = groups[g][gi][i];
+          if (!loaded) {
+            std::ifstream f(files[p], std::ios::binary);
+            bodies[i].resize(body);
+            if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
           }
-          kmx_cquery_task t; memset(&t, 0, sizeof t);
-          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
-          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
-          t.rows = rows.data(); t.bitw = w; t.min_class = min_class;
-          t.hits = first ? kmx_cquery_result_hits_dev(first) : nullptr;
-          t.sums = first ? kmx_cquery_result_sums_dev(first) : nullptr;
-          kmx_cquery_result* r = nullptr;
-          chk(ctx, kmx_cquery_host(ctx, &t, &r), "kmx_cquery_host");
-          chk(ctx, kmx_cquery_result_wait(r), "kmx_cquery");      // (the bodies are reused by the next group)
-          if (!first) first = r; else kmx_cquery_result_free(r);
+          rows[p] = bodies[i].data();
         }
-        if (!first) return;      // (more shards than partitions)
-        std::vector<uint32_t> sh(nq * N);
-        std::vector<uint64_t> ss(nq * N);
-        chk(ctx, kmx_cquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_cquery_result_copy_hits");
-        chk(ctx, kmx_cquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_cquery_result_copy_sums");
-        chk(ctx, kmx_cquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_cquery_result_copy_kmers");
-        kmx_cquery_result_free(first);
-        std::lock_guard<std::mutex> lk(mu);
-        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
-        for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
-        kmers = sk;      // (every shard walks every query: the same numbers)
-      } catch (const std::exception& e) { die(e.what()); }
+        kmx_cquery_task t; memset(&t, 0, sizeof t);
+        t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+        t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
+        t.rows = rows.data(); t.bitw = w; t.min_class = min_class;
+        t.hits = first ? kmx_cquery_result_hits_dev(first) : nullptr;
+        t.sums = first ? kmx_cquery_result_sums_dev(first) : nullptr;
+        kmx_cquery_result* r = nullptr;
+        chk(ctx, kmx_cquery_host(ctx, &t, &r), "kmx_cquery_host");
+        chk(ctx, kmx_cquery_result_wait(r), "kmx_cquery");      // (the bodies are reused by the next group)
+        if (!first) first = r; else kmx_cquery_result_free(r);
+      }
+      if (!first) return;      // (more shards than partitions)
+      std::vector<uint32_t> sh(nq * N);
+      std::vector<uint64_t> ss(nq * N);
+      chk(ctx, kmx_cquery_result_copy_hits(first, sh.data(), sh.size()), "kmx_cquery_result_copy_hits");
+      chk(ctx, kmx_cquery_result_copy_sums(first, ss.data(), ss.size()), "kmx_cquery_result_copy_sums");
+      chk(ctx, kmx_cquery_result_copy_kmers(first, sk.data(), sk.size()), "kmx_cquery_result_copy_kmers");
+      kmx_cquery_result_free(first);
+      std::lock_guard<std::mutex> lk(mu);
+      for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+      for (size_t i = 0; i < ss.size(); i++) sums[i] += ss[i];
+      kmers = sk;      // (every shard walks every query: the same numbers)
     };
     // every shard sees all queries of the batch; its groups add up on its device, the shards' tables on the host
     auto shard = [&](uint32_t g) {
-      try {
-        kmx_ctx* ctx = ctxs[g];
-        kmx_query_result* first = nullptr;
-        std::vector<std::vector<uint8_t>> own;
-        const bool keep = groups[g].size() == 1;
-        std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
-        std::vector<const uint8_t*> rows(P);
-        std::vector<uint32_t> sk(nq);
-        for (size_t gi = 0; gi < groups[g].size(); gi++) {
-          std::fill(rows.begin(), rows.end(), nullptr);
-          const bool loaded = keep && bodies.size() == groups[g][gi].size();
-          if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
-          for (size_t i = 0; i < groups[g][gi].size(); i++) {
-            const uint32_t p = groups[g][gi][i];
-            if (!loaded) {
-              std::ifstream f(files[p], std::ios::binary);
-              bodies[i].resize(body);
-              if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
-            }
-            rows[p] = bodies[i].data();
+      kmx_ctx* ctx = dev.ctxs[g];
+      kmx_query_result* first = nullptr;
+      std::vector<std::vector<uint8_t>> own;
+      const bool keep = groups[g].size() == 1;
+      std::vector<std::vector<uint8_t>>& bodies = keep ? kept[g] : own;
+      std::vector<const uint8_t*> rows(P);
+      std::vector<uint32_t> sk(nq);
+      for (size_t gi = 0; gi < groups[g].size(); gi++) {
+        std::fill(rows.begin(), rows.end(), nullptr);
+        const bool loaded = keep && bodies.size() == groups[g][gi].size();
+        if (!loaded) bodies.assign(groups[g][gi].size(), std::vector<uint8_t>());
+        for (size_t i = 0; i < groups[g][gi].size(); i++) {
+          const uint32_t p = groups[g][gi][i];
+          if (!loaded) {
+            std::ifstream f(files[p], std::ios::binary);
+            bodies[i].resize(body);
+            if (!f.seekg(CMBF_HEADER) || !f.read((char*)bodies[i].data(), (std::streamsize)body)) die("short read: " + files[p]);
           }
-          kmx_query_task t; memset(&t, 0, sizeof t);
-          t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
-          t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
-          t.rows = rows.data(); t.hits = first ? kmx_query_result_hits_dev(first) : nullptr;
-          kmx_query_result* r = nullptr;
-          chk(ctx, kmx_query_host(ctx, &t, &r), "kmx_query_host");
-          chk(ctx, kmx_query_result_wait(r), "kmx_query");      // (the bodies are reused by the next group)
-          if (!first) first = r; else kmx_query_result_free(r);
+          rows[p] = bodies[i].data();
         }
-        if (!first) return;      // (more shards than partitions)
-        std::vector<uint32_t> sh(nq * N);
-        chk(ctx, kmx_query_result_copy_hits(first, sh.data(), sh.size()), "kmx_query_result_copy_hits");
-        chk(ctx, kmx_query_result_copy_kmers(first, sk.data(), sk.size()), "kmx_query_result_copy_kmers");
-        kmx_query_result_free(first);
-        std::lock_guard<std::mutex> lk(mu);
-        for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
-        kmers = sk;      // (every shard walks every query: the same numbers)
-      } catch (const std::exception& e) { die(e.what()); }
+        kmx_query_task t; memset(&t, 0, sizeof t);
+        t.bases = bases.data() + offs[q0]; t.offsets = boffs.data(); t.n_seqs = nq;
+        t.kmer_size = k; t.minim_size = msize; t.repart = table.data(); t.nb_parts = (uint32_t)P; t.n_cols = N; t.window = W;
+        t.rows = rows.data(); t.hits = first ? kmx_query_result_hits_dev(first) : nullptr;
+        kmx_query_result* r = nullptr;
+        chk(ctx, kmx_query_host(ctx, &t, &r), "kmx_query_host");
+        chk(ctx, kmx_query_result_wait(r), "kmx_query");      // (the bodies are reused by the next group)
+        if (!first) first = r; else kmx_query_result_free(r);
+      }
+      if (!first) return;      // (more shards than partitions)
+      std::vector<uint32_t> sh(nq * N);
+      chk(ctx, kmx_query_result_copy_hits(first, sh.data(), sh.size()), "kmx_query_result_copy_hits");
+      chk(ctx, kmx_query_result_copy_kmers(first, sk.data(), sk.size()), "kmx_query_result_copy_kmers");
+      kmx_query_result_free(first);
+      std::lock_guard<std::mutex> lk(mu);
+      for (size_t i = 0; i < sh.size(); i++) hits[i] += sh[i];
+      kmers = sk;      // (every shard walks every query: the same numbers)
     };
     // --z: one shard; the groups of a batch fill one bits table on the device, the batch's last group runs the window pass.
     // n_kmers are K-positions
-    auto zshard = [&]() {
-      kmx_ctx* ctx = ctxs[0];
+    auto zshard = [&](uint32_t) {
+      kmx_ctx* ctx = dev.ctxs[0];
       kmx_zquery_result* first = nullptr;
       std::vector<std::vector<uint8_t>> own;
       const bool keep = groups[0].size() == 1;
@@ -497,13 +456,9 @@ int kmx_query_main(int argc, char** argv)
       }
       kmx_zquery_result_free(first);
     };
-    if (o.z >= 0) { try { zshard(); } catch (const std::exception& e) { die(e.what()); } }
-    else {
-      std::vector<std::thread> workers;
-      for (uint32_t g = 1; g < G; g++) { if (bfc) workers.emplace_back(cshard, g); else workers.emplace_back(shard, g); }
-      if (bfc) cshard(0); else shard(0);
-      for (std::thread& t : workers) t.join();
-    }
+    if (o.z >= 0) in_shards(1, zshard);
+    else if (bfc) in_shards(G, cshard);
+    else in_shards(G, shard);
     std::string txt;
     for (uint64_t i = 0; i < nq; i++) {
       const std::string& name = names[q0 + i];
@@ -520,6 +475,6 @@ int kmx_query_main(int argc, char** argv)
     if (fwrite(txt.data(), 1, txt.size(), out) != txt.size()) die("write failed: " + (o.out.empty() ? std::string("stdout") : o.out));
   }
   if (out != stdout) { if (fclose(out) != 0) die("write failed: " + o.out); } else fflush(stdout);
-  for (uint32_t g = 0; g < G; g++) kmx_destroy(ctxs[g]);
+  dev.close();
   return 0;
 }

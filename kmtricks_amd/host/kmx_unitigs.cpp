@@ -5,18 +5,9 @@
 // are the run's rows in (partition ascending, file order); their keys are copied out of the bodies as they are read.  The graph is built
 // by one kmx_unitigs_host call on one device; the table comes from kmx_groupsum_host over every partition, the device tables
 // accumulating, in windows of unitigs that fit --batch-mb.  Every check that needs no GPU comes before kmx_create.
-#include <kmx.h>
-#include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <sstream>
-#include <thread>
-#include "kmx_io.hpp"
-#include "kmx_run.hpp"
+#include "kmx_driver.hpp"
 
-namespace fs = std::filesystem;
-using namespace kmxio;
+using namespace kmxdrv;
 
 namespace {
 
@@ -40,22 +31,20 @@ const char* USAGE = "usage: kmx unitigs --run <run dir made with --mode kmer:cou
 UOpt parse(int argc, char** argv)
 {
   UOpt o;
-  auto need = [&](int& i) -> std::string { if (i + 1 >= argc) die(std::string("missing value for ") + argv[i] + "\n" + USAGE); return argv[++i]; };
-  auto num = [&](int& i) -> unsigned long { const std::string v = need(i); try { size_t n = 0; if (v.empty() || v[0] == '-') throw 1; const unsigned long x = std::stoul(v, &n); if (n != v.size()) throw 1; return x; } catch (...) { die(std::string("bad number for ") + argv[i - 1] + ": " + v); } };
-  auto u32 = [&](int& i) -> uint32_t { const unsigned long x = num(i); if (x > 0xFFFFFFFFul) die(std::string(argv[i - 1]) + " does not fit 32 bits"); return (uint32_t)x; };
+  const Args in{argc, argv, USAGE};
   for (int i = 2; i < argc; i++) {
     const std::string a = argv[i];
-    if (a == "--run") o.run = need(i);
-    else if (a == "--kmers") o.kmers = need(i);
-    else if (a == "--output") o.out = need(i);
-    else if (a == "--table") o.table = need(i);
-    else if (a == "--value") o.value = need(i);
-    else if (a == "--samples") o.samples = need(i);
-    else if (a == "--min-abund") { o.min_abund = u32(i); if (o.min_abund == 0) die("--min-abund must be at least 1"); }
-    else if (a == "--gpus") o.gpus = u32(i);
-    else if (a == "--batch-mb") o.batch_mb = num(i);
-    else if (a == "-v" || a == "--verbose") { o.verbose = true; if (i + 1 < argc && argv[i + 1][0] != '-') i++; }
-    else die("unknown option " + a + "\n" + USAGE);
+    if (a == "--run") o.run = in.need(i);
+    else if (a == "--kmers") o.kmers = in.need(i);
+    else if (a == "--output") o.out = in.need(i);
+    else if (a == "--table") o.table = in.need(i);
+    else if (a == "--value") o.value = in.need(i);
+    else if (a == "--samples") o.samples = in.need(i);
+    else if (a == "--min-abund") { o.min_abund = in.u32(i); if (o.min_abund == 0) die("--min-abund must be at least 1"); }
+    else if (a == "--gpus") o.gpus = in.u32(i);
+    else if (a == "--batch-mb") o.batch_mb = in.num(i);
+    else if (in.verbose(a, i)) o.verbose = true;
+    else in.unknown(a);
   }
   if (o.run.empty()) die(std::string("--run is required\n") + USAGE);
   if (o.out.empty() && o.table.empty()) die(std::string("one of --output and --table is required\n") + USAGE);
@@ -63,25 +52,6 @@ UOpt parse(int argc, char** argv)
   if (!o.value.empty() && o.value != "mean" && o.value != "frac" && o.value != "sum" && o.value != "present") die("--value must be mean, frac, sum or present");
   if (o.gpus < 1 || o.gpus > 16) die("--gpus must be in [1, 16]");
   return o;
-}
-
-void chk(kmx_ctx* c, int rc, const char* what) { if (rc != KMX_OK) die(std::string(what) + ": " + kmx_last_error(c)); }
-
-std::string option_of(const std::string& line, const std::string& key)
-{
-  const size_t at = line.find(" " + key + "="); if (at == std::string::npos) return "";
-  const size_t b = at + key.size() + 2, e = line.find(',', b);
-  std::string v = line.substr(b, e == std::string::npos ? std::string::npos : e - b);
-  while (!v.empty() && (v.back() == '\n' || v.back() == '\r' || v.back() == ' ')) v.pop_back();
-  return v;
-}
-
-void write_file(const std::string& path, const std::string& s)
-{
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) die("Unable to write at " + path);
-  if (!s.empty() && fwrite(s.data(), 1, s.size(), f) != s.size()) die("write failed: " + path);
-  if (fclose(f) != 0) die("write failed: " + path);
 }
 
 // a k-mer as the matrices' keys hold it: digit i is base k - 1 - i, A0 C1 T2 G3; kw words, low word first
@@ -109,55 +79,22 @@ bool canonical_key(const std::string& s, uint32_t kw, Key& out)
 int kmx_unitigs_main(int argc, char** argv)
 {
   const UOpt o = parse(argc, argv);
-  const std::string& run = o.run;
   // ---- the run directory; every check before kmx_create ----
-  if (!fs::exists(run + "/kmtricks.fof")) die(run + " is not a kmtricks runtime directory.");
-  std::string opt; { std::ifstream f(run + "/options.txt"); if (!f) die("Unable to read at " + run + "/options.txt"); std::getline(f, opt); }
-  const std::string mode = option_of(opt, "count_format") + ":" + option_of(opt, "mode") + ":" + option_of(opt, "format");
-  const bool count = mode == "kmer:count:bin";
-  if (!count && mode != "kmer:pa:bin")
-    die("kmx unitigs needs a run made with --mode kmer:count:bin or kmer:pa:bin (the keys of hash and Bloom filter runs are not k-mers); " + run + " was made with " + mode);
-  const char* ext = count ? "count" : "pa";
-  const uint64_t magic = count ? MAGIC_MATRIX : MAGIC_PA;
-  const size_t hdr = 45, cols_at = count ? 33 : 29;
-  if (!count && o.min_abund > 1) die("--min-abund above 1 needs counts: " + run + " was made with " + mode);
+  RunDir dir;
+  dir.at("unitigs", o.run);
+  dir.read_mode(KMER_KINDS, "kmer:count:bin or kmer:pa:bin (the keys of hash and Bloom filter runs are not k-mers)");
+  const std::string& run = dir.run;
+  const bool count = dir.count();
+  if (!count && o.min_abund > 1) die("--min-abund above 1 needs counts: " + run + " was made with " + dir.mode);
   const std::string value = !o.value.empty() ? o.value : count ? "mean" : "frac";
-  if (!count && (value == "sum" || value == "mean")) die("--value " + value + " needs counts: " + run + " was made with " + mode);
-  uint32_t k = 0;
-  try { k = (uint32_t)std::stoul(option_of(opt, "kmer_size")); } catch (...) { die(run + "/options.txt names no kmer_size"); }
-  if (k < 8 || k > 127) die("the run's options.txt names a k-mer size outside [8, 127]");
-  uint16_t rp = 0;
-  read_repartition(run + "/repartition_gatb/repartition.minimRepart", &rp);
-  const uint64_t P = rp;
-  if (P == 0) die("the run's partition count is outside [1, 65535]");
-  const std::vector<Sample> samples = parse_fof(run + "/kmtricks.fof", 1);
-  const uint32_t N = (uint32_t)samples.size();
-  if (N == 0) die(run + "/kmtricks.fof names no sample");
+  if (!count && (value == "sum" || value == "mean")) die("--value " + value + " needs counts: " + run + " was made with " + dir.mode);
+  dir.shape();
+  const uint32_t N = dir.N, k = dir.k, kw = dir.kw;
+  const uint64_t P = dir.P, stride = dir.stride;
+  const std::vector<Sample>& samples = dir.samples;
   std::vector<uint32_t> cols;
-  if (!o.samples.empty()) {
-    std::ifstream f(o.samples);
-    if (!f) die("Unable to read at " + o.samples);
-    std::map<std::string, uint32_t> at;
-    for (uint32_t i = 0; i < N; i++) at[samples[i].id] = i;
-    std::vector<bool> seen(N, false);
-    std::string line;
-    for (uint64_t ln = 1; std::getline(f, line); ln++) {
-      std::istringstream is(line);
-      std::string id, more;
-      if (!(is >> id)) continue;
-      const std::string where = o.samples + " line " + std::to_string(ln) + ": ";
-      if (is >> more) die(where + "expected one sample id");
-      const auto it = at.find(id);
-      if (it == at.end()) die(where + "sample " + id + " is not in the run's kmtricks.fof");
-      if (seen[it->second]) die(where + "sample " + id + " is named twice");
-      seen[it->second] = true;
-      cols.push_back(it->second);
-    }
-    if (cols.empty()) die(o.samples + " names no sample");
-  }
+  if (!o.samples.empty()) cols = read_sample_list(o.samples, samples);
   const uint32_t M = o.samples.empty() ? N : (uint32_t)cols.size();
-  const uint32_t kw = (k + 31) / 32;
-  const uint64_t stride = 8ull * kw + (count ? 4ull * N : (N + 7) / 8);
   // the list of k-mers: canonical keys, sorted
   const bool listed = !o.kmers.empty();
   std::vector<Key> want;
@@ -179,32 +116,15 @@ int kmx_unitigs_main(int argc, char** argv)
     std::sort(want.begin(), want.end(), [&](const Key& a, const Key& b) { return key_less(a.data(), b.data(), kw); });
     want.erase(std::unique(want.begin(), want.end()), want.end());
   }
-  std::vector<std::string> files(P);
-  for (uint64_t p = 0; p < P; p++) {
-    const std::string plain = run + "/matrices/matrix_" + std::to_string(p) + "." + ext;
-    files[p] = !fs::exists(plain) && fs::exists(plain + ".lz4") ? plain + ".lz4" : plain;
-    std::ifstream f(files[p], std::ios::binary);
-    uint8_t h[49];
-    if (!f || !f.read((char*)h, (std::streamsize)hdr)) die("Unable to read at " + plain);
-    if (rd<uint64_t>(&h[0]) != MAGIC_BASE || rd<uint64_t>(&h[13]) != magic) die("Invalid file format: " + files[p]);
-    if (rd<uint32_t>(&h[21]) != k || rd<uint32_t>(&h[25]) != kw)
-      die(files[p] + " was made with k = " + std::to_string(rd<uint32_t>(&h[21])) + " in " + std::to_string(rd<uint32_t>(&h[25])) + " words, the run's options.txt says " + std::to_string(k));
-    const uint32_t c = rd<uint32_t>(&h[cols_at]);
-    if (c != N) die(files[p] + " has rows of " + std::to_string(c) + " columns, the run's kmtricks.fof has " + std::to_string(N) + " samples");
-  }
-  auto read_body = [&](uint64_t p) {
-    std::vector<uint8_t> raw = slurp(files[p]);
-    std::vector<uint8_t> body = body_of(raw, hdr, magic, files[p]);
-    if (body.size() % stride) die("truncated matrix (its body is no whole number of rows of " + std::to_string(stride) + " bytes): " + files[p]);
-    return body;
-  };
+  dir.open_files();
 
   // ---- the nodes: the kept rows' keys, and per partition which node a row is (0xFFFFFFFF: none) ----
   std::vector<uint64_t> keys;
   std::vector<std::vector<uint32_t>> node_of(P);
   std::vector<bool> found(want.size(), false);
   for (uint64_t p = 0; p < P; p++) {
-    const std::vector<uint8_t> body = read_body(p);
+    const auto loaded = dir.load(p);
+    const std::vector<uint8_t>& body = *loaded;
     const uint64_t rows = body.size() / stride;
     node_of[p].assign(rows, 0xFFFFFFFFu);
     std::vector<uint64_t> rk(kw);
@@ -234,11 +154,9 @@ int kmx_unitigs_main(int argc, char** argv)
   }
 
   // ---- the graph, on one device ----
-  if (kmx_version() != KMX_VERSION) die("libkmx.so is not the version this driver was built for");
-  const uint32_t G = o.gpus, ndev = (uint32_t)std::max(1, kmx_device_count());
-  std::vector<kmx_ctx*> ctxs(G, nullptr);
-  for (uint32_t g = 0; g < G; g++) if (kmx_create((int)(g % ndev), &ctxs[g]) != KMX_OK) die(std::string("kmx_create: ") + kmx_last_error(nullptr));
-  kmx_ctx* c0 = ctxs[0];
+  Devices dev = open_devices(o.gpus, o.batch_mb ? o.batch_mb : 256, 4);      // (the table's budget is given: the devices' memory is not asked)
+  const uint32_t G = dev.G();
+  kmx_ctx* c0 = dev.ctxs[0];
   kmx_unitigs_task ut; memset(&ut, 0, sizeof ut);
   ut.keys = keys.data(); ut.n = n; ut.kmer_size = k; ut.key_words = kw;
   kmx_unitigs_result* ur = nullptr;
@@ -252,7 +170,7 @@ int kmx_unitigs_main(int argc, char** argv)
   chk(c0, kmx_unitigs_result_copy_len(ur, len.data(), U), "kmx_unitigs_result_copy_len");
   chk(c0, kmx_unitigs_result_copy_circ(ur, circ.data(), U), "kmx_unitigs_result_copy_circ");
   chk(c0, kmx_unitigs_result_copy_seq_off(ur, seq_off.data(), U + 1), "kmx_unitigs_result_copy_seq_off");
-  if (o.verbose) fprintf(stderr, "[kmx unitigs] %llu k-mers of %llu partitions (%s), k = %u: %llu unitigs\n", (unsigned long long)n, (unsigned long long)P, mode.c_str(), k,
+  if (o.verbose) fprintf(stderr, "[kmx unitigs] %llu k-mers of %llu partitions (%s), k = %u: %llu unitigs\n", (unsigned long long)n, (unsigned long long)P, dir.mode.c_str(), k,
                          (unsigned long long)U);
   if (!o.out.empty()) {
     std::vector<uint8_t> seqs(kmx_unitigs_result_seq_bytes(ur));
@@ -264,7 +182,7 @@ int kmx_unitigs_main(int argc, char** argv)
       t.append((const char*)&seqs[seq_off[u]], seq_off[u + 1] - seq_off[u]);
       t += '\n';
     }
-    write_file(o.out, t);
+    write_text(o.out, t);
   }
   kmx_unitigs_result_free(ur);
   keys = std::vector<uint64_t>();
@@ -277,47 +195,40 @@ int kmx_unitigs_main(int argc, char** argv)
     t += "\n";
     for (uint64_t p = 0; p < P; p++) for (uint32_t& v : node_of[p]) if (v != 0xFFFFFFFFu) v = unitig[v];      // a row's label: its unitig
     const uint64_t per_group = 4 + 4ull * M + (sums ? 8ull * M : 0);
-    const uint64_t budget = (o.batch_mb ? o.batch_mb : 256) << 20;
-    const uint64_t win = std::min<uint64_t>(std::max<uint64_t>(budget / per_group, 1), std::min<uint64_t>(std::max<uint64_t>(U, 1), (1ull << 32) / M));
+    const uint64_t win = std::min<uint64_t>(std::max<uint64_t>(dev.budget / per_group, 1), std::min<uint64_t>(std::max<uint64_t>(U, 1), (1ull << 32) / M));
     if (o.verbose) fprintf(stderr, "[kmx unitigs] table: %u of %u samples, value %s, windows of %llu unitigs, %u shards\n", M, N, value.c_str(), (unsigned long long)win, G);
     for (uint64_t g0 = 0; g0 < U; g0 += win) {
       const uint32_t Gw = (uint32_t)std::min<uint64_t>(win, U - g0);
       std::vector<uint32_t> size(Gw, 0), present((uint64_t)Gw * M, 0);
       std::vector<uint64_t> sum(sums ? (uint64_t)Gw * M : 0, 0);
       std::mutex mu;
-      auto shard = [&](uint32_t g) {
-        try {
-          kmx_ctx* ctx = ctxs[g];
-          kmx_groupsum_result* first = nullptr;
-          for (uint64_t p = g; p < P; p += G) {
-            const std::vector<uint8_t> body = read_body(p);
-            kmx_groupsum_task gt; memset(&gt, 0, sizeof gt);
-            gt.key_words = kw; gt.mode = count ? KMX_MODE_COUNT : KMX_MODE_PA; gt.n_cols = N; gt.n_use = M;
-            gt.rows = body.data(); gt.n_rows = body.size() / stride; gt.cols = cols.empty() ? nullptr : cols.data(); gt.groups = node_of[p].data();
-            gt.min_abund = o.min_abund; gt.flags = sums ? KMX_GROUPSUM_SUMS : 0; gt.g0 = (uint32_t)g0; gt.n_groups = Gw;
-            if (first) { gt.present = kmx_groupsum_result_present_dev(first); gt.size = kmx_groupsum_result_size_dev(first); gt.sums = sums ? kmx_groupsum_result_sums_dev(first) : nullptr; }
-            kmx_groupsum_result* r = nullptr;
-            chk(ctx, kmx_groupsum_host(ctx, &gt, &r), "kmx_groupsum_host");
-            chk(ctx, kmx_groupsum_result_wait(r), "kmx_groupsum");      // (the body goes at the end of this trip)
-            if (first) kmx_groupsum_result_free(r); else first = r;
-          }
-          if (!first) return;
-          std::vector<uint32_t> sz(Gw), pr((uint64_t)Gw * M);
-          std::vector<uint64_t> sm(sum.size());
-          chk(ctx, kmx_groupsum_result_copy_size(first, sz.data(), sz.size()), "kmx_groupsum_result_copy_size");
-          chk(ctx, kmx_groupsum_result_copy_present(first, pr.data(), pr.size()), "kmx_groupsum_result_copy_present");
-          if (sums) chk(ctx, kmx_groupsum_result_copy_sums(first, sm.data(), sm.size()), "kmx_groupsum_result_copy_sums");
-          kmx_groupsum_result_free(first);
-          std::lock_guard<std::mutex> lk(mu);
-          for (size_t i = 0; i < sz.size(); i++) size[i] += sz[i];
-          for (size_t i = 0; i < pr.size(); i++) present[i] += pr[i];
-          for (size_t i = 0; i < sm.size(); i++) sum[i] += sm[i];
-        } catch (const std::exception& e) { die(e.what()); }
-      };
-      std::vector<std::thread> workers;
-      for (uint32_t g = 1; g < G; g++) workers.emplace_back(shard, g);
-      shard(0);
-      for (std::thread& w : workers) w.join();
+      in_shards(G, [&](uint32_t g) {
+        kmx_ctx* ctx = dev.ctxs[g];
+        kmx_groupsum_result* first = nullptr;
+        for (uint64_t p = g; p < P; p += G) {
+          const auto body = dir.load(p);
+          kmx_groupsum_task gt; memset(&gt, 0, sizeof gt);
+          gt.key_words = kw; gt.mode = dir.rmode(); gt.n_cols = N; gt.n_use = M;
+          gt.rows = body->data(); gt.n_rows = body->size() / stride; gt.cols = cols.empty() ? nullptr : cols.data(); gt.groups = node_of[p].data();
+          gt.min_abund = o.min_abund; gt.flags = sums ? KMX_GROUPSUM_SUMS : 0; gt.g0 = (uint32_t)g0; gt.n_groups = Gw;
+          if (first) { gt.present = kmx_groupsum_result_present_dev(first); gt.size = kmx_groupsum_result_size_dev(first); gt.sums = sums ? kmx_groupsum_result_sums_dev(first) : nullptr; }
+          kmx_groupsum_result* r = nullptr;
+          chk(ctx, kmx_groupsum_host(ctx, &gt, &r), "kmx_groupsum_host");
+          chk(ctx, kmx_groupsum_result_wait(r), "kmx_groupsum");      // (the body goes at the end of this trip)
+          if (first) kmx_groupsum_result_free(r); else first = r;
+        }
+        if (!first) return;
+        std::vector<uint32_t> sz(Gw), pr((uint64_t)Gw * M);
+        std::vector<uint64_t> sm(sum.size());
+        chk(ctx, kmx_groupsum_result_copy_size(first, sz.data(), sz.size()), "kmx_groupsum_result_copy_size");
+        chk(ctx, kmx_groupsum_result_copy_present(first, pr.data(), pr.size()), "kmx_groupsum_result_copy_present");
+        if (sums) chk(ctx, kmx_groupsum_result_copy_sums(first, sm.data(), sm.size()), "kmx_groupsum_result_copy_sums");
+        kmx_groupsum_result_free(first);
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < sz.size(); i++) size[i] += sz[i];
+        for (size_t i = 0; i < pr.size(); i++) present[i] += pr[i];
+        for (size_t i = 0; i < sm.size(); i++) sum[i] += sm[i];
+      });
       char buf[64];
       for (uint32_t u = 0; u < Gw; u++) {
         if (size[u] != len[g0 + u]) die("kmx_groupsum: a unitig's rows are not its k-mers");
@@ -333,8 +244,8 @@ int kmx_unitigs_main(int argc, char** argv)
         t += "\n";
       }
     }
-    write_file(o.table, t);
+    write_text(o.table, t);
   }
-  for (uint32_t g = 0; g < G; g++) kmx_destroy(ctxs[g]);
+  dev.close();
   return 0;
 }
