@@ -48,6 +48,10 @@
  *                               a set of distinct canonical k-mers compacted into the unitigs of its de Bruijn graph
  *   kmx_groupsum_dev / _host    no counterpart either (MUSET's `kmat_tools unitig`): a matrix's rows summed by a label per row -- per
  *                               group and sample the rows present and the counts' sum, the unitig x sample table among others
+ *   kmx_kset_dev / _host        no counterpart either: a set of canonical k-mers (duplicates allowed) resident on a device as a hash table
+ *                               built for membership at one look-up a base
+ *   kmx_match_dev / _host       no counterpart either (kmdiff's map-back, the read fetch of a k-mer GWAS, back_to_sequences): per read the
+ *                               k-mers it shares with a kset, their strand, the bases they cover, first and last hit; per k-mer its occurrences
  *   kmx_superk_partition       replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -1368,6 +1372,113 @@ double    kmx_groupsum_result_kernel_ms(kmx_groupsum_result* r);         /* need
  *  */
 uint64_t  kmx_groupsum_result_algo_bytes(kmx_groupsum_result* r);
 void      kmx_groupsum_result_free(kmx_groupsum_result* r);
+
+/* ------------------------------------------------------------------- kset */
+
+/* A set of k-mers resident on a device: built once, used by many kmx_match_* calls (the significant k-mers of kmx_diff_* / kmx_assoc_*,
+ * the k-mers of the unitigs of kmx_unitigs_*, the row keys of a run).  This comment is the contract.
+ * INPUT: keys[n][key_words] u64, low word first; dense (stride 8 * key_words bytes), 8-byte aligned.  key_words = ceil(kmer_size / 32).
+ * The encoding is the matrices' own, exactly as the unitigs section says: digit i (bits 2i, 2i + 1) is base k - 1 - i, A0 C1 T2 G3, the
+ * complement is digit ^ 2.  The keys are CANONICAL k-mers in ANY order.  DUPLICATES ARE ALLOWED: the ID of a key is the least index at
+ * which it occurs, n_distinct the number of ids (the indices v with id[v] == v).
+ * The set keeps its own copy of the keys: the caller's are free for reuse once kmx_kset_wait has returned.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: kmer_size outside 8 ... 127; key_words != ceil(kmer_size / 32); null keys with
+ * n > 0; flag bits.  KMX_E_UNSUPPORTED: n > 2^31.  n = 0 is a valid, empty set.
+ * DATA ERRORS, found on the device; kmx_kset_wait, every accessor and every kmx_match_* call on the set return them as KMX_E_INVAL, the
+ * message naming the cause: a key with bits set from 2 k upwards; a key greater than its reverse complement.
+ * MEMORY the set holds until it is freed: 8 * key_words bytes a key plus the table -- 8 bytes a slot, (tag << 32) | index, T = the power
+ * of two >= 2 n slots: 16 to 32 bytes a key.  4 bytes a key of scratch while kmx_kset_copy_ids runs.
+ * Free a set when the kmx_match_* results made from it have been waited for. */
+typedef struct {
+  const uint64_t* keys;          /* n * key_words words */
+  uint64_t        n;
+  uint32_t        kmer_size;     /* k: 8 ... 127 */
+  uint32_t        key_words;     /* ceil(k / 32) */
+  uint32_t        flags;         /* 0 */
+  uint32_t        reserved;      /* not read */
+} kmx_kset_task;                 /* 32 bytes */
+
+typedef struct kmx_kset kmx_kset;
+
+/* _dev: keys a DEVICE pointer, copied by the call on the context's stream, the kernels queued behind it and the call back without
+ * waiting.  _host: a HOST pointer, uploaded on a stream of its own. */
+int kmx_kset_dev(kmx_ctx* ctx, const kmx_kset_task* task, kmx_kset** out);
+int kmx_kset_host(kmx_ctx* ctx, const kmx_kset_task* task, kmx_kset** out);
+int       kmx_kset_wait(kmx_kset* s);
+/* (the accessors below wait for the build themselves; after a data error each returns that error or 0) */
+uint64_t  kmx_kset_n(kmx_kset* s);
+uint64_t  kmx_kset_n_distinct(kmx_kset* s);
+uint32_t  kmx_kset_kmer_size(kmx_kset* s);
+int       kmx_kset_copy_ids(kmx_kset* s, uint32_t* host_dst, uint64_t dst_entries);      /* n: for every input index, the id of its key */
+double    kmx_kset_kernel_ms(kmx_kset* s);      /* clearing the table + k_ks_build + the count of ids (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+void      kmx_kset_free(kmx_kset* s);
+
+/* ------------------------------------------------------------------ match */
+
+/* Reads against a set: which reads hold the set's k-mers, how many, on which strand, over how much of the read, and how often each k-mer
+ * occurs (kmdiff's map-back, the read fetch of a k-mer GWAS, back_to_sequences).  This comment is the contract.
+ * For every read q and every position i with i + k <= len(q) whose k bases are all ACGT (either case), let x be the k-mer at i and c its
+ * canonical form.
+ *   n_kmers[q]  counts the position.
+ *   When c is in the set, with id j:
+ *     hits[q]   counts it;
+ *     fwd[q]    counts it when x == c: the read shows the key itself (a palindrome counts as forward);
+ *     the bases i ... i + k - 1 of q are COVERED;
+ *     first[q]  is the least such i and last[q] the greatest, relative to the read's start; both 0xFFFFFFFF when there is none;
+ *     occ[j]    counts it (KMX_MATCH_OCC).  Only ids are ever counted: a duplicate's later indices keep what they had.
+ *   covered[q]  the number of bases of q that lie in at least one hit.
+ *   ids[p]      (KMX_MATCH_IDS; u32, one per base of the call) j for the position p = offsets[q] + i of a hit, 0xFFFFFFFF everywhere else.
+ * Every occurrence counts; a read without a valid k-mer is reported with zeros.  Every result is an integer that does not depend on
+ * the order of the adds.
+ * occ: NULL (with KMX_MATCH_OCC the result owns a zeroed table), or a DEVICE table of n u64 (n the set's) that the call ADDS to: the
+ * batches of a set of reads accumulate on the device.
+ * EXAMPLE.  k = 5 (below the call's own limit: for the reader and the CPU restatement), keys (TTGCA, ATTGC, TTGCA, TGCAC) = (692, 173,
+ * 692, 721): ids = (0, 1, 0, 3), n_distinct = 3.  Reads (CATTGCAC, ttgcaNtgcaat, ACGT, GGGGGGG, TGCAC):
+ *   recs (n_kmers, hits, fwd, covered, first, last) = (4,3,3,7,1,3), (3,3,1,11,0,7), (0,0,0,0,-,-), (3,0,0,0,-,-), (1,1,1,5,0,0)
+ *   occ = (3, 2, 0, 2); the ids that are not 0xFFFFFFFF, batch position -> id: 1 -> 1, 2 -> 0, 3 -> 3, 8 -> 0, 14 -> 0, 15 -> 1, 31 -> 3
+ * LIMITS, each refused before any GPU work: a null set or one of another context, flag bits, null reads, an occ table without
+ * KMX_MATCH_OCC (KMX_E_INVAL); fewer than 2^31 reads and fewer than 2^32 bases a call (KMX_E_UNSUPPORTED).  n_seqs = 0 is valid.  A set
+ * with a data error: that error.
+ * Scratch from the context's pool: 8 bytes per 64 bases (the hit bits).  The result keeps 24 bytes a read, with KMX_MATCH_IDS 4 bytes a
+ * base, with KMX_MATCH_OCC and no table of the caller's 8 bytes a key. */
+#define KMX_MATCH_IDS 1u
+#define KMX_MATCH_OCC 2u
+typedef struct { uint32_t n_kmers, hits, fwd, covered, first, last; } kmx_match_rec;      /* 24 bytes */
+typedef struct {
+  const kmx_kset* set;
+  const char*     bases;
+  const uint64_t* offsets;       /* [n_seqs + 1], offsets[0] = 0 */
+  uint64_t        n_seqs;
+  uint32_t        flags;         /* KMX_MATCH_IDS | KMX_MATCH_OCC */
+  uint32_t        reserved;      /* not read */
+  uint64_t*       occ;           /* NULL, or (with KMX_MATCH_OCC) a DEVICE table of n u64 to accumulate into */
+  uint64_t        reserved2;     /* not read */
+} kmx_match_task;                /* 56 bytes */
+
+typedef struct kmx_match_result kmx_match_result;
+
+/* _dev: bases and offsets DEVICE pointers; _host: HOST pointers, uploaded on a stream of its own (free for reuse once _result_wait has
+ * returned).  The same division as the query calls. */
+int kmx_match_dev(kmx_ctx* ctx, const kmx_match_task* task, kmx_match_result** out);
+int kmx_match_host(kmx_ctx* ctx, const kmx_match_task* task, kmx_match_result** out);
+int       kmx_match_result_wait(kmx_match_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t  kmx_match_result_n_seqs(const kmx_match_result* r);
+uint64_t  kmx_match_result_n_bases(const kmx_match_result* r);
+int       kmx_match_result_copy_recs(kmx_match_result* r, kmx_match_rec* host_dst, uint64_t dst_entries);      /* n_seqs */
+int       kmx_match_result_copy_ids(kmx_match_result* r, uint32_t* host_dst, uint64_t dst_entries);            /* n_bases; KMX_E_INVAL without KMX_MATCH_IDS */
+uint64_t* kmx_match_result_occ_dev(kmx_match_result* r);                                                       /* the table the call added to; NULL without KMX_MATCH_OCC */
+int       kmx_match_result_copy_occ(kmx_match_result* r, uint64_t* host_dst, uint64_t dst_entries);            /* n: the table as it stands; KMX_E_INVAL without KMX_MATCH_OCC */
+uint64_t  kmx_match_result_total_kmers(kmx_match_result* r);
+uint64_t  kmx_match_result_total_hits(kmx_match_result* r);
+double    kmx_match_result_kernel_ms(kmx_match_result* r);      /* needs kmx_set_profiling(ctx, 1); < 0 if unavailable */
+/* the same interval in its parts: the clears + k_mt_probe; k_mt_cover + k_mt_last; either pointer may be NULL */
+int       kmx_match_result_kernel_parts_ms(kmx_match_result* r, double* probe_ms, double* cover_ms);
+/* algorithmic bytes: the bases + 8 per valid k-mer (its slot) + 8 * key_words per tag match (the key it is confirmed against) + the
+ * records (24 * n_seqs) + n_bases / 8 of hit bits written and read (2 * 8 * ceil(n_bases / 64)) + with KMX_MATCH_IDS 4 * n_bases + with
+ * KMX_MATCH_OCC 8 per hit */
+uint64_t  kmx_match_result_algo_bytes(kmx_match_result* r);
+void      kmx_match_result_free(kmx_match_result* r);
 
 /* ------------------------------------------------------------------ count */
 

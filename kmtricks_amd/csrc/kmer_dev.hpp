@@ -172,6 +172,41 @@ __device__ __forceinline__ bool q_tile_kmer(const char* __restrict__ bases, u64 
   return (fi_lo & klo) == 0 && (fi_hi & khi) == 0;
 }
 
+// q_tile_kmer's sibling for a walk that has no minimizer (match.hip): the canonical words alone, from the tile's bases and the 128 behind
+// them, and the strand -- fwd: the read shows the canonical k-mer itself (a palindrome counts as forward).  Of wk only k, klo and khi
+// are read.  Returns whether the k bases are all ACGT.
+template <int KW>
+__device__ __forceinline__ bool q_tile_kmer_strand(const char* __restrict__ bases, u64 n_bases, u64 pos, int lane, const QWalk& wk, u64 (&cw)[KW], bool& fwd)
+{
+  const int k = wk.k;
+  const u64 klo = wk.klo, khi = wk.khi;
+  u8 cc[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) cc[i] = pos + 64u * i < n_bases ? (u8)bases[pos + 64u * i] : (u8)'N';
+  u64 I[3], A[3], B[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) { I[i] = __ballot(!nt_valid(cc[i])); A[i] = __ballot((cc[i] >> 1) & 1); B[i] = __ballot((cc[i] >> 2) & 1); }
+  auto fun = [&](u64 x, u64 y) { return lane ? (x >> lane) | (y << (64 - lane)) : x; };
+  const u64 fi_lo = fun(I[0], I[1]), fi_hi = fun(I[1], I[2]);
+  const u64 a_lo = fun(A[0], A[1]) & klo, a_hi = fun(A[1], A[2]) & khi, b_lo = fun(B[0], B[1]) & klo, b_hi = fun(B[1], B[2]) & khi;
+  u64 ra_lo, ra_hi, rb_lo, rb_hi;
+  q_rev(a_lo, a_hi, k, ra_lo, ra_hi); q_rev(b_lo, b_hi, k, rb_lo, rb_hi);
+  const u64 nb_lo = ~b_lo & klo, nb_hi = ~b_hi & khi;
+  u64 f[KW], r[KW];
+#pragma unroll
+  for (int w = 0; w < KW; w++) {
+    f[w] = spread32(q_bits32(ra_lo, ra_hi, w)) | (spread32(q_bits32(rb_lo, rb_hi, w)) << 1);
+    r[w] = spread32(q_bits32(a_lo, a_hi, w)) | (spread32(q_bits32(nb_lo, nb_hi, w)) << 1);
+  }
+  bool less = false, decided = false;
+#pragma unroll
+  for (int w = KW - 1; w >= 0; w--) if (!decided && f[w] != r[w]) { less = f[w] < r[w]; decided = true; }
+#pragma unroll
+  for (int w = 0; w < KW; w++) cw[w] = less ? f[w] : r[w];
+  fwd = less || !decided;
+  return (fi_lo & klo) == 0 && (fi_hi & khi) == 0;
+}
+
 // the tile's adds: one per partition of the tile to its (partition, chunk) counter, one per query to n_kmers[query]
 __device__ __forceinline__ void q_tile_adds(bool valid, u32 part, u32 q, int lane, u32* __restrict__ hist, u32 n_chunks, u32 c, u32* __restrict__ n_kmers)
 {

@@ -534,6 +534,12 @@ class SeqReader {
   // (kmx query) from here on next() keeps the name of the record it returns: the first word of its header line
   void keep_names() { names_ = true; }
   const std::string& name() const { return name_; }
+  // (kmx match) ... and the whole record: its header line as read (the '>' / '@' included, the line end not) and, for FASTQ, its quality
+  // string (the lines behind the '+' joined).  next_view is not for a reader in this mode
+  void keep_records() { names_ = true; records_ = true; }
+  const std::string& header() const { return header_; }
+  const std::string& quality() const { return qual_; }
+  bool fastq() const { return fastq_; }
   bool next(std::string& seq) {
     seq.clear();
     char c;
@@ -543,6 +549,7 @@ class SeqReader {
     }
     have_hdr_ = false;
     if (names_) name_ = next_name_;
+    if (records_) { header_ = next_header_; fastq_ = hdr_ == '@'; qual_.clear(); }
     if (hdr_ == '>') {
       while (peek(c)) { if (c == '>') { have_hdr_ = true; hdr_ = '>'; header_line(); break; } take_line(seq); }
       return true;
@@ -550,7 +557,8 @@ class SeqReader {
     // FASTQ: sequence lines until '+', then as many quality characters as bases
     while (peek(c)) { if (c == '+') { skip_line(); break; } take_line(seq); }
     size_t q = 0;
-    while (q < seq.size() && peek(c)) q += skip_line();
+    if (records_) while (qual_.size() < seq.size() && peek(c)) take_line(qual_);
+    else while (q < seq.size() && peek(c)) q += skip_line();
     return true;
   }
  private:
@@ -584,6 +592,7 @@ class SeqReader {
   void header_line() {
     if (!names_) { skip_line(); return; }
     next_name_.clear();
+    if (records_) next_header_.clear();
     bool open = true;
     for (;;) {
       if (pos_ == end_ && !fill()) break;
@@ -591,10 +600,12 @@ class SeqReader {
       const char* nl = (const char*)memchr(b, '\n', end_ - pos_);
       const size_t m = nl ? (size_t)(nl - b) : end_ - pos_;
       for (size_t i = 0; i < m && open; i++) { const char c = b[i]; if (c == ' ' || c == '\t' || c == '\r') open = false; else next_name_ += c; }
+      if (records_) next_header_.append(b, m);
       pos_ += m + (nl ? 1 : 0);
       if (nl) break;
     }
     if (!next_name_.empty()) next_name_.erase(0, 1);
+    if (records_ && !next_header_.empty() && next_header_.back() == '\r') next_header_.pop_back();
   }
   // the rest of the current line goes behind `s`, blanks, tabs and carriage returns left out
   void take_line(std::string& s) {
@@ -613,6 +624,7 @@ class SeqReader {
   }
   gzFile gz_ = nullptr; int fd_ = -1; std::string path_; char hdr_ = 0; bool have_hdr_ = false, eof_ = false;
   bool names_ = false; std::string name_, next_name_;
+  bool records_ = false, fastq_ = false; std::string header_, next_header_, qual_;
   std::unique_ptr<char[]> buf_; size_t pos_ = 0, end_ = 0;
 };
 

@@ -158,6 +158,23 @@ assert C.sizeof(KmxGroupsumTask) == 88
 GROUPSUM_SUMS = 1
 
 
+class KmxKsetTask(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("n", C.c_uint64), ("kmer_size", C.c_uint32), ("key_words", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class KmxMatchTask(C.Structure):
+    _fields_ = [("set", C.c_void_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("occ", C.c_void_p), ("reserved2", C.c_uint64)]
+
+
+assert C.sizeof(KmxKsetTask) == 32 and C.sizeof(KmxMatchTask) == 56
+MATCH_IDS, MATCH_OCC = 1, 2
+MATCH_REC = np.dtype([("n_kmers", "<u4"), ("hits", "<u4"), ("fwd", "<u4"), ("covered", "<u4"), ("first", "<u4"), ("last", "<u4")])
+assert MATCH_REC.itemsize == 24
+MATCH_NONE = 0xFFFFFFFF
+
+
 class KmxGramTask(C.Structure):
     _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("weights", C.c_void_p),
@@ -521,6 +538,39 @@ _lib.kmx_groupsum_result_free.argtypes = [_vp]
 GROUPSUM_EXPORTS = ["kmx_groupsum_dev", "kmx_groupsum_host", "kmx_groupsum_result_wait", "kmx_groupsum_result_present_dev", "kmx_groupsum_result_sums_dev",
                     "kmx_groupsum_result_size_dev", "kmx_groupsum_result_copy_present", "kmx_groupsum_result_copy_sums", "kmx_groupsum_result_copy_size",
                     "kmx_groupsum_result_kernel_ms", "kmx_groupsum_result_algo_bytes", "kmx_groupsum_result_free"]
+_lib.kmx_kset_dev.argtypes = [_vp, C.POINTER(KmxKsetTask), C.POINTER(_vp)]
+_lib.kmx_kset_host.argtypes = [_vp, C.POINTER(KmxKsetTask), C.POINTER(_vp)]
+_lib.kmx_kset_wait.argtypes = [_vp]
+for _f in ("kmx_kset_n", "kmx_kset_n_distinct"):
+    getattr(_lib, _f).restype = C.c_uint64
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_kset_kmer_size.restype = C.c_uint32
+_lib.kmx_kset_kmer_size.argtypes = [_vp]
+_lib.kmx_kset_copy_ids.argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_kset_kernel_ms.restype = C.c_double
+_lib.kmx_kset_kernel_ms.argtypes = [_vp]
+_lib.kmx_kset_free.argtypes = [_vp]
+KSET_EXPORTS = ["kmx_kset_dev", "kmx_kset_host", "kmx_kset_wait", "kmx_kset_n", "kmx_kset_n_distinct", "kmx_kset_kmer_size", "kmx_kset_copy_ids",
+                "kmx_kset_kernel_ms", "kmx_kset_free"]
+_lib.kmx_match_dev.argtypes = [_vp, C.POINTER(KmxMatchTask), C.POINTER(_vp)]
+_lib.kmx_match_host.argtypes = [_vp, C.POINTER(KmxMatchTask), C.POINTER(_vp)]
+_lib.kmx_match_result_wait.argtypes = [_vp]
+for _f in ("n_seqs", "n_bases", "total_kmers", "total_hits", "algo_bytes"):
+    getattr(_lib, "kmx_match_result_" + _f).restype = C.c_uint64
+    getattr(_lib, "kmx_match_result_" + _f).argtypes = [_vp]
+MATCH_COPIES = ["recs", "ids", "occ"]
+for _f in MATCH_COPIES:
+    getattr(_lib, "kmx_match_result_copy_" + _f).argtypes = [_vp, _vp, C.c_uint64]
+_lib.kmx_match_result_occ_dev.restype = _vp
+_lib.kmx_match_result_occ_dev.argtypes = [_vp]
+_lib.kmx_match_result_kernel_ms.restype = C.c_double
+_lib.kmx_match_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_match_result_kernel_parts_ms.argtypes = [_vp] + [C.POINTER(C.c_double)] * 2
+_lib.kmx_match_result_free.argtypes = [_vp]
+MATCH_EXPORTS = (["kmx_match_dev", "kmx_match_host", "kmx_match_result_wait", "kmx_match_result_n_seqs", "kmx_match_result_n_bases",
+                  "kmx_match_result_occ_dev", "kmx_match_result_total_kmers", "kmx_match_result_total_hits", "kmx_match_result_kernel_ms",
+                  "kmx_match_result_kernel_parts_ms", "kmx_match_result_algo_bytes", "kmx_match_result_free"] +
+                 ["kmx_match_result_copy_" + _f for _f in MATCH_COPIES])
 _lib.kmx_gram_dev.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
 _lib.kmx_gram_host.argtypes = [_vp, C.POINTER(KmxGramTask), C.POINTER(_vp)]
 _lib.kmx_gram_result_wait.argtypes = [_vp]
@@ -1364,6 +1414,52 @@ class Context:
         self._check(_lib.kmx_unitigs_dev(self._h, C.byref(t), C.byref(res)), "kmx_unitigs_dev")
         return self._finish(UnitigsResult(self, res, n, kmer_size), keep)
 
+    def kset(self, keys_words, k):
+        """kmx_kset_host: keys_words uint64[n, ceil(k / 32)] (low word first), canonical k-mers in any order, duplicates allowed.
+        -> Kset (the set stays in HBM for match(); .free() it)"""
+        kw = key_words_of(k)
+        a = np.ascontiguousarray(keys_words, dtype=np.uint64).reshape(-1, kw)
+        t = KmxKsetTask(a.ctypes.data if len(a) else None, len(a), k, kw, 0, 0)
+        h = _vp()
+        self._check(_lib.kmx_kset_host(self._h, C.byref(t), C.byref(h)), "kmx_kset_host")
+        s = Kset(self, h)
+        try:
+            s.wait()      # (the host buffer above may go once the build has run)
+        except KmxError:      # a data error found on the device: the set is of no use
+            s.free()
+            raise
+        return s
+
+    def kset_dev(self, keys_dev, n, k):
+        """kmx_kset_dev: keys_dev a device pointer to n keys.  -> Kset (a data error shows at .wait() and at every use)"""
+        t = KmxKsetTask(keys_dev, n, k, key_words_of(k), 0, 0)
+        h = _vp()
+        self._check(_lib.kmx_kset_dev(self._h, C.byref(t), C.byref(h)), "kmx_kset_dev")
+        return Kset(self, h)
+
+    def match(self, kset, reads, ids=False, occ=False, occ_dev=None, keep=False):
+        """kmx_match_host: reads a list of sequences (str / bytes) or pack_reads() output, against a Kset.  ids: the id per base of the
+        call; occ: the occurrences per key -- occ_dev None (the result owns a zeroed table) or a device pointer to n uint64 the call
+        adds to.  -> MatchOutput (numpy copies), or with keep the MatchResult itself (the tables left in HBM; .free() it)"""
+        blob, offs = reads if isinstance(reads, tuple) else self.pack_reads(reads)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        bb = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, np.uint8)
+        flags = (MATCH_IDS if ids else 0) | (MATCH_OCC if occ or occ_dev is not None else 0)
+        t = KmxMatchTask(kset._h, bb.ctypes.data, offs.ctypes.data, len(offs) - 1, flags, 0, occ_dev, 0)
+        res = _vp()
+        self._check(_lib.kmx_match_host(self._h, C.byref(t), C.byref(res)), "kmx_match_host")
+        r = MatchResult(self, res, kset.n, flags)
+        r.wait()      # (the host buffers above may go once the call has run)
+        return self._finish(r, keep)
+
+    def match_dev(self, kset, bases_dev, offsets_dev, n_seqs, ids=False, occ=False, occ_dev=None, keep=False):
+        """kmx_match_dev: device pointers to the bases and the uint64 offsets [n_seqs + 1].  -> as match"""
+        flags = (MATCH_IDS if ids else 0) | (MATCH_OCC if occ or occ_dev is not None else 0)
+        t = KmxMatchTask(kset._h, bases_dev, offsets_dev, n_seqs, flags, 0, occ_dev, 0)
+        res = _vp()
+        self._check(_lib.kmx_match_dev(self._h, C.byref(t), C.byref(res)), "kmx_match_dev")
+        return self._finish(MatchResult(self, res, kset.n, flags), keep)
+
     @staticmethod
     def _groupsum_task(rows, n_rows, n_cols, key_words, mode, groups, g0, n_groups, cols, min_abund, sums, present_dev, sums_dev, size_dev):
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
@@ -1803,6 +1899,86 @@ class UnitigsResult(_Result):
         flat = self._copy("seqs", np.zeros(self.seq_bytes(), np.uint8)).tobytes()
         seqs = [flat[int(seq_off[u]):int(seq_off[u + 1])] for u in range(U)]
         return UnitigsOutput(U, unitig, pos, ori, start, length, circ, seq_off, seqs, self.kernel_ms(), self.algo_bytes())
+
+
+class Kset:
+    """a set of k-mers resident on the device (kmx_kset_*): n keys as given, n_distinct ids; ids() uint32[n]: for every input index the
+    least index of its key; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, ctx, h):
+        self._ctx, self._h = ctx, h
+        self._n = None
+
+    def wait(self):
+        self._ctx._check(_lib.kmx_kset_wait(self._h), "kmx_kset_wait")
+
+    @property
+    def n(self):
+        if self._n is None:
+            self.wait()
+            self._n = _lib.kmx_kset_n(self._h)
+        return self._n
+
+    @property
+    def n_distinct(self):
+        self.wait()
+        return _lib.kmx_kset_n_distinct(self._h)
+
+    @property
+    def kmer_size(self):
+        self.wait()
+        return _lib.kmx_kset_kmer_size(self._h)
+
+    @property
+    def kernel_ms(self):
+        return _lib.kmx_kset_kernel_ms(self._h)
+
+    def ids(self):
+        a = np.zeros(self.n, np.uint32)
+        self._ctx._check(_lib.kmx_kset_copy_ids(self._h, a.ctypes.data, a.size), "kmx_kset_copy_ids")
+        return a
+
+    def free(self):
+        if self._h:
+            _lib.kmx_kset_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MatchOutput:
+    """recs: a structured array (MATCH_REC: n_kmers, hits, fwd, covered, first, last), one record a read; ids uint32[n_bases] or None; occ
+    uint64[n] (the table as it stands) or None; total_kmers, total_hits; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, recs, ids, occ, total_kmers, total_hits, kernel_ms, algo_bytes):
+        self.recs, self.ids, self.occ, self.total_kmers, self.total_hits = recs, ids, occ, total_kmers, total_hits
+        self.kernel_ms, self.algo_bytes = kernel_ms, algo_bytes
+
+
+class MatchResult(_Result):
+    _prefix = "match"
+
+    def __init__(self, ctx, h, n_keys, flags):
+        super().__init__(ctx, h)
+        self._n, self._flags = n_keys, flags
+
+    def occ_dev(self):
+        return self._call("occ_dev")
+
+    def kernel_parts_ms(self):
+        """(the clears + k_mt_probe, k_mt_cover + k_mt_last) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(2)
+
+    def output(self):
+        self.wait()
+        recs = self._copy("recs", np.zeros(self._call("n_seqs"), MATCH_REC))
+        ids = self._copy("ids", np.zeros(self._call("n_bases"), np.uint32)) if self._flags & MATCH_IDS else None
+        occ = self._copy("occ", np.zeros(self._n, np.uint64)) if self._flags & MATCH_OCC else None
+        return MatchOutput(recs, ids, occ, self._call("total_kmers"), self._call("total_hits"), self.kernel_ms(), self.algo_bytes())
 
 
 class GroupsumOutput:
