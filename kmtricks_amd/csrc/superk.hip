@@ -222,7 +222,7 @@ void k_superk_wave(const char* __restrict__ bases, const u64* __restrict__ offse
             else { const u32 dd = (u32)(p0 - ps); bits = (hist >> (64u - dd)) | (Wb << dd); }
             S.sk_rec[di] = make_ulonglong2((bits & ((1ULL << n) - 1ULL)) | ((u64)(n & 15u) << 60), (u64)(u32)(b0 + ps) | ((u64)mini << 32) | ((u64)(n >> 4) << 62));
           }
-          hist = (hist >> own) | (Wb << (64u - own));      // (own = 33 .. 63)
+          hist = (hist >> own) | (Wb << (64u - own));      // (own = 32 .. 63: 32 at nbm = 32, k = 41 with m = 10)
         } else {
         int w_l = __shfl_up(w, 1); if (lane == 0) w_l = pw;
         const bool T = valid && (start || w != w_l);                       // first k-mer of a run of one strand
