@@ -52,6 +52,8 @@
  *                               built for membership at one look-up a base
  *   kmx_match_dev / _host       no counterpart either (kmdiff's map-back, the read fetch of a k-mer GWAS, back_to_sequences): per read the
  *                               k-mers it shares with a kset, their strand, the bases they cover, first and last hit; per k-mer its occurrences
+ *   kmx_spectra_dev / _host     no counterpart either (KAT `hist` / `comp`, Merqury's spectra-cn): per sample the rows by count, per pair
+ *                               of samples the rows by the two counts -- the tables k-mer completeness and consensus quality follow from
  *   kmx_superk_partition       replaces KmFillPartitions / Sequence2SuperKmer / SuperKmer::save
  *                               (include/kmtricks/gatb/fill_partitions.hpp:59-105, gatb kmer/impl/Sequence2SuperKmer.hpp:80-158,
  *                                gatb kmer/impl/Model.hpp:1086-1139, 1388-1433), SuperKTask::exec (task.hpp:255-320)
@@ -1479,6 +1481,90 @@ int       kmx_match_result_kernel_parts_ms(kmx_match_result* r, double* probe_ms
  * KMX_MATCH_OCC 8 per hit */
 uint64_t  kmx_match_result_algo_bytes(kmx_match_result* r);
 void      kmx_match_result_free(kmx_match_result* r);
+
+/* ---------------------------------------------------------------- spectra */
+
+/* The abundance spectrum of every listed sample and the joint spectrum of pairs of samples (what KAT `hist` / `comp` and Merqury's
+ * spectra-cn tabulate; no counterpart in the kmtricks tree): how many rows a sample holds with a count of 0, 1, 2, ..., and how many rows
+ * hold a count of a in sample x and of b in sample y.  dist's sum of minima and colsums' totals are summaries of these tables.
+ * INPUT, as for kmx_pan_*: a run of n_rows rows of ONE partition's matrix body, n_cols = N samples, KMX_MODE_COUNT or KMX_MODE_PA,
+ * `rows` at any address.  The padding bits of a PA row never reach a result.  Keys are never read.
+ * PARAMETERS:
+ *   flags      KMX_SPECTRA_HIST | KMX_SPECTRA_JOINT, at least one
+ *   cols       (HIST) select's convention: a HOST array of M = n_use distinct input column indices, each < N, in any order; NULL is the
+ *              identity and requires M = N.  Ordinal j is input column cols[j].
+ *   cap1       (HIST) C1 in 1 ... 65535: counts of C1 and more share the last bin
+ *   pairs      (JOINT) a HOST array of 2 * P input column indices (x_0, y_0, x_1, y_1, ...), each < N; x = y and repeated pairs are allowed
+ *   cap2       (JOINT) C2 in 1 ... 255
+ * PER ROW, with v_c the count of input column c (COUNT) or its bit (PA):
+ *   HIST   for every j < M, v = v_cols[j]:  hist[j][min(v, C1)] += 1, and if v >= C1 also hist[j][C1 + 1] += v
+ *   JOINT  for every p < P:                 joint[p][min(v_x, C2)][min(v_y, C2)] += 1
+ * OUTPUTS: u64 DEVICE tables.  The call ADDS into a table of the caller's, or into a zeroed one the result owns when the pointer is
+ * NULL.  Partitions and runs of rows accumulate in any order; n_rows = 0 adds nothing.
+ *   hist[M][C1 + 2]            [j][b] for b <= C1 the rows by (capped) count; [j][C1 + 1] the volume of the last bin, so that the sum
+ *                              over b < C1 of b * hist[j][b], plus hist[j][C1 + 1], is the column's exact total
+ *   joint[P][C2 + 1][C2 + 1]   [p][a][b] the rows with (capped) counts a in x_p and b in y_p
+ * EXAMPLE.  N = 3, cols NULL, C1 = 2, pairs (0,1), (2,2), C2 = 2, four rows:
+ *   (1,0,2)   (0,0,5)   (3,3,3)   (0,0,0)
+ *   hist[0] = (2,1,1, 3)   hist[1] = (3,0,1, 3)   hist[2] = (1,0,3, 10)
+ *   joint[0]: [0][0] = 2, [1][0] = 1, [2][2] = 1;  joint[1]: [0][0] = 1, [2][2] = 3; every other cell is zero
+ * With cols = (2) hist is the one line (1,0,3, 10).
+ * IDENTITIES of one call's increments: the sum of hist[j][0 ... C1] is n_rows; the total above is colsums' sum of the column; the sum of
+ * hist[j][1 ... C1] is the rows that hold the column; the sum of joint[p] is n_rows, its row sums are x_p's histogram folded at C2 and
+ * its column sums y_p's; joint of (x, x) is diagonal; while no count reaches C2 the sum of min(a, b) * joint[p][a][b] is mins[x][y] of
+ * kmx_dist_*.
+ * LIMITS, each refused before any GPU work.  KMX_E_INVAL: n_cols = 0; no flag or unknown flag bits; key_words 0 or > 4; a mode other than
+ * COUNT / PA; HIST with n_use = 0, n_use > n_cols, a column index >= N or listed twice, cols = NULL with M != N, cap1 outside 1 ... 65535;
+ * without HIST n_use != 0, cols != NULL or hist != NULL; JOINT with n_pairs = 0, pairs NULL, a pair index >= N, cap2 outside 1 ... 255;
+ * without JOINT n_pairs != 0, pairs != NULL or joint != NULL.  KMX_E_UNSUPPORTED: KMX_MODE_BF, KMX_MODE_BFC, KMX_MODE_BFT (a Bloom row
+ * is a hash bit: it has no count); n_rows > 2^32 - 256; a row of 4 GiB or more; a table of 8 GiB or more (M * (C1 + 2) or
+ * P * (C2 + 1)^2 entries of 2^30 and more).
+ * SCRATCH from the context's pool, per call: 4 bytes per input column (rounded up to 8 columns) with HIST, 8 bytes a pair with JOINT;
+ * for _host the uploaded rows.  The tables the result owns live until the result is freed. */
+#define KMX_SPECTRA_HIST  1u
+#define KMX_SPECTRA_JOINT 2u
+
+typedef struct {
+  uint32_t        key_words;     /* 1 ... 4 */
+  uint32_t        mode;          /* KMX_MODE_COUNT | KMX_MODE_PA */
+  uint32_t        n_cols;        /* N: samples of the matrix */
+  uint32_t        n_use;         /* M: samples of the list (HIST; 0 without) */
+  const void*     rows;
+  uint64_t        n_rows;
+  const uint32_t* cols;          /* HOST: M input column indices (copied by the call), or NULL: the identity */
+  const uint32_t* pairs;         /* HOST: 2 * P input column indices (copied by the call) */
+  uint32_t        n_pairs;       /* P */
+  uint32_t        cap1;          /* C1 (HIST) */
+  uint32_t        cap2;          /* C2 (JOINT) */
+  uint32_t        flags;         /* KMX_SPECTRA_HIST | KMX_SPECTRA_JOINT */
+  uint64_t*       hist;          /* NULL, or (HIST) a device table of M * (C1 + 2) u64 to accumulate into */
+  uint64_t*       joint;         /* NULL, or (JOINT) a device table of P * (C2 + 1)^2 u64 to accumulate into */
+} kmx_spectra_task;              /* 80 bytes */
+
+typedef struct kmx_spectra_result kmx_spectra_result;
+
+/* _dev and _host as for kmx_pan_*: rows a DEVICE pointer, the kernels queued on the context's stream and the call back without waiting;
+ * or a HOST pointer, uploaded on a stream of its own, the buffer free for reuse once _result_wait has returned.  cols and pairs are host
+ * arrays in both; hist and joint are device tables in both and stay the caller's. */
+int kmx_spectra_dev(kmx_ctx* ctx, const kmx_spectra_task* task, kmx_spectra_result** out);
+int kmx_spectra_host(kmx_ctx* ctx, const kmx_spectra_task* task, kmx_spectra_result** out);
+int       kmx_spectra_result_wait(kmx_spectra_result* r);
+/* (the accessors below wait for the call themselves) */
+uint64_t* kmx_spectra_result_hist_dev(kmx_spectra_result* r);       /* the table as it stands: the result's own or the task's; NULL without HIST */
+uint64_t* kmx_spectra_result_joint_dev(kmx_spectra_result* r);      /* NULL without JOINT */
+int       kmx_spectra_result_copy_hist(kmx_spectra_result* r, uint64_t* host_dst, uint64_t dst_entries);    /* M * (C1 + 2); KMX_E_INVAL without HIST */
+int       kmx_spectra_result_copy_joint(kmx_spectra_result* r, uint64_t* host_dst, uint64_t dst_entries);   /* P * (C2 + 1)^2; KMX_E_INVAL without JOINT */
+/* duration in ms of the call's kernels, the clearing of the tables the result owns included (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+double    kmx_spectra_result_kernel_ms(kmx_spectra_result* r);
+/* the same interval in its parts: clearing + the HIST kernel, the JOINT kernel (-1 for the part that was not asked for); any pointer may be NULL */
+int       kmx_spectra_result_kernel_parts_ms(kmx_spectra_result* r, double* hist_ms, double* joint_ms);
+/* algorithmic bytes.  HIST: the body read once (n_rows * row bytes) + the table, 8 * M * (C1 + 2).  JOINT: the pairs go in groups of G
+ * consecutive pairs (G = min(16, floor(12288 / (C2 + 1)^2)) while C2 <= 109, else 16); U_g is the number of distinct columns of group g
+ * and n_groups = ceil(P / G).  When 256 * max U_g <= row bytes the columns are gathered: n_rows * u * (the sum of U_g) with u = 4
+ * (COUNT) or 1 (PA); otherwise the rows are streamed once a group: n_groups * n_rows * row bytes.  To that the table, 8 * P * (C2 + 1)^2.
+ * With both flags the sum of the two. */
+uint64_t  kmx_spectra_result_algo_bytes(kmx_spectra_result* r);
+void      kmx_spectra_result_free(kmx_spectra_result* r);
 
 /* ------------------------------------------------------------------ count */
 

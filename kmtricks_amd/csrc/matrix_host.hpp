@@ -1,6 +1,6 @@
-// matrix_host.hpp -- the host path the eight matrix-tool calls share (kmx_select_*, kmx_colsums_*, kmx_diff_*, kmx_dist_*, kmx_pan_*,
-// kmx_colors_*, kmx_gram_*, kmx_assoc_*): one matrix body goes in, tables, kept rows or records come out.  A family (select.hip, diff.hip,
-// dist.hip, pan.hip, colors.hip, gram.hip, assoc.hip) keeps what is its own: its extra limits, its blocks and their sizes, its launches,
+// matrix_host.hpp -- the host path the nine matrix-tool calls share (kmx_select_*, kmx_colsums_*, kmx_diff_*, kmx_dist_*, kmx_pan_*,
+// kmx_colors_*, kmx_gram_*, kmx_assoc_*, kmx_spectra_*): one matrix body goes in, tables, kept rows or records come out.  A family (select.hip, diff.hip,
+// dist.hip, pan.hip, colors.hip, gram.hip, assoc.hip, spectra.hip) keeps what is its own: its extra limits, its blocks and their sizes, its launches,
 // its formula for algo_bytes and its accessors.  Everything else is here, once.
 #pragma once
 #include "kmx_host.hpp"
@@ -11,7 +11,7 @@
 #pragma GCC visibility push(hidden)      // internal to libkmx: none of this joins the library's dynamic symbols
 namespace kmx {
 
-// what the eight result types have in common; kmx_select_result and its siblings derive from it
+// what the nine result types have in common; kmx_select_result and its siblings derive from it
 struct MatResult {
   kmx_ctx* ctx = nullptr;
   const char* name = "";                // "kmx_select", ...: leads the message of wait

@@ -1339,6 +1339,7 @@ int kmx_pca_main(int argc, char** argv);        // kmx_pca.cpp: pca
 int kmx_assoc_main(int argc, char** argv);      // kmx_assoc.cpp: assoc
 int kmx_unitigs_main(int argc, char** argv);    // kmx_unitigs.cpp: unitigs
 int kmx_match_main(int argc, char** argv);      // kmx_match.cpp: match
+int kmx_spectra_main(int argc, char** argv);    // kmx_spectra.cpp: spectra
 
 int main(int argc, char** argv)
 {
@@ -1353,6 +1354,7 @@ int main(int argc, char** argv)
   if (argc >= 2 && std::string(argv[1]) == "assoc") { try { return kmx_assoc_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "unitigs") { try { return kmx_unitigs_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && std::string(argv[1]) == "match") { try { return kmx_match_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
+  if (argc >= 2 && std::string(argv[1]) == "spectra") { try { return kmx_spectra_main(argc, argv); } catch (const std::exception& e) { die(e.what()); } }
   if (argc >= 2 && (std::string(argv[1]) == "dump" || std::string(argv[1]) == "aggregate" || std::string(argv[1]) == "combine")) return kmx_tools_main(argc, argv);
   try { return run(argc, argv); }
   catch (const std::exception& e) { die(e.what()); }

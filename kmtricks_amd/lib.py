@@ -131,6 +131,17 @@ assert C.sizeof(KmxPanTask) == 64
 PAN_SHARED = 1
 
 
+class KmxSpectraTask(C.Structure):
+    _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
+                ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("pairs", C.c_void_p),
+                ("n_pairs", C.c_uint32), ("cap1", C.c_uint32), ("cap2", C.c_uint32), ("flags", C.c_uint32),
+                ("hist", C.c_void_p), ("joint", C.c_void_p)]
+
+
+assert C.sizeof(KmxSpectraTask) == 80
+SPECTRA_HIST, SPECTRA_JOINT = 1, 2
+
+
 class KmxColorsTask(C.Structure):
     _fields_ = [("key_words", C.c_uint32), ("mode", C.c_uint32), ("n_cols", C.c_uint32), ("n_use", C.c_uint32),
                 ("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("min_abund", C.c_uint32),
@@ -585,6 +596,23 @@ _lib.kmx_gram_result_kernel_parts_ms.argtypes = [_vp] + [C.POINTER(C.c_double)] 
 _lib.kmx_gram_result_free.argtypes = [_vp]
 GRAM_EXPORTS = ["kmx_gram_dev", "kmx_gram_host", "kmx_gram_result_wait", "kmx_gram_result_table_dev", "kmx_gram_result_copy_table",
                 "kmx_gram_result_kernel_ms", "kmx_gram_result_kernel_parts_ms", "kmx_gram_result_algo_bytes", "kmx_gram_result_free"]
+_lib.kmx_spectra_dev.argtypes = [_vp, C.POINTER(KmxSpectraTask), C.POINTER(_vp)]
+_lib.kmx_spectra_host.argtypes = [_vp, C.POINTER(KmxSpectraTask), C.POINTER(_vp)]
+_lib.kmx_spectra_result_wait.argtypes = [_vp]
+_lib.kmx_spectra_result_algo_bytes.restype = C.c_uint64
+_lib.kmx_spectra_result_algo_bytes.argtypes = [_vp]
+for _f in ("kmx_spectra_result_copy_hist", "kmx_spectra_result_copy_joint"):
+    getattr(_lib, _f).argtypes = [_vp, _vp, C.c_uint64]
+for _f in ("kmx_spectra_result_hist_dev", "kmx_spectra_result_joint_dev"):
+    getattr(_lib, _f).restype = _vp
+    getattr(_lib, _f).argtypes = [_vp]
+_lib.kmx_spectra_result_kernel_ms.restype = C.c_double
+_lib.kmx_spectra_result_kernel_ms.argtypes = [_vp]
+_lib.kmx_spectra_result_kernel_parts_ms.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+_lib.kmx_spectra_result_free.argtypes = [_vp]
+SPECTRA_EXPORTS = ["kmx_spectra_dev", "kmx_spectra_host", "kmx_spectra_result_wait", "kmx_spectra_result_hist_dev", "kmx_spectra_result_joint_dev",
+                   "kmx_spectra_result_copy_hist", "kmx_spectra_result_copy_joint", "kmx_spectra_result_kernel_ms", "kmx_spectra_result_kernel_parts_ms",
+                   "kmx_spectra_result_algo_bytes", "kmx_spectra_result_free"]
 PAN_EXPORTS = ["kmx_pan_dev", "kmx_pan_host", "kmx_pan_result_wait", "kmx_pan_result_spectrum_dev", "kmx_pan_result_shared_dev",
                "kmx_pan_result_copy_spectrum", "kmx_pan_result_copy_shared", "kmx_pan_result_kernel_ms", "kmx_pan_result_kernel_parts_ms",
                "kmx_pan_result_algo_bytes", "kmx_pan_result_free"]
@@ -1366,6 +1394,43 @@ class Context:
         return self._finish(PanResult(self, res, n_cols, n_use, want), keep)
 
     @staticmethod
+    def _spectra_task(rows, n_rows, n_cols, key_words, mode, cols, cap, pairs, joint_cap, hist_dev, joint_dev, hist):
+        want_h = bool(hist) or hist_dev is not None
+        want_j = pairs is not None or joint_dev is not None
+        c = None if cols is None or not want_h else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        n_use = 0 if not want_h else n_cols if c is None else len(c)
+        p = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        n_pairs = 0 if p is None else len(p) // 2
+        t = KmxSpectraTask(key_words, mode, n_cols, n_use, rows, n_rows, c.ctypes.data if c is not None and len(c) else None,
+                           p.ctypes.data if p is not None and len(p) else None, n_pairs, cap if want_h else 0, joint_cap if want_j else 0,
+                           (SPECTRA_HIST if want_h else 0) | (SPECTRA_JOINT if want_j else 0), hist_dev, joint_dev)
+        shape = (n_use, cap, n_pairs, joint_cap, want_h, want_j)
+        return t, (c, p), shape      # (the arrays are kept alive by the caller until the call has copied them)
+
+    def spectra(self, body, n_rows, n_cols, key_words, mode, cols=None, cap=255, pairs=None, joint_cap=63, hist_dev=None, joint_dev=None,
+                keep=False, hist=True):
+        """kmx_spectra_host: body as for pan.  The abundance spectra (unless hist is False) of the input columns cols (None: all, as they
+        stand), counts of cap and more in the last bin; the joint spectra of pairs, a sequence of (x, y) input columns, counts capped at
+        joint_cap (None: no joint spectra).  hist_dev / joint_dev: None (the result owns a zeroed table) or a device pointer to a
+        uint64 table [M, cap + 2] / [P, joint_cap + 1, joint_cap + 1] the call adds to.
+        -> SpectraOutput (numpy copies), or with keep the SpectraResult itself (the tables left in HBM; .free() it)"""
+        a, n_rows = self._whole_rows(body, n_rows, n_cols, key_words, mode)
+        t, hold, shape = self._spectra_task(a.ctypes.data if len(a) else None, n_rows, n_cols, key_words, mode, cols, cap, pairs, joint_cap, hist_dev, joint_dev, hist)
+        res = _vp()
+        self._check(_lib.kmx_spectra_host(self._h, C.byref(t), C.byref(res)), "kmx_spectra_host")
+        r = SpectraResult(self, res, *shape)
+        r.wait()      # (the host buffer above may go once the call has run)
+        return self._finish(r, keep)
+
+    def spectra_dev(self, rows_dev, n_rows, n_cols, key_words, mode, cols=None, cap=255, pairs=None, joint_cap=63, hist_dev=None, joint_dev=None,
+                    keep=False, hist=True):
+        """kmx_spectra_dev: rows_dev a device pointer to n_rows rows (cols and pairs stay host arrays).  -> as spectra"""
+        t, hold, shape = self._spectra_task(rows_dev, n_rows, n_cols, key_words, mode, cols, cap, pairs, joint_cap, hist_dev, joint_dev, hist)
+        res = _vp()
+        self._check(_lib.kmx_spectra_dev(self._h, C.byref(t), C.byref(res)), "kmx_spectra_dev")
+        return self._finish(SpectraResult(self, res, *shape), keep)
+
+    @staticmethod
     def _colors_task(rows, n_rows, n_cols, key_words, mode, cols, min_abund):
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
         n_use = n_cols if c is None else len(c)
@@ -1800,6 +1865,38 @@ class PanResult(_Result):
         spectrum = self._copy("spectrum", np.zeros((3, self._m + 1), np.uint64))
         shared = self._copy("shared", np.zeros((self._m + 1, self._n), np.uint64)) if self._shared else None
         return PanOutput(spectrum, shared, self.kernel_ms(), self.algo_bytes())
+
+
+class SpectraOutput:
+    """hist uint64[M, cap + 2] (None unless asked for): per listed sample the rows by count, counts of cap and more in bin cap, the
+    volume of that bin last; joint uint64[P, joint_cap + 1, joint_cap + 1] (None unless asked for): per pair the rows by the two capped
+    counts -- the tables the call added to, when they were given; kernel_ms < 0 without set_profiling"""
+
+    def __init__(self, hist, joint, kernel_ms, algo_bytes):
+        self.hist, self.joint, self.kernel_ms, self.algo_bytes = hist, joint, kernel_ms, algo_bytes
+
+class SpectraResult(_Result):
+    _prefix = "spectra"
+
+    def __init__(self, ctx, h, n_use, cap, n_pairs, joint_cap, has_hist, has_joint):
+        super().__init__(ctx, h)
+        self._m, self._c1, self._p, self._c2, self._hist, self._joint = n_use, cap, n_pairs, joint_cap, has_hist, has_joint
+
+    def hist_dev(self):
+        return self._call("hist_dev")
+
+    def joint_dev(self):
+        return self._call("joint_dev")
+
+    def kernel_parts_ms(self):
+        """(clearing + the HIST kernel, the JOINT kernel) in ms; -1 where unavailable"""
+        return self._kernel_parts_ms(2)
+
+    def output(self):
+        self.wait()
+        hist = self._copy("hist", np.zeros((self._m, self._c1 + 2), np.uint64)) if self._hist else None
+        joint = self._copy("joint", np.zeros((self._p, self._c2 + 1, self._c2 + 1), np.uint64)) if self._joint else None
+        return SpectraOutput(hist, joint, self.kernel_ms(), self.algo_bytes())
 
 
 class GramOutput:
