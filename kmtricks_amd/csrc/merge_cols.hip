@@ -112,6 +112,7 @@ __device__ __forceinline__ CKey cl_key(const CRec& r) { return (u64)r.v.x | ((u6
 __device__ __forceinline__ u32 cl_cnt(const CRec& r) { return r.v.z; }
 __device__ __forceinline__ CRec cl_none() { CRec r; r.v.x = ~0u; r.v.y = ~0u; r.v.z = 0; return r; }
 __device__ __forceinline__ CRec cl_load(gu32* p) { CRec r; r.v = *(gu32x3*)p; return r; }
+__device__ __forceinline__ CRec cl_pick(bool p, const CRec& a, const CRec& b) { CRec r; r.v.x = p ? a.v.x : b.v.x; r.v.y = p ? a.v.y : b.v.y; r.v.z = p ? a.v.z : b.v.z; return r; }      // (selects of registers, a dword at a time)
 __device__ __forceinline__ bool ent_hit(const ClEnt& e, CKey k) { return (((u64)e.khi << 32) | e.klo) == k && e.idx != 0; }      // (one 64-bit compare)
 __device__ __forceinline__ void ent_set(ClEnt& e, CKey k) { e.klo = (u32)k; e.khi = (u32)(k >> 32); }
 __device__ __forceinline__ ClEnt ent_load(const ClEnt* tab, u32 h) { const uint4 v = reinterpret_cast<const uint4*>(tab)[h]; ClEnt e; e.klo = v.x; e.khi = v.y; e.idx = v.z; e.pad = v.w; return e; }      // one 16-byte LDS read
@@ -132,6 +133,12 @@ __device__ __forceinline__ CKey cl_key(const CRec& r) { CKey k; k.lo = (u64)r.k.
 __device__ __forceinline__ u32 cl_cnt(const CRec& r) { return r.c; }
 __device__ __forceinline__ CRec cl_none() { CRec r; r.k.x = ~0u; r.k.y = ~0u; r.k.z = ~0u; r.k.w = ~0u; r.c = 0; return r; }
 __device__ __forceinline__ CRec cl_load(gu32* p) { CRec r; r.k = *(gu32x4*)p; r.c = p[4]; return r; }
+__device__ __forceinline__ CRec cl_pick(bool p, const CRec& a, const CRec& b)
+{ // (the counts as values of their own first: a select between two loads of the window's count fields became ONE load at a selected
+  //  address -- and the whole window a copy in scratch memory)
+  u32 ca = a.c, cb = b.c; asm volatile("" : "+v"(ca), "+v"(cb));
+  CRec r; r.k.x = p ? a.k.x : b.k.x; r.k.y = p ? a.k.y : b.k.y; r.k.z = p ? a.k.z : b.k.z; r.k.w = p ? a.k.w : b.k.w; r.c = p ? ca : cb; return r;
+}
 __device__ __forceinline__ bool ent_hit(const ClEnt& e, CKey k) { return e.lo == k.lo && e.hi == k.hi && e.idx != 0; }
 __device__ __forceinline__ void ent_set(ClEnt& e, CKey k) { e.lo = k.lo; e.hi = k.hi; }
 __device__ __forceinline__ ClEnt ent_load(const ClEnt* tab, u32 h)
@@ -151,14 +158,16 @@ __device__ __forceinline__ void cl_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // Keys of real minimizer partitions are structured (the row keys of a tile share their leading nucleotides, neighbours in
 // the genome are shifted copies of each other): for a tile in a thousand none of the cheap hashes is collision free.  Those
 // tiles use a second family -- a 64-bit multiplicative hash of the whole key (bit 31 of the hash word set; a uniform branch).
-__device__ __forceinline__ u32 cl_thash(CKey key, u32 hf)
+__device__ __forceinline__ u32 cl_thash_wide(CKey key, u32 hf)      // the second family (bit 31 of the hash word)
 {
   const u64 k = ck_fold(key);
-  if (hf & 0x80000000u) {
-    const u64 m = 0x9E3779B97F4A7C15ULL + 2ULL * (u64)(hf & 0xFFFFu) * 0xBF58476D1CE4E5B9ULL;      // odd
-    return (u32)((k * m) >> (CL_PT == 2048 ? 53 : 52));      // the product's TOP bits: every key bit counts (a k-mer and its variant with one
-                                                             // substitution near the front differ in one high bit and sit in the same tile)
-  }
+  const u64 m = 0x9E3779B97F4A7C15ULL + 2ULL * (u64)(hf & 0xFFFFu) * 0xBF58476D1CE4E5B9ULL;      // odd
+  return (u32)((k * m) >> (CL_PT == 2048 ? 53 : 52));      // the product's TOP bits: every key bit counts (a k-mer and its variant with one
+                                                           // substitution near the front differ in one high bit and sit in the same tile)
+}
+__device__ __forceinline__ u32 cl_thash_cheap(CKey key, u32 hf)
+{
+  const u64 k = ck_fold(key);
 #if KMX_CL_KW == 1
   const u32 x = ((u32)k ^ (u32)(k >> (hf >> 24))) & 0xFFFFFFu;
 #else
@@ -170,6 +179,10 @@ __device__ __forceinline__ u32 cl_thash(CKey key, u32 hf)
   const u32 x = (f ^ (f >> 8)) & 0xFFFFFFu;
 #endif
   return ((u32)__umul24(x, hf) >> CL_PTSHIFT) & (u32)(CL_PT - 1);      // (__umul24 takes the low 24 bits of hf, and returns int)
+}
+__device__ __forceinline__ u32 cl_thash(CKey key, u32 hf)
+{
+  return (hf & 0x80000000u) ? cl_thash_wide(key, hf) : cl_thash_cheap(key, hf);
 }
 __device__ __forceinline__ u32 cl_mult(u32 seed)
 {
@@ -567,13 +580,17 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
     // CL_G adjacent lanes per list; circular window: lane r, slot u holds the record whose index is == r + CL_G * u
     // (mod CL_W) inside [cur, cur + CL_W)
     const u32 lg = (u32)tid / CL_G, r = (u32)tid & (CL_G - 1);
+    const u32 lgm = lg - (MODE == 0 && !NAR ? iw : nbs);      // (a deposit's place in the image: (row + 1) * pitch + lgm)
     const bool on = lg < nbl;
     const u32 li = col0 + (on ? lg : 0u);
     u32 cur = on ? T.bounds[(u64)range * N + li] : 0u;
     const u32 end = on ? T.bounds[(u64)(range + 1) * N + li] : 0u;
     const u32 smin = T.soft_min[li];
     gu32* const base = (gu32*)(uintptr_t)T.recs[li];
-    gu32* const sentinel = (gu32*)(uintptr_t)kmx_cols_sentinel;
+    // (its address formed once per work item and kept in a scalar register pair: as a constant it was rebuilt -- s_getpc_b64 and two
+    //  adds -- in front of every slot's refill)
+    u64 sent_a = (u64)(uintptr_t)kmx_cols_sentinel; asm volatile("" : "+s"(sent_a));
+    gu32* const sentinel = (gu32*)(uintptr_t)sent_a;
     CRec rec[CL_U];
 #pragma unroll
     for (int u = 0; u < CL_U; u++) {
@@ -673,10 +690,20 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
         for (int g = 0; g < CL_U; g += 4) {
           __builtin_amdgcn_sched_barrier(0);
           u32 curg = cur; asm volatile("" : "+v"(curg));      // (re-derived per group: 16 slot indices kept live get spilled)
+          // (the hash word's family: a uniform test per group of four slots, not one inside every slot's hash)
+          u32 hs[4];
+          if (__builtin_expect((mult & 0x80000000u) != 0, 0)) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) hs[j] = cl_thash_wide(cl_key(rec[g + j]), mult);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) hs[j] = cl_thash_cheap(cl_key(rec[g + j]), mult);
+          }
           ClEnt pe[4];
 #pragma unroll
-          for (int j = 0; j < 4; j++) pe[j] = ent_load(tab, cl_thash(cl_key(rec[g + j]), mult));
-          u32 ovm = 0;
+          for (int j = 0; j < 4; j++) pe[j] = ent_load(tab, hs[j]);
+          u32 ovm = 0;          // bit j: slot g + j holds a record for the slices
+          bool anybig = false;  // NAR: some slot of the group deposits a count above 254
 #pragma unroll
           for (int j = 0; j < 4; j++) {
             // straight-line: masks and selects, no branches (a deposit that is none goes to a scratch word)
@@ -691,30 +718,42 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
             // (RESC: a row key's row has recurrence-min >= share-min solid records: its non-solid records are rescued, written like the others)
             const bool dep = RESC ? (cons && hit && (solid || rescue)) : (solid && hit);
             if (RESC) { const bool rs = cons && hit && !solid && rescue; rsum += rs ? c : 0u; rn += rs ? 1u : 0u; }
-            bool big = false;      // NAR: a count that does not fit its byte -- to the 4-byte row, by the lane that holds it (below, in the slot's one branch)
-            if (NAR) { img8[dep ? __umul24(pe[j].idx - 1, nbs) + lg : dummyb] = (u8)min(c, 255u); big = dep && c > 254u; }
-            else if (MODE == 0) img[dep ? __umul24(pe[j].idx - 1, iw) + lg : dummy] = c;
+            // NAR: a count that does not fit its byte goes to the 4-byte row, by the lane that holds it (below, once per group: rare)
+            // (the deposit's place: one multiply-add -- idx = row + 1, lgm = lg - row pitch -- and one select; left to the compiler the
+            //  select became a branch around the multiply, exec saved and restored in every slot)
+            if (NAR) { u32 a = __umul24(pe[j].idx, nbs) + lgm; asm volatile("" : "+v"(a)); img8[dep ? a : dummyb] = (u8)min(c, 255u); anybig |= dep && c > 254u; }
+            else if (MODE == 0) { u32 a = __umul24(pe[j].idx, iw) + lgm; asm volatile("" : "+v"(a)); img[dep ? a : dummy] = c; }
             else if (dep) atomicOr(&img[__umul24(pe[j].idx - 1, iw) + (lg >> 5)], 1u << (lg & 31u));
-            ovm |= (((RESC ? cons : solid) && !hit) ? 1u : 0u) << j;
-            if (NAR) ovm |= (big ? 0x11u : 0u) << j;      // (bit 4 + j: the slot's record is such a count, not a record for the slices)
+            ovm |= ((RESC ? cons : solid) && !hit) ? (1u << j) : 0u;
           }
           asm volatile("" : "+v"(tsum), "+v"(tn));      // summed up here, not at the end of the scan (with every count kept until then)
           if (RESC) asm volatile("" : "+v"(rsum), "+v"(rn));
-          // solid records that are not row keys: appended to the wave's slice of the tile (positions from ballots)
+          // solid records that are not row keys: appended to the wave's slice of the tile (positions from ballots).  ONCE per group
+          // of four slots, not once per slot: 3 % of the records are such, so four slots in five hold one in some lane -- but a lane
+          // holds two of a group once in 200 times.  Every lane with a marked slot picks its lowest one (a select among its four
+          // records), one ballot / position / store sequence serves all of them, and a second turn takes what is left: 1.3 sequences
+          // a group where the per-slot form ran 3.3.  (The entries of a slice come in another order: k_cols_sparse sorts them.)
+          if (NAR && __builtin_expect(__ballot(anybig) != 0, 0)) {      // counts above 254 -- rare: to the 4-byte row, the slot's row looked up again
 #pragma unroll
-          for (int j = 0; j < 4; j++) {
-            u64 bal = __ballot((ovm >> j) & 1u);
-            if (bal) {      // (the same block without this branch around it: no difference, 2.29 ms either way)
-              if (NAR) {
-                const bool isbig = (ovm >> (4 + j)) & 1u;
-                if (__builtin_expect(__ballot(isbig) != 0, 0)) {
-                  if (isbig) { const u32 rw = ent_load(tab, cl_thash(cl_key(rec[g + j]), mult)).idx - 1; reinterpret_cast<u32*>(C.dense + (u64)(s0 + rw) * opitch)[li] = cl_cnt(rec[g + j]); rowbig[rw] = 1; }      // (its row: looked up again -- rare)
-                  ovm &= isbig ? ~(1u << j) : ~0u;
-                  bal = __ballot((ovm >> j) & 1u);
-                }
+            for (int j = 0; j < 4; j++) {
+              const ClEnt e = ent_load(tab, cl_thash(cl_key(rec[g + j]), mult));
+              const u32 c = cl_cnt(rec[g + j]);
+              const bool cons = (consm >> (g + j)) & 1u;
+              if (cons && ent_hit(e, cl_key(rec[g + j])) && (RESC ? (c >= smin || rescue) : c >= smin) && c > 254u) {      // (the deposit's own test)
+                reinterpret_cast<u32*>(C.dense + (u64)(s0 + e.idx - 1) * opitch)[li] = c; rowbig[e.idx - 1] = 1;
               }
-              const CKey kk = cl_key(rec[g + j]);
-              const u64 pay = li_hi | cl_cnt(rec[g + j]) | ((RESC && cl_cnt(rec[g + j]) < smin) ? CL_NONSOLID : 0ULL);
+            }
+          }
+          if (__ballot(ovm != 0)) {      // one uniform test for the whole group
+            u32 om = ovm;
+            for (u64 bal = __ballot(om != 0); bal; bal = __ballot(om != 0)) {
+              const bool mine = om != 0;
+              CRec sr = cl_pick((om & 4u) != 0, rec[g + 2], rec[g + 3]);      // my lowest marked slot's record (temporaries of this block)
+              sr = cl_pick((om & 2u) != 0, rec[g + 1], sr);
+              sr = cl_pick((om & 1u) != 0, rec[g], sr);
+              om &= om - 1u;
+              const CKey kk = cl_key(sr);
+              const u64 pay = li_hi | cl_cnt(sr) | ((RESC && cl_cnt(sr) < smin) ? CL_NONSOLID : 0ULL);
 #if KMX_CL_KW == 1
 #define CL_PUT(o, pos) do { (o)[2 * (pos)] = kk; (o)[2 * (pos) + 1] = pay; } while (0)
 #else
@@ -722,18 +761,18 @@ void k_merge_cols(const TaskDev* __restrict__ tasks, const ColsDev* __restrict__
 #endif
               if (CL_HALVES == 1) {
                 if (EXT && __builtin_expect(wov + (u32)__popcll(bal) > (u32)CL_OVW && xb0 == 0, 0)) extend(xb0);
-                if ((ovm >> j) & 1u) {
+                if (mine) {
                   const u32 pos = wov + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
                   if (pos < (u32)CL_OVW) CL_PUT(ovk0, pos);
                   else if (EXT && xb0 - 1u < 0xFFFFFFFEu && pos - (u32)CL_OVW < (u32)CL_XS) { gu64w* const o = ovx + (u64)(xb0 - 1u) * EW; const u32 px = pos - (u32)CL_OVW; CL_PUT(o, px); }
                 }
                 wov += (u32)__popcll(bal);
               } else {
-                const u64 hi = __ballot(((ovm >> j) & 1u) && !ck_lt(kk, kmid)), lo = bal & ~hi;
+                const bool up = !ck_lt(kk, kmid);
+                const u64 hi = __ballot(mine && up), lo = bal & ~hi;
                 if (EXT && __builtin_expect(wov + (u32)__popcll(lo) > (u32)CL_OVW && xb0 == 0, 0)) extend(xb0);
                 if (EXT && __builtin_expect(wov1 + (u32)__popcll(hi) > (u32)CL_OVW && xb1 == 0, 0)) extend(xb1);
-                if ((ovm >> j) & 1u) {
-                  const bool up = !ck_lt(kk, kmid);
+                if (mine) {
                   const u64 m = up ? hi : lo;
                   const u32 pos = (up ? wov1 : wov) + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
                   if (pos < (u32)CL_OVW) { gu64w* const o = up ? ovk1 : ovk0; CL_PUT(o, pos); }
