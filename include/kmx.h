@@ -283,7 +283,8 @@ uint8_t* kmx_filter_marks_alloc(kmx_ctx* ctx, uint64_t n);
 void     kmx_filter_marks_free(kmx_ctx* ctx, uint8_t* marks);
 
 /* every pointer of the task a DEVICE pointer; the kernels are queued on the context's stream (kmx_stream) and the call returns;
- * the result stays in HBM until it is freed */
+ * the result (M, V, K as asked for) stays in HBM until it is freed, the call's scratch returns to the context's pool in
+ * kmx_filter_result_wait */
 int kmx_filter_dev(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out);
 /* HOST pointers (see key_on_device): the rows (and the key) are uploaded on a stream of their own, so a run travels while the run
  * before it is filtered; host marks are brought back too.  The host buffers may be reused once kmx_filter_result_wait has returned. */
@@ -301,7 +302,8 @@ int      kmx_filter_result_copy_vector(kmx_filter_result* r, uint32_t* host_dst,
 uint64_t kmx_filter_result_absent(kmx_filter_result* r);           /* records of K */
 const void* kmx_filter_result_absent_dev(kmx_filter_result* r);
 int      kmx_filter_result_copy_absent(kmx_filter_result* r, void* host_dst, uint64_t dst_bytes);
-/* duration in ms of the call's kernels (needs kmx_set_profiling(ctx, 1)); < 0 if unavailable */
+/* duration in ms of the call's kernels, for kmx_filter_host with marks their way back included (needs kmx_set_profiling(ctx, 1));
+ * < 0 if unavailable */
 double   kmx_filter_result_kernel_ms(kmx_filter_result* r);
 /* algorithmic bytes: the rows' keys and the key list read, the kept rows in and out (M), the vector (V), the absent records (K) --
  * not the rows that are dropped: the match touches their key only */
@@ -333,9 +335,10 @@ void     kmx_filter_result_free(kmx_filter_result* r);
  * 1 ... 4, mode COUNT or PA, count_bytes 1, 2 or 4 for COUNT, at least one column a block (KMX_E_INVAL; Bloom modes
  * KMX_E_UNSUPPORTED); at most 2^32 - 256 rows a block and as many in the output -- the output's rows are known on the device
  * only, so the test is on their bound, the blocks' rows together; an input or output row below 4 GiB (KMX_E_UNSUPPORTED).
- * Scratch, from the context's pool: 8 * key_words + 4 * n_blocks bytes per input row, and the output is sized for the bound of its
- * rows, the blocks' rows together (the call does not wait for the true count).  A call on large bodies already in HBM can therefore
- * return KMX_E_NOMEM although its true output would fit: combine such a partition in key ranges, as `kmx combine --gpus` does. */
+ * Scratch, from the context's pool until kmx_combine_result_wait gives it back: 8 * key_words + 4 * n_blocks bytes per input row;
+ * and the output is sized for the bound of its rows, the blocks' rows together (the call does not wait for the true count).  A
+ * call on large bodies already in HBM can therefore return KMX_E_NOMEM although its true output would fit: combine such a
+ * partition in key ranges, as `kmx combine --gpus` does. */
 #define KMX_COMBINE_DROP_LAST 1u
 #define KMX_COMBINE_MAX_BLOCKS 64u
 typedef struct {

@@ -19,13 +19,24 @@
 //                     zeros; the others (keys, block boundaries, row ends, narrow counts, every PA piece) are built unit by unit.
 //
 // Nothing here holds a row in LDS: no limit on the number of columns.  No atomics, no library kernels.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 namespace kmx {
 
 constexpr u32 CB_TILE = 256;           // rows of a rank tile = threads of a workgroup
 constexpr u32 CB_LDS_W = 2048;         // u64 words of keys staged per span (16 KB)
 constexpr u32 CB_MAX_GRID = 1u << 18;  // workgroups of a launch: every kernel strides over its work
+
+struct CombineBlock {      // one block as the kernels see it (array in HBM)
+  const u8* rows;
+  u64 irb;                 // bytes of a row: key + payload
+  u64 key_off;             // rows of the blocks in front of it (its place in the dense key array)
+  u32 n_rows, n_cols;
+  u32 cb;                  // bytes of a count (COUNT)
+  u32 pos;                 // its first column in the output
+  u32 toff;                // its first tile slot: tiles + 1 slots a block (tile counts / bases with the total behind them, 4 u64 of bits a slot)
+  u32 ntiles;
+};
 
 // a row's key: rows start at any byte (a .kmer body with 1-byte counts has 9-byte rows)
 template <int KW> __device__ __forceinline__ Key<KW> cb_row_key(const u8* p) {
@@ -330,7 +341,7 @@ void k_combine_move(const CombineBlock* __restrict__ blocks, u32 nb, u32 kb, u32
   }
 }
 
-// ---- launchers ------------------------------------------------------------------------------------------------------------------
+// ---- launchers: this file's own (no header declares them; their names stay among the library's dynamic symbols as they were) --------
 static u32 cb_grid(u64 items) { return (u32)std::min<u64>(std::max<u64>(items, 1), kmx_grid_cap(CB_MAX_GRID)); }
 
 u32 combine_tiles(u32 n) { return (n + CB_TILE - 1) / CB_TILE; }
@@ -393,3 +404,130 @@ hipError_t launch_combine_move(int pa, const CombineBlock* blocks, u32 nb, u32 k
 }
 
 }  // namespace kmx
+
+using namespace kmx;
+
+// ---- C ABI ------------------------------------------------------------------------------------------------------------------------------
+// kmx_combine_dev / kmx_combine_host: the blocks of one partition (or of one key range of it) joined by key
+struct kmx_combine_result : MatResult {      // n_rows: the blocks' rows together, the bound of the output's rows; n_cols: their columns together;
+  u32 nb = 0, kw = 0, mode = 0, flags = 0;   // row_bytes: 0 (every block has its own); h_tot: [0] output rows, [1] distinct keys
+  u32 n_slots = 0;
+  u64 orb = 0, in_bytes = 0;                 // a row of the output; the bytes of the blocks' rows
+  u8* d_out = nullptr;
+};
+
+static u64 combine_block_row_bytes(const kmx_combine_task* K, const kmx_block& b)
+{ return 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? (u64)b.n_cols * b.count_bytes : ((u64)b.n_cols + 7) / 8); }
+
+static int combine_check(kmx_ctx* ctx, const kmx_combine_task* K, const char* who, u64* orb, u64* cap, u64* n_cols)
+{
+  const MatCheck c{ctx, who};
+  int rc;
+  if ((rc = c.key_words(K->key_words))) return rc;
+  if (MatCheck::is_bloom(K->mode)) return c.no(KMX_E_UNSUPPORTED, ": Bloom filter matrices are not combined (KMX_MODE_COUNT and KMX_MODE_PA rows only)");
+  if ((rc = c.mode(K->mode))) return rc;
+  if (K->flags & ~(u32)KMX_COMBINE_DROP_LAST) return c.no(KMX_E_INVAL, ": unknown flag (KMX_COMBINE_DROP_LAST is the only one)");
+  if (K->n_blocks == 0) return c.no(KMX_E_INVAL, ": a task has at least one block");
+  if (K->n_blocks > KMX_COMBINE_MAX_BLOCKS) return c.no(KMX_E_UNSUPPORTED, ": " + std::to_string(K->n_blocks) + " blocks, at most " + std::to_string(KMX_COMBINE_MAX_BLOCKS) + " are combined in one call");
+  if (!K->blocks) return c.no(KMX_E_INVAL, ": null block array");
+  u64 cols = 0, rows = 0;
+  for (u32 i = 0; i < K->n_blocks; i++) {
+    const kmx_block& b = K->blocks[i];
+    const std::string bi = ": block " + std::to_string(i);
+    if (b.n_cols == 0) return c.no(KMX_E_INVAL, bi + ": a block has at least one column");
+    if (K->mode == KMX_MODE_COUNT && b.count_bytes != 1 && b.count_bytes != 2 && b.count_bytes != 4) return c.no(KMX_E_INVAL, bi + ": count_bytes must be 1, 2 or 4");
+    if (b.n_rows && !b.rows) return c.no(KMX_E_INVAL, bi + ": null row pointer");
+    if (b.n_rows > 0xFFFFFF00ull) return c.no(KMX_E_UNSUPPORTED, bi + ": more than 2^32 - 256 rows (combine the partition in key ranges)");
+    if (combine_block_row_bytes(K, b) > 0xFFFFFFFFull) return c.no(KMX_E_UNSUPPORTED, bi + ": rows of 4 GiB and more");
+    cols += b.n_cols; rows += b.n_rows;
+  }
+  *orb = 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? 4 * cols : (cols + 7) / 8);
+  if (*orb > 0xFFFFFFFFull) return c.no(KMX_E_UNSUPPORTED, ": output rows of 4 GiB and more");
+  // the output's rows are known on the device only; the blocks' rows together bound them
+  if (rows > 0xFFFFFF00ull) return c.no(KMX_E_UNSUPPORTED, ": the blocks hold more than 2^32 - 256 rows together, the bound of the output's rows (combine the partition in key ranges)");
+  *cap = rows; *n_cols = cols;
+  return KMX_OK;
+}
+
+// the kernels of one call, queued on ctx->stream; rows[i]: block i's rows in device memory
+static int combine_queue(kmx_ctx* ctx, const kmx_combine_task* K, const void* const* rows, kmx_combine_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u32 nb = R->nb, kw = R->kw;
+  CombineBlock* h_desc = (CombineBlock*)R->pin(sizeof(CombineBlock) * nb);      // the blocks as the kernels see them, on their way up
+  if (!(R->h_tot = (u32*)R->pin(64)) || !h_desc) return ctx->fail(KMX_E_NOMEM, "kmx_combine: host allocation failed");
+  R->h_tot[0] = R->h_tot[1] = 0;
+  u64 key_off = 0; u32 pos = 0, toff = 0;
+  for (u32 i = 0; i < nb; i++) {
+    const kmx_block& b = K->blocks[i];
+    CombineBlock& d = h_desc[i];
+    d.rows = (const u8*)rows[i]; d.irb = combine_block_row_bytes(K, b); d.key_off = key_off;
+    d.n_rows = (u32)b.n_rows; d.n_cols = b.n_cols; d.cb = K->mode == KMX_MODE_COUNT ? b.count_bytes : 0; d.pos = pos; d.toff = toff;
+    d.ntiles = combine_tiles(d.n_rows);
+    key_off += b.n_rows; pos += b.n_cols; toff += d.ntiles + 1;
+    R->in_bytes += b.n_rows * d.irb;
+  }
+  R->n_slots = toff;
+  const u64 cap = R->n_rows;
+  CombineBlock* d_desc = (CombineBlock*)R->tmp(sizeof(CombineBlock) * nb);
+  u32* d_tot = (u32*)R->tmp(64);
+  u32* d_tcnt = (u32*)R->tmp(4ull * toff);
+  u64* d_fbits = (u64*)R->tmp(32ull * toff);
+  u64* d_keys = (u64*)R->tmp(8ull * kw * cap);
+  u32* d_src = (u32*)R->tmp(4ull * nb * cap);
+  R->d_out = (u8*)R->keep(cap * R->orb + 16);      // every key held by one block only
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_combine: device allocation failed");
+  KMX_HIP(ctx, hipMemcpyAsync(d_desc, h_desc, sizeof(CombineBlock) * nb, hipMemcpyHostToDevice, st));
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipMemsetAsync(d_tot, 0, 64, st));
+  if (cap) {
+    KMX_HIP(ctx, hipMemsetAsync(d_src, 0, 4ull * nb * cap, st));
+    KMX_HIP(ctx, launch_combine_keys((int)kw, d_desc, nb, toff, d_keys, st));
+    KMX_HIP(ctx, launch_combine_first((int)kw, d_desc, nb, toff, d_keys, d_tcnt, d_fbits, st));
+    KMX_HIP(ctx, launch_combine_scan(d_desc, nb, d_tcnt, st));
+    KMX_HIP(ctx, launch_combine_place((int)kw, d_desc, nb, toff, d_keys, d_tcnt, d_fbits, d_src, cap, st));
+    KMX_HIP(ctx, launch_combine_total(d_desc, nb, d_tcnt, d_src, cap, (R->flags & KMX_COMBINE_DROP_LAST) != 0, d_tot, st));
+    KMX_HIP(ctx, launch_combine_move(R->mode == KMX_MODE_PA, d_desc, nb, 8 * kw, R->n_cols, (u32)R->orb, d_src, cap, d_tot, R->d_out, st));
+  }
+  return mat_queue_tail(R, d_tot, d_tot + 1);
+}
+
+static int combine_call(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out, bool host, const char* who)
+{
+  if (!ctx) return KMX_E_INVAL;
+  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
+  *out = nullptr;
+  u64 orb = 0, cap = 0, n_cols = 0;
+  int rc = combine_check(ctx, task, who, &orb, &cap, &n_cols);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipSetDevice(ctx->device));
+  kmx_combine_result* R = new kmx_combine_result();
+  R->ctx = ctx; R->name = "kmx_combine"; R->n_rows = cap; R->row_bytes = 0; R->n_cols = (u32)n_cols;
+  R->nb = task->n_blocks; R->kw = task->key_words; R->mode = task->mode; R->flags = task->flags; R->orb = orb;
+  std::vector<const void*> rows(task->n_blocks);
+  for (u32 i = 0; i < task->n_blocks; i++) rows[i] = task->blocks[i].rows;
+  if (host) {      // the blocks that do not lie on the device
+    for (u32 i = 0; i < task->n_blocks; i++) {
+      const kmx_block& b = task->blocks[i];
+      const u64 bytes = b.n_rows * combine_block_row_bytes(task, b);
+      if (bytes && !(task->block_on_device && task->block_on_device[i])) rows[i] = mat_upload_tmp(R, b.rows, bytes);
+    }
+    rc = R->nomem ? ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed") : mat_uploads_done(R, who);
+  }
+  if (rc == KMX_OK) rc = combine_queue(ctx, task, rows.data(), R);
+  return mat_finish(rc, R, out, host);
+}
+extern "C" int kmx_combine_dev(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out) { return combine_call(ctx, task, out, false, "kmx_combine_dev"); }
+extern "C" int kmx_combine_host(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out) { return combine_call(ctx, task, out, true, "kmx_combine_host"); }
+
+extern "C" int kmx_combine_result_wait(kmx_combine_result* R) { return mat_wait(R); }
+extern "C" uint64_t kmx_combine_result_rows(kmx_combine_result* R) { return mat_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" uint64_t kmx_combine_result_row_bytes(const kmx_combine_result* R) { return R ? R->orb : 0; }
+extern "C" uint64_t kmx_combine_result_body_bytes(kmx_combine_result* R) { return kmx_combine_result_rows(R) * (R ? R->orb : 0); }
+extern "C" const void* kmx_combine_result_body_dev(kmx_combine_result* R) { return mat_wait(R) == KMX_OK ? R->d_out : nullptr; }
+extern "C" uint64_t kmx_combine_result_algo_bytes(kmx_combine_result* R) { return mat_wait(R) == KMX_OK ? R->in_bytes + (u64)R->h_tot[0] * R->orb : 0; }
+extern "C" int kmx_combine_result_copy_body(kmx_combine_result* R, void* host_dst, uint64_t dst_bytes)
+{ return mat_copy_out(R, host_dst, dst_bytes, R ? R->d_out : nullptr, kmx_combine_result_body_bytes(R), 1); }
+extern "C" double kmx_combine_result_kernel_ms(kmx_combine_result* R) { return mat_kernel_ms(R); }
+extern "C" void kmx_combine_result_free(kmx_combine_result* R) { mat_free(R); }

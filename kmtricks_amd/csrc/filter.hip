@@ -12,7 +12,7 @@
 //   k_filter_absent_* the key records without a mark, compacted (count per tile, the same scan, scatter)
 //
 // Nothing here holds a row in LDS or a row's cursors: no limit on the number of columns.
-#include "kmx_host.hpp"
+#include "matrix_host.hpp"
 
 namespace kmx {
 
@@ -288,3 +288,136 @@ hipError_t launch_filter_absent_scatter(int kw, const u8* key, const u8* marks, 
 }
 
 }  // namespace kmx
+
+using namespace kmx;
+
+// ---- C ABI ------------------------------------------------------------------------------------------------------------------------------
+// kmx_filter_dev / kmx_filter_host: a run of whole rows of one partition's matrix against the new sample's count list
+struct kmx_filter_result : MatResult {      // row_bytes: a row as it came in; h_tot: [0] kept rows, [1] absent records
+  u32 n_key = 0, want = 0, kw = 0;
+  u64 orb = 0;                              // a row of M
+  u32* d_vec = nullptr;                     // null without KMX_FILTER_V
+  u8 *d_out = nullptr, *d_absent = nullptr;
+  u8* h_marks = nullptr;                    // kmx_filter_host: where the marks go back to
+};
+
+static int filter_check(kmx_ctx* ctx, const kmx_filter_task* K, const char* who, u64* irb, u64* orb)
+{
+  const MatCheck c{ctx, who};
+  int rc;
+  if ((rc = c.key_words(K->key_words))) return rc;
+  if (MatCheck::is_bloom(K->mode))
+    return c.no(KMX_E_UNSUPPORTED, ": Bloom filter matrices are not filtered (KMX_MODE_COUNT and KMX_MODE_PA rows of k-mer matrices only; hash matrices neither)");
+  if ((rc = c.mode(K->mode)) || (rc = c.n_cols(K->n_cols))) return rc;
+  if (K->want == 0 || (K->want & ~(u32)(KMX_FILTER_M | KMX_FILTER_V | KMX_FILTER_K))) return c.no(KMX_E_INVAL, ": want must be a non-empty set of KMX_FILTER_M | KMX_FILTER_V | KMX_FILTER_K");
+  if (K->n_rows && !K->rows) return c.no(KMX_E_INVAL, ": null row pointer");
+  if (K->key.n && !K->key.recs) return c.no(KMX_E_INVAL, ": null record pointer");
+  if ((uintptr_t)K->key.recs & 3u) return c.no(KMX_E_INVAL, ": record pointers must be 4-byte aligned");
+  *irb = MatCheck::row_bytes(K->key_words, K->mode, K->n_cols);
+  *orb = *irb + (K->mode == KMX_MODE_COUNT ? 4 : 0);
+  if ((rc = c.row_fits(*orb))) return rc;
+  if (K->n_rows > 0xFFFFFF00ull) return c.no(KMX_E_UNSUPPORTED, ": more than 2^32 - 256 rows in one call (filter the partition in runs of rows)");
+  if (K->key.n > 0xFFFFFF00ull) return c.no(KMX_E_UNSUPPORTED, ": more than 2^32 - 256 records in the key list");
+  return KMX_OK;
+}
+
+// the kernels of one call, queued on ctx->stream; every pointer of K a device pointer
+static int filter_queue(kmx_ctx* ctx, const kmx_filter_task* K, kmx_filter_result* R)
+{
+  hipStream_t st = ctx->stream;
+  const u32 n_rows = (u32)R->n_rows, n_key = R->n_key, tiles = filter_tiles(n_rows), ktiles = filter_tiles(n_key);
+  const u64 irb = R->row_bytes, rb = R->kw * 8 + 4;
+  const bool m = K->want & KMX_FILTER_M, v = K->want & KMX_FILTER_V, k = K->want & KMX_FILTER_K;
+  if (!(R->h_tot = (u32*)R->pin(64))) return ctx->fail(KMX_E_NOMEM, "kmx_filter: host allocation failed");
+  R->h_tot[0] = R->h_tot[1] = 0;
+  u32* d_hit = (u32*)R->tmp(4ull * n_rows);
+  u32* d_vec = (u32*)(v ? R->keep(4ull * n_rows) : R->tmp(4ull * n_rows));
+  u32* d_tiles = (u32*)R->tmp(4ull * (tiles + 1));
+  u32* d_ktiles = nullptr;
+  u8 *marks = K->marks, *marks_own = nullptr;
+  if (!marks) marks = marks_own = (u8*)R->tmp(n_key);
+  if (v) R->d_vec = d_vec;
+  if (m) R->d_out = (u8*)R->keep((u64)n_rows * R->orb + 16);      // every row kept
+  if (k) { d_ktiles = (u32*)R->tmp(4ull * (ktiles + 1)); R->d_absent = (u8*)R->keep((u64)n_key * rb); }
+  if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_filter: device allocation failed");
+  if (marks_own && n_key) KMX_HIP(ctx, hipMemsetAsync(marks_own, 0, n_key, st));
+  int rc = mat_queue_head(R);
+  if (rc != KMX_OK) return rc;
+  if (n_rows) KMX_HIP(ctx, launch_filter_match((int)R->kw, (const u8*)K->rows, n_rows, irb, (const u8*)K->key.recs, n_key, K->mode == KMX_MODE_PA,
+                                               d_hit, d_vec, marks, d_tiles, st));
+  KMX_HIP(ctx, launch_filter_scan(d_tiles, tiles, st));
+  if (m && n_rows) KMX_HIP(ctx, launch_filter_move((const u8*)K->rows, n_rows, irb, R->orb, d_hit, d_vec, d_tiles, R->d_out, st));
+  if (k) {
+    if (n_key) KMX_HIP(ctx, launch_filter_absent_count(marks, n_key, d_ktiles, st));
+    KMX_HIP(ctx, launch_filter_scan(d_ktiles, ktiles, st));
+    if (n_key) KMX_HIP(ctx, launch_filter_absent_scatter((int)R->kw, (const u8*)K->key.recs, marks, n_key, d_ktiles, R->d_absent, st));
+  }
+  if (R->h_marks && n_key) KMX_HIP(ctx, hipMemcpyAsync(R->h_marks, marks, n_key, hipMemcpyDeviceToHost, st));
+  return mat_queue_tail(R, d_tiles + tiles, k ? d_ktiles + ktiles : nullptr);
+}
+
+extern "C" uint8_t* kmx_filter_marks_alloc(kmx_ctx* ctx, uint64_t n)
+{
+  if (!ctx || hipSetDevice(ctx->device) != hipSuccess) return nullptr;
+  u8* p = (u8*)ctx->dalloc(n);
+  if (!p) { ctx->fail(KMX_E_NOMEM, "kmx_filter_marks_alloc: device allocation failed"); return nullptr; }
+  if (hipMemsetAsync(p, 0, n ? n : 1, ctx->stream) != hipSuccess) { ctx->dfree(p); ctx->fail(KMX_E_HIP, "kmx_filter_marks_alloc: clearing failed"); return nullptr; }
+  return p;
+}
+extern "C" void kmx_filter_marks_free(kmx_ctx* ctx, uint8_t* marks) { if (ctx && marks) { (void)hipStreamSynchronize(ctx->stream); ctx->dfree(marks); } }
+
+static int filter_call(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out, bool host, const char* who)
+{
+  if (!ctx) return KMX_E_INVAL;
+  if (!task || !out) return ctx->fail(KMX_E_INVAL, std::string(who) + ": null argument");
+  *out = nullptr;
+  u64 irb = 0, orb = 0;
+  int rc = filter_check(ctx, task, who, &irb, &orb);
+  if (rc != KMX_OK) return rc;
+  KMX_HIP(ctx, hipSetDevice(ctx->device));
+  kmx_filter_result* R = new kmx_filter_result();
+  R->ctx = ctx; R->name = "kmx_filter"; R->n_rows = task->n_rows; R->row_bytes = irb; R->n_cols = task->n_cols;
+  R->n_key = (u32)task->key.n; R->want = task->want; R->kw = task->key_words; R->orb = orb;
+  kmx_filter_task dt = *task;
+  if (host) {      // the rows and, unless they lie on the device, the key list and its marks
+    const u64 rows_bytes = task->n_rows * irb, key_bytes = task->key.n * (task->key_words * 8 + 4);
+    if (rows_bytes) dt.rows = mat_upload_tmp(R, task->rows, rows_bytes);
+    if (!task->key_on_device) {
+      if (key_bytes) dt.key.recs = mat_upload_tmp(R, task->key.recs, key_bytes);
+      if (task->marks && task->key.n) { dt.marks = (u8*)mat_upload_tmp(R, task->marks, task->key.n); R->h_marks = task->marks; }
+    }
+    rc = R->nomem ? ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed") : mat_uploads_done(R, who);
+  }
+  if (rc == KMX_OK) rc = filter_queue(ctx, &dt, R);
+  return mat_finish(rc, R, out, host);
+}
+extern "C" int kmx_filter_dev(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out) { return filter_call(ctx, task, out, false, "kmx_filter_dev"); }
+extern "C" int kmx_filter_host(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out) { return filter_call(ctx, task, out, true, "kmx_filter_host"); }
+
+extern "C" int kmx_filter_result_wait(kmx_filter_result* R) { return mat_wait(R); }
+extern "C" uint64_t kmx_filter_result_rows(kmx_filter_result* R) { return mat_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
+extern "C" uint64_t kmx_filter_result_row_bytes(const kmx_filter_result* R) { return R ? R->orb : 0; }
+extern "C" uint64_t kmx_filter_result_body_bytes(kmx_filter_result* R) { return R && (R->want & KMX_FILTER_M) ? kmx_filter_result_rows(R) * R->orb : 0; }
+extern "C" const void* kmx_filter_result_body_dev(kmx_filter_result* R) { return mat_wait(R) == KMX_OK ? R->d_out : nullptr; }
+extern "C" const void* kmx_filter_result_vector_dev(kmx_filter_result* R) { return mat_wait(R) == KMX_OK ? R->d_vec : nullptr; }
+extern "C" uint64_t kmx_filter_result_vector_len(const kmx_filter_result* R) { return R && (R->want & KMX_FILTER_V) ? R->n_rows : 0; }
+extern "C" uint64_t kmx_filter_result_absent(kmx_filter_result* R) { return R && (R->want & KMX_FILTER_K) && mat_wait(R) == KMX_OK ? R->h_tot[1] : 0; }
+extern "C" const void* kmx_filter_result_absent_dev(kmx_filter_result* R) { return mat_wait(R) == KMX_OK ? R->d_absent : nullptr; }
+extern "C" int kmx_filter_result_copy_body(kmx_filter_result* R, void* host_dst, uint64_t dst_bytes)
+{ return mat_copy_out(R, host_dst, dst_bytes, R ? R->d_out : nullptr, kmx_filter_result_body_bytes(R), 1); }
+extern "C" int kmx_filter_result_copy_vector(kmx_filter_result* R, uint32_t* host_dst, uint64_t dst_entries)
+{ return mat_copy_out(R, host_dst, dst_entries, R ? R->d_vec : nullptr, kmx_filter_result_vector_len(R), 4); }
+extern "C" int kmx_filter_result_copy_absent(kmx_filter_result* R, void* host_dst, uint64_t dst_bytes)
+{ return mat_copy_out(R, host_dst, dst_bytes, R ? R->d_absent : nullptr, R ? kmx_filter_result_absent(R) * (R->kw * 8 + 4) : 0, 1); }
+extern "C" double kmx_filter_result_kernel_ms(kmx_filter_result* R) { return mat_kernel_ms(R); }
+extern "C" uint64_t kmx_filter_result_algo_bytes(kmx_filter_result* R)
+{
+  if (mat_wait(R) != KMX_OK) return 0;
+  const u64 rb = R->kw * 8 + 4;
+  u64 b = R->n_rows * 8 * R->kw + (u64)R->n_key * rb;
+  if (R->want & KMX_FILTER_M) b += (u64)R->h_tot[0] * (R->row_bytes + R->orb);
+  if (R->want & KMX_FILTER_V) b += 4 * R->n_rows;
+  if (R->want & KMX_FILTER_K) b += (u64)R->h_tot[1] * rb;
+  return b;
+}
+extern "C" void kmx_filter_result_free(kmx_filter_result* R) { mat_free(R); }

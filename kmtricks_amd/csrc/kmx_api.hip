@@ -1,5 +1,5 @@
-// kmx_api.hip -- C ABI of libkmx (include/kmx.h): context, device memory pool, stores, batch merge driver, filter and combine (the
-// query, dist and diff calls lie beside their kernels).
+// kmx_api.hip -- C ABI of libkmx (include/kmx.h): context, device memory pool, stores, batch merge driver (every
+// other call lies beside its kernels).
 // No CPU fallback anywhere: every entry point needs a live HIP device.
 #include "kmx_host.hpp"
 
@@ -1817,436 +1817,4 @@ extern "C" int kmx_merge(kmx_ctx* ctx, const kmx_merge_task* task, void** body, 
   else (void)hipStreamSynchronize(ctx->stream);
   ctx->dfree(d_in);
   return rc;
-}
-
-// ---- filter ------------------------------------------------------------------------------------------------------------------------
-// kmx_filter_dev / kmx_filter_host: a run of whole rows of one partition's matrix against the new sample's count list (filter.hip).
-struct kmx_filter_result {
-  kmx_ctx* ctx = nullptr;
-  u32 n_rows = 0, n_key = 0, want = 0, kw = 0;
-  u64 irb = 0, orb = 0;
-  u32 *d_hit = nullptr, *d_vec = nullptr, *d_tiles = nullptr, *d_ktiles = nullptr;
-  u8 *d_marks_own = nullptr, *d_out = nullptr, *d_absent = nullptr;
-  u8 *d_in_rows = nullptr, *d_in_key = nullptr, *d_in_marks = nullptr;      // kmx_filter_host: the uploads
-  u8* h_marks = nullptr;                                                      // ... and where the marks go back to
-  u32* h_tot = nullptr;                                                       // page-locked: [0] kept rows, [1] absent records
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
-};
-
-static int filter_check(kmx_ctx* ctx, const kmx_filter_task* K, const char* who, u64* irb, u64* orb)
-{
-  const std::string w(who);
-  if (K->key_words < 1 || K->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (K->mode == KMX_MODE_BF || K->mode == KMX_MODE_BFC || K->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter matrices are not filtered (KMX_MODE_COUNT and KMX_MODE_PA rows of k-mer matrices only; hash matrices neither)");
-  if (K->mode != KMX_MODE_COUNT && K->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (K->n_cols == 0) return ctx->fail(KMX_E_INVAL, w + ": a matrix has at least one column");
-  if (K->want == 0 || (K->want & ~(u32)(KMX_FILTER_M | KMX_FILTER_V | KMX_FILTER_K))) return ctx->fail(KMX_E_INVAL, w + ": want must be a non-empty set of KMX_FILTER_M | KMX_FILTER_V | KMX_FILTER_K");
-  if (K->n_rows && !K->rows) return ctx->fail(KMX_E_INVAL, w + ": null row pointer");
-  if (K->key.n && !K->key.recs) return ctx->fail(KMX_E_INVAL, w + ": null record pointer");
-  if ((uintptr_t)K->key.recs & 3u) return ctx->fail(KMX_E_INVAL, w + ": record pointers must be 4-byte aligned");
-  const u64 payload = K->mode == KMX_MODE_COUNT ? 4ull * K->n_cols : ((u64)K->n_cols + 7) / 8;
-  *irb = 8ull * K->key_words + payload;
-  *orb = *irb + (K->mode == KMX_MODE_COUNT ? 4 : 0);
-  if (*orb > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": rows of 4 GiB and more");
-  if (K->n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 rows in one call (filter the partition in runs of rows)");
-  if (K->key.n > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": more than 2^32 - 256 records in the key list");
-  return KMX_OK;
-}
-
-static void filter_release(kmx_filter_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_hit, R->d_vec, R->d_tiles, R->d_ktiles, R->d_marks_own, R->d_out, R->d_absent, R->d_in_rows, R->d_in_key, R->d_in_marks};
-  for (void* p : blocks) c->dfree(p);
-  c->hfree(R->h_tot);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
-
-// the kernels of one call, queued on ctx->stream; R holds the uploads already when kmx_filter_host calls
-static int filter_queue(kmx_ctx* ctx, const kmx_filter_task* K, kmx_filter_result* R)
-{
-  hipStream_t st = ctx->stream;
-  const u32 n_rows = R->n_rows, n_key = R->n_key, tiles = filter_tiles(n_rows), ktiles = filter_tiles(n_key);
-  const size_t rb = R->kw * 8 + 4;
-  const bool m = K->want & KMX_FILTER_M, k = K->want & KMX_FILTER_K;
-  if (!(R->h_tot = (u32*)ctx->halloc(64))) return ctx->fail(KMX_E_NOMEM, "kmx_filter: host allocation failed");
-  R->h_tot[0] = R->h_tot[1] = 0;
-  R->d_hit = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_vec = (u32*)ctx->dalloc(4ull * n_rows);
-  R->d_tiles = (u32*)ctx->dalloc(4ull * (tiles + 1));
-  u8* marks = K->marks;
-  if (!marks) marks = R->d_marks_own = (u8*)ctx->dalloc(n_key);
-  if (m) R->d_out = (u8*)ctx->dalloc((u64)n_rows * R->orb + 16);      // every row kept
-  if (k) { R->d_ktiles = (u32*)ctx->dalloc(4ull * (ktiles + 1)); R->d_absent = (u8*)ctx->dalloc((u64)n_key * rb); }
-  if (!R->d_hit || !R->d_vec || !R->d_tiles || !marks || (m && !R->d_out) || (k && (!R->d_ktiles || !R->d_absent)))
-    return ctx->fail(KMX_E_NOMEM, "kmx_filter: device allocation failed");
-  if (R->d_marks_own && n_key) KMX_HIP(ctx, hipMemsetAsync(R->d_marks_own, 0, n_key, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  if (n_rows) KMX_HIP(ctx, launch_filter_match((int)R->kw, (const u8*)K->rows, n_rows, R->irb, (const u8*)K->key.recs, n_key, K->mode == KMX_MODE_PA,
-                                               R->d_hit, R->d_vec, marks, R->d_tiles, st));
-  KMX_HIP(ctx, launch_filter_scan(R->d_tiles, tiles, st));
-  if (m && n_rows) KMX_HIP(ctx, launch_filter_move((const u8*)K->rows, n_rows, R->irb, R->orb, R->d_hit, R->d_vec, R->d_tiles, R->d_out, st));
-  if (k) {
-    if (n_key) KMX_HIP(ctx, launch_filter_absent_count(marks, n_key, R->d_ktiles, st));
-    KMX_HIP(ctx, launch_filter_scan(R->d_ktiles, ktiles, st));
-    if (n_key) KMX_HIP(ctx, launch_filter_absent_scatter((int)R->kw, (const u8*)K->key.recs, marks, n_key, R->d_ktiles, R->d_absent, st));
-  }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[0], R->d_tiles + tiles, 4, hipMemcpyDeviceToHost, st));
-  if (k) KMX_HIP(ctx, hipMemcpyAsync(&R->h_tot[1], R->d_ktiles + ktiles, 4, hipMemcpyDeviceToHost, st));
-  if (R->h_marks && n_key) KMX_HIP(ctx, hipMemcpyAsync(R->h_marks, marks, n_key, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-extern "C" uint8_t* kmx_filter_marks_alloc(kmx_ctx* ctx, uint64_t n)
-{
-  if (!ctx || hipSetDevice(ctx->device) != hipSuccess) return nullptr;
-  u8* p = (u8*)ctx->dalloc(n);
-  if (!p) { ctx->fail(KMX_E_NOMEM, "kmx_filter_marks_alloc: device allocation failed"); return nullptr; }
-  if (hipMemsetAsync(p, 0, n ? n : 1, ctx->stream) != hipSuccess) { ctx->dfree(p); ctx->fail(KMX_E_HIP, "kmx_filter_marks_alloc: clearing failed"); return nullptr; }
-  return p;
-}
-extern "C" void kmx_filter_marks_free(kmx_ctx* ctx, uint8_t* marks) { if (ctx && marks) { (void)hipStreamSynchronize(ctx->stream); ctx->dfree(marks); } }
-
-extern "C" int kmx_filter_dev(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_filter_dev: null argument");
-  *out = nullptr;
-  u64 irb = 0, orb = 0;
-  int rc = filter_check(ctx, task, "kmx_filter_dev", &irb, &orb);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_filter_result* R = new kmx_filter_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->n_key = (u32)task->key.n; R->want = task->want; R->kw = task->key_words; R->irb = irb; R->orb = orb;
-  if ((rc = filter_queue(ctx, task, R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); filter_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_filter_host(kmx_ctx* ctx, const kmx_filter_task* task, kmx_filter_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_filter_host: null argument");
-  *out = nullptr;
-  u64 irb = 0, orb = 0;
-  int rc = filter_check(ctx, task, "kmx_filter_host", &irb, &orb);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_filter_result* R = new kmx_filter_result();
-  R->ctx = ctx; R->n_rows = (u32)task->n_rows; R->n_key = (u32)task->key.n; R->want = task->want; R->kw = task->key_words; R->irb = irb; R->orb = orb;
-  kmx_filter_task dt = *task;
-  const u64 rows_bytes = task->n_rows * irb, key_bytes = task->key.n * (task->key_words * 8 + 4);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); filter_release(R); return code; };
-  hipError_t e = hipSuccess;
-  if (rows_bytes) {
-    if (!(R->d_in_rows = (u8*)ctx->dalloc(rows_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_filter_host: upload allocation failed"));
-    e = hipMemcpyAsync(R->d_in_rows, task->rows, rows_bytes, hipMemcpyHostToDevice, ctx->up);
-    dt.rows = R->d_in_rows;
-  }
-  if (!task->key_on_device && e == hipSuccess) {
-    if (key_bytes) {
-      if (!(R->d_in_key = (u8*)ctx->dalloc(key_bytes))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_filter_host: upload allocation failed"));
-      e = hipMemcpyAsync(R->d_in_key, task->key.recs, key_bytes, hipMemcpyHostToDevice, ctx->up);
-      dt.key.recs = R->d_in_key;
-    }
-    if (task->marks && task->key.n && e == hipSuccess) {
-      if (!(R->d_in_marks = (u8*)ctx->dalloc(task->key.n))) return fail(ctx->fail(KMX_E_NOMEM, "kmx_filter_host: upload allocation failed"));
-      e = hipMemcpyAsync(R->d_in_marks, task->marks, task->key.n, hipMemcpyHostToDevice, ctx->up);
-      dt.marks = R->d_in_marks; R->h_marks = task->marks;
-    }
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_filter_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = filter_queue(ctx, &dt, R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_filter_result_wait(kmx_filter_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  kmx_ctx* ctx = R->ctx;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = ctx->fail(KMX_E_HIP, std::string("kmx_filter: ") + hipGetErrorString(e));
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_filter_result_rows(kmx_filter_result* R) { return R && kmx_filter_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
-extern "C" uint64_t kmx_filter_result_row_bytes(const kmx_filter_result* R) { return R ? R->orb : 0; }
-extern "C" uint64_t kmx_filter_result_body_bytes(kmx_filter_result* R) { return R && (R->want & KMX_FILTER_M) ? kmx_filter_result_rows(R) * R->orb : 0; }
-extern "C" const void* kmx_filter_result_body_dev(kmx_filter_result* R) { return R && kmx_filter_result_wait(R) == KMX_OK ? R->d_out : nullptr; }
-extern "C" const void* kmx_filter_result_vector_dev(kmx_filter_result* R) { return R && (R->want & KMX_FILTER_V) && kmx_filter_result_wait(R) == KMX_OK ? R->d_vec : nullptr; }
-extern "C" uint64_t kmx_filter_result_vector_len(const kmx_filter_result* R) { return R && (R->want & KMX_FILTER_V) ? R->n_rows : 0; }
-extern "C" uint64_t kmx_filter_result_absent(kmx_filter_result* R) { return R && (R->want & KMX_FILTER_K) && kmx_filter_result_wait(R) == KMX_OK ? R->h_tot[1] : 0; }
-extern "C" const void* kmx_filter_result_absent_dev(kmx_filter_result* R) { return R && kmx_filter_result_wait(R) == KMX_OK ? R->d_absent : nullptr; }
-
-static int filter_copy_out(kmx_filter_result* R, void* dst, uint64_t dst_bytes, const void* src, u64 bytes)
-{
-  kmx_ctx* ctx = R->ctx;
-  if (dst_bytes < bytes) return ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!bytes) return KMX_OK;
-  if (!dst) return ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(ctx, dst, src, bytes);
-}
-extern "C" int kmx_filter_result_copy_body(kmx_filter_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_filter_result_wait(R);
-  return rc != KMX_OK ? rc : filter_copy_out(R, host_dst, dst_bytes, R->d_out, kmx_filter_result_body_bytes(R));
-}
-extern "C" int kmx_filter_result_copy_vector(kmx_filter_result* R, uint32_t* host_dst, uint64_t dst_entries)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_filter_result_wait(R);
-  return rc != KMX_OK ? rc : filter_copy_out(R, host_dst, dst_entries * 4, R->d_vec, 4ull * kmx_filter_result_vector_len(R));
-}
-extern "C" int kmx_filter_result_copy_absent(kmx_filter_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_filter_result_wait(R);
-  return rc != KMX_OK ? rc : filter_copy_out(R, host_dst, dst_bytes, R->d_absent, kmx_filter_result_absent(R) * (R->kw * 8 + 4));
-}
-extern "C" double kmx_filter_result_kernel_ms(kmx_filter_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_filter_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
-extern "C" uint64_t kmx_filter_result_algo_bytes(kmx_filter_result* R)
-{
-  if (!R || kmx_filter_result_wait(R) != KMX_OK) return 0;
-  const u64 rb = R->kw * 8 + 4;
-  u64 b = (u64)R->n_rows * 8 * R->kw + (u64)R->n_key * rb;
-  if (R->want & KMX_FILTER_M) b += (u64)R->h_tot[0] * (R->irb + R->orb);
-  if (R->want & KMX_FILTER_V) b += 4ull * R->n_rows;
-  if (R->want & KMX_FILTER_K) b += (u64)R->h_tot[1] * rb;
-  return b;
-}
-extern "C" void kmx_filter_result_free(kmx_filter_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  filter_release(R);
-}
-
-// ---- combine -----------------------------------------------------------------------------------------------------------------------
-// kmx_combine_dev / kmx_combine_host: the blocks of one partition (or of one key range of it) joined by key (combine.hip).
-struct kmx_combine_result {
-  kmx_ctx* ctx = nullptr;
-  u32 nb = 0, kw = 0, mode = 0, flags = 0, n_cols = 0, n_slots = 0;
-  u64 orb = 0, cap = 0, in_bytes = 0;
-  CombineBlock* h_desc = nullptr;      // page-locked: the blocks as the kernels see them (on their way up until the call has run)
-  CombineBlock* d_desc = nullptr;
-  u64 *d_keys = nullptr, *d_fbits = nullptr;
-  u32 *d_tcnt = nullptr, *d_src = nullptr, *d_tot = nullptr;
-  u8* d_out = nullptr;
-  std::vector<u8*> d_in;               // kmx_combine_host: the uploads
-  u32* h_tot = nullptr;                // page-locked: [0] output rows, [1] distinct keys
-  hipEvent_t ev_in = nullptr, ev_done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool waited = false; int status = KMX_OK;
-};
-
-static u64 combine_block_row_bytes(const kmx_combine_task* K, const kmx_block& b)
-{ return 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? (u64)b.n_cols * b.count_bytes : ((u64)b.n_cols + 7) / 8); }
-
-static int combine_check(kmx_ctx* ctx, const kmx_combine_task* K, const char* who, u64* orb, u64* cap, u64* n_cols)
-{
-  const std::string w(who);
-  if (K->key_words < 1 || K->key_words > 4) return ctx->fail(KMX_E_INVAL, w + ": key_words must be 1 ... 4");
-  if (K->mode == KMX_MODE_BF || K->mode == KMX_MODE_BFC || K->mode == KMX_MODE_BFT)
-    return ctx->fail(KMX_E_UNSUPPORTED, w + ": Bloom filter matrices are not combined (KMX_MODE_COUNT and KMX_MODE_PA rows only)");
-  if (K->mode != KMX_MODE_COUNT && K->mode != KMX_MODE_PA) return ctx->fail(KMX_E_INVAL, w + ": mode must be KMX_MODE_COUNT or KMX_MODE_PA");
-  if (K->flags & ~(u32)KMX_COMBINE_DROP_LAST) return ctx->fail(KMX_E_INVAL, w + ": unknown flag (KMX_COMBINE_DROP_LAST is the only one)");
-  if (K->n_blocks == 0) return ctx->fail(KMX_E_INVAL, w + ": a task has at least one block");
-  if (K->n_blocks > KMX_COMBINE_MAX_BLOCKS) return ctx->fail(KMX_E_UNSUPPORTED, w + ": " + std::to_string(K->n_blocks) + " blocks, at most " + std::to_string(KMX_COMBINE_MAX_BLOCKS) + " are combined in one call");
-  if (!K->blocks) return ctx->fail(KMX_E_INVAL, w + ": null block array");
-  u64 cols = 0, rows = 0;
-  for (u32 i = 0; i < K->n_blocks; i++) {
-    const kmx_block& b = K->blocks[i];
-    const std::string bi = w + ": block " + std::to_string(i);
-    if (b.n_cols == 0) return ctx->fail(KMX_E_INVAL, bi + ": a block has at least one column");
-    if (K->mode == KMX_MODE_COUNT && b.count_bytes != 1 && b.count_bytes != 2 && b.count_bytes != 4) return ctx->fail(KMX_E_INVAL, bi + ": count_bytes must be 1, 2 or 4");
-    if (b.n_rows && !b.rows) return ctx->fail(KMX_E_INVAL, bi + ": null row pointer");
-    if (b.n_rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, bi + ": more than 2^32 - 256 rows (combine the partition in key ranges)");
-    if (combine_block_row_bytes(K, b) > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, bi + ": rows of 4 GiB and more");
-    cols += b.n_cols; rows += b.n_rows;
-  }
-  *orb = 8ull * K->key_words + (K->mode == KMX_MODE_COUNT ? 4 * cols : (cols + 7) / 8);
-  if (*orb > 0xFFFFFFFFull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": output rows of 4 GiB and more");
-  // the output's rows are known on the device only; the blocks' rows together bound them
-  if (rows > 0xFFFFFF00ull) return ctx->fail(KMX_E_UNSUPPORTED, w + ": the blocks hold more than 2^32 - 256 rows together, the bound of the output's rows (combine the partition in key ranges)");
-  *cap = rows; *n_cols = cols;
-  return KMX_OK;
-}
-
-static void combine_release(kmx_combine_result* R)
-{
-  kmx_ctx* c = R->ctx;
-  void* blocks[] = {R->d_desc, R->d_keys, R->d_fbits, R->d_tcnt, R->d_src, R->d_tot, R->d_out};
-  for (void* p : blocks) c->dfree(p);
-  for (u8* p : R->d_in) c->dfree(p);
-  c->hfree(R->h_tot); c->hfree(R->h_desc);
-  for (hipEvent_t e : {R->ev_in, R->ev_done, R->ev0, R->ev1}) if (e) (void)hipEventDestroy(e);
-  delete R;
-}
-
-static kmx_combine_result* combine_new(kmx_ctx* ctx, const kmx_combine_task* K, u64 orb, u64 cap, u64 n_cols)
-{
-  kmx_combine_result* R = new kmx_combine_result();
-  R->ctx = ctx; R->nb = K->n_blocks; R->kw = K->key_words; R->mode = K->mode; R->flags = K->flags; R->orb = orb; R->cap = cap; R->n_cols = (u32)n_cols;
-  return R;
-}
-
-// the kernels of one call, queued on ctx->stream; rows[i]: block i's rows in device memory
-static int combine_queue(kmx_ctx* ctx, const kmx_combine_task* K, const void* const* rows, kmx_combine_result* R)
-{
-  hipStream_t st = ctx->stream;
-  const u32 nb = R->nb, kw = R->kw;
-  if (!(R->h_tot = (u32*)ctx->halloc(64)) || !(R->h_desc = (CombineBlock*)ctx->halloc(sizeof(CombineBlock) * nb)))
-    return ctx->fail(KMX_E_NOMEM, "kmx_combine: host allocation failed");
-  R->h_tot[0] = R->h_tot[1] = 0;
-  u64 key_off = 0; u32 pos = 0, toff = 0;
-  for (u32 i = 0; i < nb; i++) {
-    const kmx_block& b = K->blocks[i];
-    CombineBlock& d = R->h_desc[i];
-    d.rows = (const u8*)rows[i]; d.irb = combine_block_row_bytes(K, b); d.key_off = key_off;
-    d.n_rows = (u32)b.n_rows; d.n_cols = b.n_cols; d.cb = K->mode == KMX_MODE_COUNT ? b.count_bytes : 0; d.pos = pos; d.toff = toff;
-    d.ntiles = combine_tiles(d.n_rows);
-    key_off += b.n_rows; pos += b.n_cols; toff += d.ntiles + 1;
-    R->in_bytes += b.n_rows * d.irb;
-  }
-  R->n_slots = toff;
-  const u64 cap = R->cap;
-  R->d_desc = (CombineBlock*)ctx->dalloc(sizeof(CombineBlock) * nb);
-  R->d_tot = (u32*)ctx->dalloc(64);
-  R->d_tcnt = (u32*)ctx->dalloc(4ull * toff);
-  R->d_fbits = (u64*)ctx->dalloc(32ull * toff);
-  R->d_keys = (u64*)ctx->dalloc(8ull * kw * cap);
-  R->d_src = (u32*)ctx->dalloc(4ull * nb * cap);
-  R->d_out = (u8*)ctx->dalloc(cap * R->orb + 16);      // every key held by one block only
-  if (!R->d_desc || !R->d_tot || !R->d_tcnt || !R->d_fbits || !R->d_keys || !R->d_src || !R->d_out)
-    return ctx->fail(KMX_E_NOMEM, "kmx_combine: device allocation failed");
-  KMX_HIP(ctx, hipMemcpyAsync(R->d_desc, R->h_desc, sizeof(CombineBlock) * nb, hipMemcpyHostToDevice, st));
-  if (ctx->profiling) {
-    KMX_HIP(ctx, hipEventCreate(&R->ev0)); KMX_HIP(ctx, hipEventCreate(&R->ev1));
-    KMX_HIP(ctx, hipEventRecord(R->ev0, st));
-  }
-  KMX_HIP(ctx, hipMemsetAsync(R->d_tot, 0, 64, st));
-  if (cap) {
-    KMX_HIP(ctx, hipMemsetAsync(R->d_src, 0, 4ull * nb * cap, st));
-    KMX_HIP(ctx, launch_combine_keys((int)kw, R->d_desc, nb, toff, R->d_keys, st));
-    KMX_HIP(ctx, launch_combine_first((int)kw, R->d_desc, nb, toff, R->d_keys, R->d_tcnt, R->d_fbits, st));
-    KMX_HIP(ctx, launch_combine_scan(R->d_desc, nb, R->d_tcnt, st));
-    KMX_HIP(ctx, launch_combine_place((int)kw, R->d_desc, nb, toff, R->d_keys, R->d_tcnt, R->d_fbits, R->d_src, cap, st));
-    KMX_HIP(ctx, launch_combine_total(R->d_desc, nb, R->d_tcnt, R->d_src, cap, (R->flags & KMX_COMBINE_DROP_LAST) != 0, R->d_tot, st));
-    KMX_HIP(ctx, launch_combine_move(R->mode == KMX_MODE_PA, R->d_desc, nb, 8 * kw, R->n_cols, (u32)R->orb, R->d_src, cap, R->d_tot, R->d_out, st));
-  }
-  if (ctx->profiling) KMX_HIP(ctx, hipEventRecord(R->ev1, st));
-  KMX_HIP(ctx, hipMemcpyAsync(R->h_tot, R->d_tot, 8, hipMemcpyDeviceToHost, st));
-  KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_done, hipEventDisableTiming));
-  KMX_HIP(ctx, hipEventRecord(R->ev_done, st));
-  return KMX_OK;
-}
-
-extern "C" int kmx_combine_dev(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_combine_dev: null argument");
-  *out = nullptr;
-  u64 orb = 0, cap = 0, n_cols = 0;
-  int rc = combine_check(ctx, task, "kmx_combine_dev", &orb, &cap, &n_cols);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_combine_result* R = combine_new(ctx, task, orb, cap, n_cols);
-  std::vector<const void*> rows(task->n_blocks);
-  for (u32 i = 0; i < task->n_blocks; i++) rows[i] = task->blocks[i].rows;
-  if ((rc = combine_queue(ctx, task, rows.data(), R)) != KMX_OK) { (void)hipStreamSynchronize(ctx->stream); combine_release(R); return rc; }
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_combine_host(kmx_ctx* ctx, const kmx_combine_task* task, kmx_combine_result** out)
-{
-  if (!ctx) return KMX_E_INVAL;
-  if (!task || !out) return ctx->fail(KMX_E_INVAL, "kmx_combine_host: null argument");
-  *out = nullptr;
-  u64 orb = 0, cap = 0, n_cols = 0;
-  int rc = combine_check(ctx, task, "kmx_combine_host", &orb, &cap, &n_cols);
-  if (rc != KMX_OK) return rc;
-  KMX_HIP(ctx, hipSetDevice(ctx->device));
-  kmx_combine_result* R = combine_new(ctx, task, orb, cap, n_cols);
-  auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamSynchronize(ctx->stream); combine_release(R); return code; };
-  std::vector<const void*> rows(task->n_blocks);
-  hipError_t e = hipSuccess;
-  for (u32 i = 0; i < task->n_blocks && e == hipSuccess; i++) {
-    const kmx_block& b = task->blocks[i];
-    rows[i] = b.rows;
-    const u64 bytes = b.n_rows * combine_block_row_bytes(task, b);
-    if ((task->block_on_device && task->block_on_device[i]) || !bytes) continue;
-    u8* d = (u8*)ctx->dalloc(bytes);
-    if (!d) return fail(ctx->fail(KMX_E_NOMEM, "kmx_combine_host: upload allocation failed"));
-    R->d_in.push_back(d);
-    e = hipMemcpyAsync(d, b.rows, bytes, hipMemcpyHostToDevice, ctx->up);
-    rows[i] = d;
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-  if (e != hipSuccess) return fail(ctx->fail(KMX_E_HIP, std::string("kmx_combine_host: upload: ") + hipGetErrorString(e)));
-  if ((rc = combine_queue(ctx, task, rows.data(), R)) != KMX_OK) return fail(rc);
-  *out = R;
-  return KMX_OK;
-}
-
-extern "C" int kmx_combine_result_wait(kmx_combine_result* R)
-{
-  if (!R) return KMX_E_INVAL;
-  if (R->waited) return R->status;
-  R->waited = true;
-  const hipError_t e = hipEventSynchronize(R->ev_done);
-  if (e != hipSuccess) return R->status = R->ctx->fail(KMX_E_HIP, std::string("kmx_combine: ") + hipGetErrorString(e));
-  return R->status = KMX_OK;
-}
-extern "C" uint64_t kmx_combine_result_rows(kmx_combine_result* R) { return R && kmx_combine_result_wait(R) == KMX_OK ? R->h_tot[0] : 0; }
-extern "C" uint64_t kmx_combine_result_row_bytes(const kmx_combine_result* R) { return R ? R->orb : 0; }
-extern "C" uint64_t kmx_combine_result_body_bytes(kmx_combine_result* R) { return kmx_combine_result_rows(R) * (R ? R->orb : 0); }
-extern "C" const void* kmx_combine_result_body_dev(kmx_combine_result* R) { return R && kmx_combine_result_wait(R) == KMX_OK ? R->d_out : nullptr; }
-extern "C" uint64_t kmx_combine_result_algo_bytes(kmx_combine_result* R)
-{ return R && kmx_combine_result_wait(R) == KMX_OK ? R->in_bytes + (u64)R->h_tot[0] * R->orb : 0; }
-extern "C" int kmx_combine_result_copy_body(kmx_combine_result* R, void* host_dst, uint64_t dst_bytes)
-{
-  if (!R) return KMX_E_INVAL;
-  const int rc = kmx_combine_result_wait(R);
-  if (rc != KMX_OK) return rc;
-  const u64 bytes = kmx_combine_result_body_bytes(R);
-  if (dst_bytes < bytes) return R->ctx->fail(KMX_E_INVAL, "destination too small");
-  if (!bytes) return KMX_OK;
-  if (!host_dst) return R->ctx->fail(KMX_E_INVAL, "null destination");
-  return kmx_copy_to_host(R->ctx, host_dst, R->d_out, bytes);
-}
-extern "C" double kmx_combine_result_kernel_ms(kmx_combine_result* R)
-{
-  if (!R || !R->ev0 || !R->ev1 || kmx_combine_result_wait(R) != KMX_OK) return -1.0;
-  float ms = 0;
-  return hipEventElapsedTime(&ms, R->ev0, R->ev1) == hipSuccess ? (double)ms : -1.0;
-}
-extern "C" void kmx_combine_result_free(kmx_combine_result* R)
-{
-  if (!R) return;
-  (void)hipSetDevice(R->ctx->device);
-  if (R->ev_done) (void)hipEventSynchronize(R->ev_done);
-  combine_release(R);
 }

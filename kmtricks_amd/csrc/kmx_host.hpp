@@ -68,7 +68,7 @@ u32 bft_round_records(bool wide);
 u32 bft_fit_rows(u32 max_n, bool bits);
 hipError_t launch_merge_bft(const TaskDev* tasks, const uint2* items, u32 n_items, u32* ticket, u32 grid_x, u32 max_n, u32 rt_max, bool rec_bits, bool wide, u64* rem, u32 rem_cap, hipStream_t st);
 hipError_t launch_bit_transpose(const u8* in, u8* out, u64 nrows, u64 ncols, hipStream_t st);
-// filter.hip: the rows of a matrix joined with one sample's count list (kmx_filter_dev)
+// filter.hip: the rows of a matrix joined with one sample's count list (kmx_filter_dev; select, diff, assoc and unitigs place their rows with these too)
 u32 filter_tiles(u32 n);      // tiles of n rows / key records: the tile counters hold one entry more
 hipError_t launch_filter_match(int kw, const u8* rows, u32 n_rows, u64 irb, const u8* key, u32 n_key, int pa,
                                u32* hit, u32* vec, u8* marks, u32* tile_cnt, hipStream_t st);
@@ -77,25 +77,6 @@ hipError_t launch_filter_move(const u8* rows, u32 n_rows, u64 irb, u64 orb, cons
                               u8* out, hipStream_t st);
 hipError_t launch_filter_absent_count(const u8* marks, u32 n_key, u32* tile_cnt, hipStream_t st);
 hipError_t launch_filter_absent_scatter(int kw, const u8* key, const u8* marks, u32 n_key, const u32* tile_base, u8* out, hipStream_t st);
-// combine.hip: the matrices of several runs joined by key, block after block (kmx_combine_dev)
-struct CombineBlock {      // one block as the kernels see it (array in HBM)
-  const u8* rows;
-  u64 irb;                 // bytes of a row: key + payload
-  u64 key_off;             // rows of the blocks in front of it (its place in the dense key array)
-  u32 n_rows, n_cols;
-  u32 cb;                  // bytes of a count (COUNT)
-  u32 pos;                 // its first column in the output
-  u32 toff;                // its first tile slot: tiles + 1 slots a block (tile counts / bases with the total behind them, 4 u64 of bits a slot)
-  u32 ntiles;
-};
-u32 combine_tiles(u32 n);
-hipError_t launch_combine_keys(int kw, const CombineBlock* blocks, u32 nb, u32 n_slots, u64* keys, hipStream_t st);
-hipError_t launch_combine_first(int kw, const CombineBlock* blocks, u32 nb, u32 n_slots, const u64* keys, u32* tcnt, u64* fbits, hipStream_t st);
-hipError_t launch_combine_scan(const CombineBlock* blocks, u32 nb, u32* tcnt, hipStream_t st);
-hipError_t launch_combine_place(int kw, const CombineBlock* blocks, u32 nb, u32 n_slots, const u64* keys, u32* tcnt, u64* fbits, u32* src, u64 cap, hipStream_t st);
-hipError_t launch_combine_total(const CombineBlock* blocks, u32 nb, const u32* tcnt, const u32* src, u64 cap, int drop_last, u32* tot, hipStream_t st);
-hipError_t launch_combine_move(int pa, const CombineBlock* blocks, u32 nb, u32 kb, u32 n_cols, u32 orb, const u32* src, u64 cap, const u32* tot,
-                               u8* out, hipStream_t st);
 // the four sequence-query families; each file holds its C entry points below its kernels, their shared host path is seqquery_host.hpp
 // query.hip: query sequences against the Bloom matrices of a run (kmx_query_dev)
 void query_chunks(u64 n_bases, u32 n_parts, u32* n_tiles, u32* n_chunks, u32* tiles_per_chunk);      // the walk's layout: tiles of 64 positions, chunks of tiles (a wave each)

@@ -303,7 +303,7 @@ static int kset_check(kmx_ctx* ctx, const kmx_kset_task* T, const char* who)
   return KMX_OK;
 }
 
-static int kset_queue(kmx_ctx* ctx, const kmx_kset_task* T, kmx_kset* S, bool host)
+static int kset_queue(kmx_ctx* ctx, const kmx_kset_task* T, kmx_kset* S, bool host, const char* who)
 {
   hipStream_t st = ctx->stream;
   const u32 n = (u32)T->n, k = S->k = T->kmer_size, kw = S->kw = T->key_words;
@@ -315,11 +315,9 @@ static int kset_queue(kmx_ctx* ctx, const kmx_kset_task* T, kmx_kset* S, bool ho
   if (N) { S->d_keys = (u64*)S->keep(kbytes); S->d_table = (u64*)S->keep(8 * slots); }
   if (S->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_kset: device allocation failed (the set must fit one device)");
   if (N) {
-    if (host) {      // up on ctx->up, ctx->stream waits for it
-      KMX_HIP(ctx, hipMemcpyAsync(S->d_keys, T->keys, kbytes, hipMemcpyHostToDevice, ctx->up));
-      KMX_HIP(ctx, hipEventCreateWithFlags(&S->ev_in, hipEventDisableTiming));
-      KMX_HIP(ctx, hipEventRecord(S->ev_in, ctx->up));
-      KMX_HIP(ctx, hipStreamWaitEvent(st, S->ev_in, 0));
+    if (host) {
+      mat_upload(S, S->d_keys, T->keys, kbytes);
+      if (int rc = mat_uploads_done(S, who)) return rc;
     } else KMX_HIP(ctx, hipMemcpyAsync(S->d_keys, T->keys, kbytes, hipMemcpyDeviceToDevice, st));
   }
   int rc = mat_queue_head(S, 2);
@@ -346,11 +344,7 @@ static int kset_call(kmx_ctx* ctx, const kmx_kset_task* task, kmx_kset** out, bo
   KMX_HIP(ctx, hipSetDevice(ctx->device));
   kmx_kset* S = new kmx_kset();
   S->ctx = ctx; S->name = "kmx_kset"; S->n_rows = task->n; S->row_bytes = 8ull * task->key_words; S->n_cols = 0;
-  if ((rc = kset_queue(ctx, task, S, host)) == KMX_OK) { *out = S; return KMX_OK; }
-  if (host) (void)hipStreamSynchronize(ctx->up);
-  (void)hipStreamSynchronize(ctx->stream);
-  mat_release(S);
-  return rc;
+  return mat_finish(kset_queue(ctx, task, S, host, who), S, out, host);
 }
 extern "C" int kmx_kset_dev(kmx_ctx* ctx, const kmx_kset_task* task, kmx_kset** out) { return kset_call(ctx, task, out, false, "kmx_kset_dev"); }
 extern "C" int kmx_kset_host(kmx_ctx* ctx, const kmx_kset_task* task, kmx_kset** out) { return kset_call(ctx, task, out, true, "kmx_kset_host"); }
@@ -487,25 +481,13 @@ static int match_call(kmx_ctx* ctx, const kmx_match_task* task, kmx_match_result
   kmx_match_result* R = new kmx_match_result();
   R->ctx = ctx; R->name = "kmx_match"; R->n_rows = task->n_seqs; R->n_bases = n_bases;
   kmx_match_task dt = *task;
-  if (host) {      // up on ctx->up, ctx->stream waits for it; the blocks go back at wait
-    char* d_bases = (char*)R->tmp(std::max<u64>(n_bases, 1));
-    u64* d_offs = (u64*)R->tmp(8 * (task->n_seqs + 1));
-    if (R->nomem) rc = ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the reads in batches)");
-    else {
-      hipError_t e = n_bases ? hipMemcpyAsync(d_bases, task->bases, n_bases, hipMemcpyHostToDevice, ctx->up) : hipSuccess;
-      if (e == hipSuccess) e = hipMemcpyAsync(d_offs, task->offsets, 8 * (task->n_seqs + 1), hipMemcpyHostToDevice, ctx->up);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-      if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-      if (e != hipSuccess) rc = ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e));
-      dt.bases = d_bases; dt.offsets = (const uint64_t*)d_offs;
-    }
+  if (host) {      // the blocks go back at wait
+    dt.bases = (const char*)mat_upload_tmp(R, task->bases, n_bases);
+    dt.offsets = (const uint64_t*)mat_upload_tmp(R, task->offsets, 8 * (task->n_seqs + 1));
+    rc = R->nomem ? ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the reads in batches)") : mat_uploads_done(R, who);
   }
-  if (rc == KMX_OK && (rc = match_queue(ctx, &dt, R)) == KMX_OK) { *out = R; return KMX_OK; }
-  if (host) (void)hipStreamSynchronize(ctx->up);
-  (void)hipStreamSynchronize(ctx->stream);
-  mat_release(R);
-  return rc;
+  if (rc == KMX_OK) rc = match_queue(ctx, &dt, R);
+  return mat_finish(rc, R, out, host);
 }
 extern "C" int kmx_match_dev(kmx_ctx* ctx, const kmx_match_task* task, kmx_match_result** out) { return match_call(ctx, task, out, false, "kmx_match_dev"); }
 extern "C" int kmx_match_host(kmx_ctx* ctx, const kmx_match_task* task, kmx_match_result** out) { return match_call(ctx, task, out, true, "kmx_match_host"); }

@@ -1,7 +1,9 @@
-// matrix_host.hpp -- the host path the nine matrix-tool calls share (kmx_select_*, kmx_colsums_*, kmx_diff_*, kmx_dist_*, kmx_pan_*,
-// kmx_colors_*, kmx_gram_*, kmx_assoc_*, kmx_spectra_*): one matrix body goes in, tables, kept rows or records come out.  A family (select.hip, diff.hip,
-// dist.hip, pan.hip, colors.hip, gram.hip, assoc.hip, spectra.hip) keeps what is its own: its extra limits, its blocks and their sizes, its launches,
-// its formula for algo_bytes and its accessors.  Everything else is here, once.
+// matrix_host.hpp -- the host path the calls of libkmx share that take a matrix body (or a list of keys, or reads against a set) and give
+// tables, kept rows or records: kmx_select_*, kmx_colsums_*, kmx_diff_*, kmx_dist_*, kmx_pan_*, kmx_colors_*, kmx_gram_*, kmx_assoc_*,
+// kmx_spectra_* and kmx_groupsum_* through mat_call; kmx_filter_*, kmx_combine_*, kmx_unitigs_*, kmx_kset_* and kmx_match_* with an entry
+// of their own (their inputs are not one body) over the same parts.  A family (select.hip, diff.hip, dist.hip, pan.hip, colors.hip,
+// gram.hip, assoc.hip, spectra.hip, groupsum.hip; filter.hip, combine.hip, unitigs.hip, match.hip) keeps what is its own: its extra
+// limits, its blocks and their sizes, its launches, its formula for algo_bytes and its accessors.  Everything else is here, once.
 #pragma once
 #include "kmx_host.hpp"
 
@@ -11,7 +13,7 @@
 #pragma GCC visibility push(hidden)      // internal to libkmx: none of this joins the library's dynamic symbols
 namespace kmx {
 
-// what the nine result types have in common; kmx_select_result and its siblings derive from it
+// what the result types have in common; kmx_select_result and its siblings derive from it
 struct MatResult {
   kmx_ctx* ctx = nullptr;
   const char* name = "";                // "kmx_select", ...: leads the message of wait
@@ -20,6 +22,7 @@ struct MatResult {
   hipEvent_t ev_in = nullptr, ev_done = nullptr, ev[5] = {};      // ev: the first n_ev are the family's profiling events, start ... end
   int n_ev = 2;
   bool waited = false; int status = KMX_OK;
+  hipError_t up_err = hipSuccess;       // _host calls: the first upload that failed (mat_upload)
   void* d_in = nullptr;                 // _host calls: the upload
   std::vector<void*> scratch, owned;    // pool blocks that go back at wait / at free; a table the caller handed in is on neither
   bool nomem = false;                   // a block of the two lists could not be had
@@ -91,9 +94,40 @@ template <class Result> void mat_release(Result* R)
   delete R;
 }
 
+// ---- a _host call's inputs on their way up: every copy on ctx->up, then ctx->stream waits for them all.  An error stays with R
+//      (the copies behind it are not queued) and is mat_uploads_done's refusal ----
+inline void mat_upload(MatResult* R, void* dst, const void* src, u64 bytes)
+{
+  if (R->up_err == hipSuccess && bytes) R->up_err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, R->ctx->up);
+}
+// ... into a scratch block of its own, which goes back at wait; nullptr: none to be had (R->nomem)
+inline void* mat_upload_tmp(MatResult* R, const void* src, u64 bytes)
+{
+  void* d = R->tmp(bytes);
+  if (d) mat_upload(R, d, src, bytes);
+  return d;
+}
+inline int mat_uploads_done(MatResult* R, const char* who)
+{
+  kmx_ctx* ctx = R->ctx;
+  hipError_t e = R->up_err;
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
+  return e == hipSuccess ? KMX_OK : ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e));
+}
+// the end of every entry point: R handed out, or both streams (host: ctx->up too) waited for and R released
+template <class Result> int mat_finish(int rc, Result* R, Result** out, bool host)
+{
+  if (rc == KMX_OK) { *out = R; return KMX_OK; }
+  if (host) (void)hipStreamSynchronize(R->ctx->up);
+  (void)hipStreamSynchronize(R->ctx->stream);
+  mat_release(R);
+  return rc;
+}
+
 // ---- the entry point: null arguments, the family's check (it gives the bytes of a row), a new result, for a _host call the body
-//      (n_rows * row_bytes bytes) up on ctx->up with ctx->stream waiting for it, the family's queue.  On failure both streams (host:
-//      ctx->up too) are waited for and the result is released.  who: "kmx_select_dev", ...; name: "kmx_select", ... ----
+//      (n_rows * row_bytes bytes) up, the family's queue.  who: "kmx_select_dev", ...; name: "kmx_select", ... ----
 template <class Result, class Task>
 int mat_call(kmx_ctx* ctx, const Task* task, Result** out, bool host, const char* who, const char* name,
              int (*check)(kmx_ctx*, const Task*, const char*, u64*), int (*queue)(kmx_ctx*, const Task*, Result*))
@@ -112,19 +146,13 @@ int mat_call(kmx_ctx* ctx, const Task* task, Result** out, bool host, const char
   if (host && bytes) {
     if (!(R->d_in = ctx->dalloc(bytes))) rc = ctx->fail(KMX_E_NOMEM, std::string(who) + ": upload allocation failed (send the body in runs of rows)");
     else {
-      hipError_t e = hipMemcpyAsync(R->d_in, task->rows, bytes, hipMemcpyHostToDevice, ctx->up);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(R->ev_in, ctx->up);
-      if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, R->ev_in, 0);
-      if (e != hipSuccess) rc = ctx->fail(KMX_E_HIP, std::string(who) + ": upload: " + hipGetErrorString(e));
+      mat_upload(R, R->d_in, task->rows, bytes);
+      rc = mat_uploads_done(R, who);
       dt.rows = R->d_in;
     }
   }
-  if (rc == KMX_OK && (rc = queue(ctx, &dt, R)) == KMX_OK) { *out = R; return KMX_OK; }
-  if (host) (void)hipStreamSynchronize(ctx->up);
-  (void)hipStreamSynchronize(ctx->stream);
-  mat_release(R);
-  return rc;
+  if (rc == KMX_OK) rc = queue(ctx, &dt, R);
+  return mat_finish(rc, R, out, host);
 }
 
 // ---- X_queue: the family takes its buffers and blocks (R->pin, R->tmp, R->keep) and uploads its tables, then mat_queue_head, its clears

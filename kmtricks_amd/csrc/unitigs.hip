@@ -381,7 +381,7 @@ static int unitigs_check(kmx_ctx* ctx, const kmx_unitigs_task* T, const char* wh
   return KMX_OK;
 }
 
-static int unitigs_queue(kmx_ctx* ctx, const kmx_unitigs_task* T, kmx_unitigs_result* R, bool host)
+static int unitigs_queue(kmx_ctx* ctx, const kmx_unitigs_task* T, kmx_unitigs_result* R, bool host, const char* who)
 {
   hipStream_t st = ctx->stream;
   const u32 n = (u32)T->n, k = R->k = T->kmer_size, kw = R->kw = T->key_words;
@@ -406,11 +406,9 @@ static int unitigs_queue(kmx_ctx* ctx, const kmx_unitigs_task* T, kmx_unitigs_re
   }
   if (R->nomem) return ctx->fail(KMX_E_NOMEM, "kmx_unitigs: device allocation failed");
   if (n) {
-    if (host) {      // up on ctx->up, ctx->stream waits for it
-      KMX_HIP(ctx, hipMemcpyAsync(R->d_keys, T->keys, kbytes, hipMemcpyHostToDevice, ctx->up));
-      KMX_HIP(ctx, hipEventCreateWithFlags(&R->ev_in, hipEventDisableTiming));
-      KMX_HIP(ctx, hipEventRecord(R->ev_in, ctx->up));
-      KMX_HIP(ctx, hipStreamWaitEvent(st, R->ev_in, 0));
+    if (host) {
+      mat_upload(R, R->d_keys, T->keys, kbytes);
+      if (int rc = mat_uploads_done(R, who)) return rc;
     } else KMX_HIP(ctx, hipMemcpyAsync(R->d_keys, T->keys, kbytes, hipMemcpyDeviceToDevice, st));
   }
   int rc = mat_queue_head(R, 5);      // ev: start, behind the table, behind the links, behind the ranking, end
@@ -477,11 +475,7 @@ static int unitigs_call(kmx_ctx* ctx, const kmx_unitigs_task* task, kmx_unitigs_
   KMX_HIP(ctx, hipSetDevice(ctx->device));
   kmx_unitigs_result* R = new kmx_unitigs_result();
   R->ctx = ctx; R->name = "kmx_unitigs"; R->n_rows = task->n; R->row_bytes = 8ull * task->key_words; R->n_cols = 0;
-  if ((rc = unitigs_queue(ctx, task, R, host)) == KMX_OK) { *out = R; return KMX_OK; }
-  if (host) (void)hipStreamSynchronize(ctx->up);
-  (void)hipStreamSynchronize(ctx->stream);
-  mat_release(R);
-  return rc;
+  return mat_finish(unitigs_queue(ctx, task, R, host, who), R, out, host);
 }
 
 extern "C" int kmx_unitigs_dev(kmx_ctx* ctx, const kmx_unitigs_task* task, kmx_unitigs_result** out) { return unitigs_call(ctx, task, out, false, "kmx_unitigs_dev"); }

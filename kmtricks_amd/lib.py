@@ -1645,49 +1645,6 @@ class CombineOutput:
         self.body, self.rows, self.row_bytes, self.kernel_ms, self.algo_bytes = body, rows, row_bytes, kernel_ms, algo_bytes
 
 
-class CombineResult:
-    def __init__(self, ctx, h):
-        self._ctx, self._h = ctx, h
-
-    def wait(self):
-        self._ctx._check(_lib.kmx_combine_result_wait(self._h), "kmx_combine_result_wait")
-
-    def rows(self):
-        return _lib.kmx_combine_result_rows(self._h)
-
-    def row_bytes(self):
-        return _lib.kmx_combine_result_row_bytes(self._h)
-
-    def body_dev(self):
-        return _lib.kmx_combine_result_body_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_combine_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_combine_result_algo_bytes(self._h)
-
-    def body(self):
-        self.wait()
-        buf = np.zeros(_lib.kmx_combine_result_body_bytes(self._h), np.uint8)
-        self._ctx._check(_lib.kmx_combine_result_copy_body(self._h, buf.ctypes.data, len(buf)), "kmx_combine_result_copy_body")
-        return buf.tobytes()
-
-    def output(self):
-        return CombineOutput(self.body(), self.rows(), self.row_bytes(), self.kernel_ms(), self.algo_bytes())
-
-    def free(self):
-        if self._h:
-            _lib.kmx_combine_result_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
 class QueryOutput:
     """n_kmers uint32[queries]: positions with a valid k-mer; hits uint32[queries, n_cols]: those whose row has the sample's bit set
     (the table the call added to, when one was given); kernel_ms < 0 without set_profiling"""
@@ -2215,50 +2172,50 @@ class FilterOutput:
         self.absent_keys, self.absent_counts = absent_keys, absent_counts
 
 
-class FilterResult:
-    def __init__(self, ctx, h, key_words):
-        self._ctx, self._h, self._kw = ctx, h, key_words
+class FilterResult(_Result):
+    _prefix = "filter"
 
-    def wait(self):
-        self._ctx._check(_lib.kmx_filter_result_wait(self._h), "kmx_filter_result_wait")
+    def __init__(self, ctx, h, key_words):
+        super().__init__(ctx, h)
+        self._kw = key_words
 
     def rows(self):
-        return _lib.kmx_filter_result_rows(self._h)
+        return self._call("rows")
 
     def row_bytes(self):
-        return _lib.kmx_filter_result_row_bytes(self._h)
+        return self._call("row_bytes")
 
     def body_dev(self):
-        return _lib.kmx_filter_result_body_dev(self._h)
-
-    def kernel_ms(self):
-        return _lib.kmx_filter_result_kernel_ms(self._h)
-
-    def algo_bytes(self):
-        return _lib.kmx_filter_result_algo_bytes(self._h)
+        return self._call("body_dev")
 
     def output(self):
         self.wait()
-        body = np.zeros(_lib.kmx_filter_result_body_bytes(self._h), np.uint8)
-        self._ctx._check(_lib.kmx_filter_result_copy_body(self._h, body.ctypes.data, len(body)), "kmx_filter_result_copy_body")
-        vec = np.zeros(_lib.kmx_filter_result_vector_len(self._h), np.uint32)
-        self._ctx._check(_lib.kmx_filter_result_copy_vector(self._h, vec.ctypes.data, len(vec)), "kmx_filter_result_copy_vector")
-        n, w = _lib.kmx_filter_result_absent(self._h), self._kw * 2 + 1
-        rec = np.zeros((n, w), np.uint32)
-        self._ctx._check(_lib.kmx_filter_result_copy_absent(self._h, rec.ctypes.data, rec.nbytes), "kmx_filter_result_copy_absent")
+        body = self._copy("body", np.zeros(self._call("body_bytes"), np.uint8))
+        vec = self._copy("vector", np.zeros(self._call("vector_len"), np.uint32))
+        n, w = self._call("absent"), self._kw * 2 + 1
+        rec = self._copy("absent", np.zeros(n * w * 4, np.uint8)).view(np.uint32).reshape(n, w)
         keys = np.ascontiguousarray(rec[:, :self._kw * 2]).view(np.uint64).reshape(n, self._kw)
         return FilterOutput(body.tobytes(), self.rows(), self.row_bytes(), vec, keys, rec[:, self._kw * 2].copy())
 
-    def free(self):
-        if self._h:
-            _lib.kmx_filter_result_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+class CombineResult(_Result):
+    _prefix = "combine"
+
+    def rows(self):
+        return self._call("rows")
+
+    def row_bytes(self):
+        return self._call("row_bytes")
+
+    def body_dev(self):
+        return self._call("body_dev")
+
+    def body(self):
+        self.wait()
+        return self._copy("body", np.zeros(self._call("body_bytes"), np.uint8)).tobytes()
+
+    def output(self):
+        return CombineOutput(self.body(), self.rows(), self.row_bytes(), self.kernel_ms(), self.algo_bytes())
 
 
 class MergeResult:
