@@ -29,8 +29,8 @@
 // for every key, kept or not, as the reference accumulates them).  Recurrence-min 0 takes the same builds: a key only non-solid
 // records hold is a row of zeros there.
 // Applicable to COUNT and PA rows, 64- and 128-bit keys, share-min <= max(1, recurrence-min) (count rows: any share-min, with k_share_fix
-// of kmx_api.hip behind the pair); chosen from 192 lists and recurrence-min <= 21
-// (the row keys come from 8..32 of the lists, more for a larger recurrence-min: cols_row_lists in kmx_api.hip).
+// of merge_host.hip behind the pair); chosen from 192 lists and recurrence-min <= 21
+// (the row keys come from 8..32 of the lists, more for a larger recurrence-min: cols_row_lists in merge_host.hip).
 #include "kmx_host.hpp"
 #include <algorithm>
 #include <cstdio>
@@ -38,7 +38,7 @@
 
 // This file is compiled twice: as it is for 64-bit keys (k <= 31, hashes), and through merge_cols_k2.hip with KMX_CL_KW = 2 for
 // 128-bit keys (32 <= k <= 63: 5-dword records, 8-slot windows, one 32-byte-entry row table).  Each build lives in its own
-// namespace and hands kmx_api.hip its entry points through a ColsOps table.
+// namespace and hands merge_host.hip its entry points through a ColsOps table.
 #ifndef KMX_CL_KW
 #define KMX_CL_KW 1
 #endif

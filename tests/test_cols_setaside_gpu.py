@@ -8,14 +8,14 @@ hold records 8 apart in its list -- a run of 9, 17 or 25 consecutive records tha
 into one group of some lane.  A wave is eight lists; its slice of half a tile takes 128 entries, the extension 384 more.
 
 Every task has ONE key range, so tile t of a task is row keys 112 t ... 112 t + 111 and its halves split at row key 112 t + 56.
-How many ranges a task gets is libkmx's choice (work items wanted / tasks of the batch / column blocks, kmx_api.hip): with
+How many ranges a task gets is libkmx's choice (work items wanted / tasks of the batch / column blocks, merge_host.hip): with
 KMX_ITEMS_PER_SLOT=1 it wants 256 work items on 256 CUs, and a batch of at least 64 tasks over five (three) column blocks leaves each
 task one range -- so every batch here is its sets repeated to 64 tasks or more (the same device lists), as in
 test_cols_seeds_gpu.py.  Where the geometry shows from outside it is asserted: 128 entries in one half of a tile complete on the
 plain build and 129 do not, 100 in either half of one tile do, 512 fit the EXT build and 513 do not.
 
 The lists are built here key by key: the row keys are the pool keys (nearly every list holds each of them, so the few lists
-libkmx merges first -- `witnesses`, the same choice as kmx_api.hip's -- agree on them), and everything a case adds goes into
+libkmx merges first -- `witnesses`, the same choice as merge_host.hip's -- agree on them), and everything a case adds goes into
 lists that are no witnesses, next to a chosen row key.  No list has keys of its own unless a case gives it some (`sprinkle`:
 the everyday records for the slices, in lists that are no witnesses), so the row keys are exactly the pool keys.  (Were libkmx
 to choose other lists, the asserts on the kernels' names in the slice tests would fail: they hold only with these tiles.)
@@ -35,7 +35,7 @@ _oracle = {}
 
 
 def cols_row_lists(rec_min):
-    """how many lists the row keys are taken from (kmx_api.hip)"""
+    """how many lists the row keys are taken from (merge_host.hip)"""
     for s in range(max(8, rec_min + 2), 33):
         p = 1.0
         for i in range(s - rec_min + 1):

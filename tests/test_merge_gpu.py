@@ -491,7 +491,7 @@ def test_cols_kept_key_outside_the_row_keys():
         k, c = lists[i]
         k2 = np.concatenate([k, extra]); c2 = np.concatenate([c, np.array([7], np.uint32)])
         o = np.argsort(k2[:, 0]); lists[i] = (np.ascontiguousarray(k2[o]), np.ascontiguousarray(c2[o]))
-    # the 8 merged lists: the one of median length (ties: lower index) in each eighth of the task (kmx_api.hip)
+    # the 8 merged lists: the one of median length (ties: lower index) in each eighth of the task (merge_host.hip)
     lens = [len(c) for _, c in lists]
     sampled = set()
     for i in range(8):
